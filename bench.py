@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the plmDCA / mfDCA hot path on MI355X (contract: see the task prompt).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload D|C|E]
+    python bench.py [--gpus N --steps K --warmup W] [--workload D|C|E] [--dump-outputs DIR]
 
 A "step" is one L-BFGS iteration of plmDCA (line search included: ~1.0-1.2 objective +
 gradient evaluations) on the synthetic protein alignment L=500, N=50k, q=21 (config D of
 BASELINE.json / SURVEY.md section 8), lambda_h=1, lambda_J=50, seqid 0.8, resident in HBM.
 N>1: sequences are sharded over the ranks, every evaluation ends with one RCCL all-reduce
 of the gradient (strong scaling: total work fixed).  Rank 0 prints ONE JSON line.
+
+--dump-outputs DIR writes what the timed path computed in its last timed step, as a caller receives it, to DIR/<name>.npy
+(float32 with --precision 32, float64 otherwise): plm_x and plm_g, the parameters and the gradient at them, and plm_lbfgs =
+[fx, xnorm, gnorm, step, iterations, evaluations]; with the mfDCA leg also mfdca_scores, its FN_APC scores.  A parameter
+vector longer than DUMP_SAMPLE elements is cut to a fixed, seeded sample of them; plm_index then holds the sampled
+positions.  The inputs are seeded, so two builds run with the same arguments can be compared file for file.
 """
 import argparse
 import json
@@ -28,6 +34,27 @@ WORKLOADS = {
 }
 HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 LDS_PEAK_GBS = 256 * 256 * 2.4    # 256 B/clk/CU x 256 CUs x 2.4 GHz = 157 TB/s (MI355X_MICROARCH.md, LDS)
+DUMP_SAMPLE = 1 << 21             # --dump-outputs: elements kept of a parameter vector (config D has 55 M)
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: all files together
+DUMP_NAMES = ("plm_x", "plm_g", "plm_index", "plm_lbfgs", "mfdca_scores")
+
+
+def dump_index(P):
+    """Positions of a P-vector that --dump-outputs keeps: all of them up to DUMP_SAMPLE, else a fixed seeded sample."""
+    if P <= DUMP_SAMPLE:
+        return None
+    return np.sort(np.random.default_rng(0).choice(P, DUMP_SAMPLE, replace=False))
+
+
+def dump_path(directory, name):
+    assert name in DUMP_NAMES, name
+    return os.path.join(directory, name + ".npy")
+
+
+def write_dump(directory, name, a):
+    os.makedirs(directory, exist_ok=True)
+    assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+    np.save(dump_path(directory, name), a)
 
 
 def kernel_sources_fingerprint():
@@ -333,7 +360,15 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=0)
     ap.add_argument("--cpu-full", action="store_true",
                     help="also time ONE full evaluation of the reference C++/OpenMP on all sequences (about a minute at config D) and report it beside the fit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and int(os.environ.get("RANK", "0")) == 0:
+        for name in DUMP_NAMES:             # a file this run does not write must not be left from an earlier one
+            if os.path.exists(dump_path(args.dump_outputs, name)):
+                os.remove(dump_path(args.dump_outputs, name))
 
     # DCA_BENCH_SELFTEST: several ranks on ONE GPU (tests): "1" = gloo + torch.distributed hooks; "native" = the library's
     # own communicators over the stand-in librccl named by DCA_RCCL_PATH (tests/fake_rccl/libfake_rccl_mp.so), i.e. the
@@ -556,41 +591,73 @@ def main():
     # ---- warm-up iterations, then exactly K timed iterations
     total_cap = args.warmup + args.steps
     ctx.plm_lbfgs_begin(total_cap + 1000)
-    st = ctx.plm_lbfgs_iterate(args.warmup) if args.warmup > 0 else None
-    it0 = st.iterations if st else 0
-    ev0 = st.evaluations if st else 1
+    last = [None]                 # stats of the latest iterate call; None right after plm_lbfgs_begin
+
+    def iterate(n, profile=None):
+        """n L-BFGS iterations -> (stats, seconds, iterations, evaluations).  The optimisation ends by itself after some
+        hundreds of iterations (config D: libLBFGS -1001, a rounding error in the line search, after about 740); it then starts
+        again from the initial point, off the clock and unprofiled, so that exactly n iterations of the same workload run.
+        `profile` (re)sets how the stages are clocked while it iterates."""
+        secs, its, evs = 0.0, 0, 0
+        while its < n:
+            if last[0] is not None and last[0].finished:
+                ctx.set_profiling(False)
+                if world == 1:
+                    ctx.plm_init_x()
+                else:
+                    ctx.plm_set_x(parallel.initial_x(X, w32, q, np.float32))
+                ctx.plm_lbfgs_begin(total_cap + 1000)
+                last[0] = None
+            if profile is not None:
+                profile()
+            i0, e0 = (last[0].iterations, last[0].evaluations) if last[0] is not None else (0, 1)
+            barrier()
+            t1 = time.perf_counter()
+            st = ctx.plm_lbfgs_iterate(n - its)
+            barrier()
+            secs += time.perf_counter() - t1
+            if st.iterations == i0 and last[0] is None:
+                raise SystemExit("bench.py: L-BFGS ends at its initial point (libLBFGS status %d)" % st.status)
+            its += st.iterations - i0
+            evs += st.evaluations - e0
+            last[0] = st
+        return last[0], secs, its, evs
+
+    iterate(args.warmup)
     # The timed region carries HIP events around ONE stage only -- the roofline's kernel (the gather stage that dominates: scatter
     # at q = 21, logits on the site-pair alphabet of q = 5).  An event record costs the stream ~5 us; two per stage and seven stages
     # per iteration were 5 % of config C's step and 4 % of E's (0.4 % of D's) -- the instrument, not the path.  The other stages are
     # clocked over the same number of iterations right after the timed region (`kernel_clock_pass`).
     roof_stage = "plm_scatter" if q == 21 else "plm_logits"
-    ctx.set_profiling_only(roof_stage)
     ctx.reset_kernel_times()
-    barrier()
-    t0 = time.perf_counter()
-    st = ctx.plm_lbfgs_iterate(args.steps)
-    barrier()
-    dt = time.perf_counter() - t0
+    st, dt, steps_done, evals = iterate(args.steps, lambda: ctx.set_profiling_only(roof_stage))
     per_rank_ms = None
     if dist is not None:
         tall = [torch.zeros(1, dtype=torch.float64, device=tdev) for _ in range(world)]
         dist.all_gather(tall, torch.tensor([dt], dtype=torch.float64, device=tdev))
         per_rank_ms = [float(t.item()) / max(args.steps, 1) * 1e3 for t in tall]       # every rank's own clock around the same K iterations
         dt = max(float(t.item()) for t in tall)
-    steps_done = st.iterations - it0
-    evals = st.evaluations - ev0
     roof_time = ctx.kernel_time(roof_stage)               # over the timed region
+    if args.dump_outputs:
+        # before the clock pass below moves the optimiser on; get_x / get_g are collective on a sharded context
+        vdt = np.float32 if args.precision == 32 else np.float64
+        sel = dump_index(ctx.num_params())
+        x_last, g_last = ctx.plm_get_x(vdt), ctx.plm_get_g(vdt)
+        if rank == 0:
+            if sel is not None:
+                x_last, g_last = x_last[sel], g_last[sel]
+                write_dump(args.dump_outputs, "plm_index", sel.astype(np.float64))
+            write_dump(args.dump_outputs, "plm_x", x_last)
+            write_dump(args.dump_outputs, "plm_g", g_last)
+            write_dump(args.dump_outputs, "plm_lbfgs", np.array([st.fx, st.xnorm, st.gnorm, st.step, st.iterations, st.evaluations],
+                                                                dtype=np.float64))
+        del x_last, g_last
     # the same number of iterations again with every stage clocked (not part of `value`); the optimiser simply goes on
-    ctx.set_profiling(True)
     ctx.reset_kernel_times()
-    barrier()
-    tk = time.perf_counter()
-    st2 = ctx.plm_lbfgs_iterate(args.steps)
-    barrier()
-    clock_pass = {"steps": st2.iterations - st.iterations, "ms_per_step": (time.perf_counter() - tk) / max(st2.iterations - st.iterations, 1) * 1e3,
+    _, secs_clocked, steps_clocked, _ = iterate(args.steps, lambda: ctx.set_profiling(True))
+    clock_pass = {"steps": steps_clocked, "ms_per_step": secs_clocked / steps_clocked * 1e3,
                   "what": "every stage bracketed with HIP events (14 event records per iteration); the timed region brackets only %s" % roof_stage}
     ktimes = {tag: ctx.kernel_time(tag) for tag in ("plm_expand", "plm_logits", "plm_softmax", "plm_scatter", "plm_fold", "lbfgs_vec")}
-    steps_clocked = max(st2.iterations - st.iterations, 1)
     if roof_time[1] > 0:
         ktimes[roof_stage] = roof_time
     ctx.set_profiling(False)
@@ -761,6 +828,8 @@ def main():
             order = mctx.scores_order()          # ranked on the device (stable radix sort)
             if rep:
                 samples.append(time.perf_counter() - t0)
+        if args.dump_outputs:
+            write_dump(args.dump_outputs, "mfdca_scores", np.asarray(scores, dtype=np.float64))
         t_mf = float(np.median(samples))
         npairs = L * (L - 1) // 2
         out["mfdca"] = {"pairs_per_s": npairs / t_mf, "seconds": t_mf, "statistic": "median of the timed passes", "samples_s": samples,
@@ -865,6 +934,10 @@ def main():
         raise SystemExit("bench.py: measured %d rank(s) for --gpus %d" % (out["n_gpus"], args.gpus))
     if comm_selection is not None and comm_selection["rccl_ranks"] != world:
         raise SystemExit("bench.py: the RCCL communicator has %d ranks, expected %d" % (comm_selection["rccl_ranks"], world))
+    if args.dump_outputs:
+        dumped = sum(os.path.getsize(dump_path(args.dump_outputs, n)) for n in DUMP_NAMES if os.path.exists(dump_path(args.dump_outputs, n)))
+        if dumped > DUMP_LIMIT_BYTES:
+            raise SystemExit("bench.py: %d bytes under %s, more than the %d allowed" % (dumped, args.dump_outputs, DUMP_LIMIT_BYTES))
     print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -724,6 +724,50 @@ def test_bench_native_path_two_processes(scheme):
     assert abs(d2["speedup_vs_single_gpu_same_run"] - d2["value"] / one_gpu["iterations_per_s"]) < 1e-9
 
 
+def test_bench_dump_outputs_are_what_the_timed_path_computed(tmp_path):
+    """bench.py --dump-outputs at config C (8.8 M parameters: the seeded sample): after exactly --steps timed iterations it
+    writes x and g of the last step, the optimiser's scalars and the mfDCA scores, within 64 MB -- bit for bit what the same
+    path gives when a caller drives the library directly."""
+    import json
+    import subprocess
+    import bench
+    from pydca_amd import _lib
+    from tools.gen_msa import dedup, generate
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "C",
+                        "--no-cpu-baseline", "--no-e2e", "--no-modes", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    files = {n: str(out / (n + ".npy")) for n in bench.DUMP_NAMES}
+    assert sum(os.path.getsize(f) for f in files.values()) <= bench.DUMP_LIMIT_BYTES
+    D = {n: np.load(f) for n, f in files.items()}
+    assert D["plm_x"].dtype == D["plm_g"].dtype == np.float32
+    assert D["plm_index"].dtype == D["plm_lbfgs"].dtype == D["mfdca_scores"].dtype == np.float64
+    L, N, q, seed, lh, lJ = bench.WORKLOADS["C"]
+    X = dedup(generate(L, N, q, seed))
+    ctx = _lib.Context(0, _lib.DCA_F32)
+    ctx.set_msa(X, q)
+    ctx.compute_weights(0.8, _lib.DCA_F32)
+    ctx.plm_configure(lh, lJ, _lib.CARRY_CHUNKED)
+    ctx.plm_init_x()
+    ctx.plm_lbfgs_begin(1 + 3 + 1000)
+    ctx.plm_lbfgs_iterate(1)
+    st = ctx.plm_lbfgs_iterate(3)
+    idx = bench.dump_index(ctx.num_params())
+    assert idx is not None and np.array_equal(D["plm_index"], idx)
+    assert np.array_equal(D["plm_x"], ctx.plm_get_x(np.float32)[idx])
+    assert np.array_equal(D["plm_g"], ctx.plm_get_g(np.float32)[idx])
+    assert np.array_equal(D["plm_lbfgs"], [st.fx, st.xnorm, st.gnorm, st.step, st.iterations, st.evaluations])
+    ctx.close()
+    m = _lib.Context(0, _lib.DCA_F64)
+    m.set_msa(X, q)
+    m.compute_weights(0.8, _lib.DCA_F64)
+    assert np.array_equal(D["mfdca_scores"], m.mf_run(0.5, True))
+    m.close()
+
+
 def test_msa_numerics_direct_information_functions():
     """Module-level DI functions of both msa_numerics mirrors against the
     reference's own output (goldens): two-site model fields and DI from caller-provided arrays."""
