@@ -88,6 +88,14 @@ int dca_read_fasta(const char* path, int biomolecule, int L, uint8_t* out, int c
 int dca_read_fasta_alloc(const char* path, int biomolecule, uint8_t** rows, int* L_out, int* raw_count);
 void dca_host_free(void* p);
 
+/* Query sequences for the energy entries (no reference counterpart): record k is seqs[offsets[k] .. offsets[k+1]) (offsets
+ * has nseq + 1 entries), encoded into out (nseq x L bytes, 0-based codes, gap = q-1) in input order, nothing de-duplicated.
+ * table 0: the residue table of dca_read_msa -- a character that reader rejects is DCA_ERR_RESIDUE; table 1: the table of
+ * dca_read_fasta -- every unknown character is the gap state.  A record of a length other than L is DCA_ERR_ARG.  On either
+ * error *bad_record (may be NULL) receives the 0-based index of the offending record (-1 otherwise). */
+int dca_encode_sequences(const char* seqs, const int* offsets, int nseq, int biomolecule, int table /* 0: plm, 1: mf */,
+                         int L, uint8_t* out, int* bad_record);
+
 /* ------------------------------------------------------------------ reference-sequence back-mapping (host)
  * Local pairwise alignment, Smith-Waterman with affine gaps (a gap of length n costs
  * gap_open + (n-1)*gap_extend), standing in for Bio.pairwise2.align.localds as called by
@@ -298,6 +306,20 @@ int dca_plm_di_scores(dca_ctx* ctx, const double* reg_fi, int apc, double* score
  * (plmdca.py:320-342).  Feeds PlmDCA.compute_params (plmdca.py:345-434). */
 int dca_plm_pair_couplings(dca_ctx* ctx, const int* pairs, int npairs, int shift, double* out);
 
+/* Statistical energies of n query sequences X (n x L codes < q, gap = q-1; host) under the current x:
+ *   E(s) = sum_i h_i(s_i) + sum_{i<j} J_ij(s_i, s_j)
+ * with h and J the parameter vector exactly as stored (fields L*q first, then the q x q blocks in pair order; gap state
+ * included; float32 values in the float32 mode, float64 in the float64 mode).  Higher is more probable.  Every term is
+ * widened to double and summed in double in an order fixed by (L, q, precision) alone: a sequence's energy is bitwise the
+ * same whatever n, its position among the queries, or the call.  The query rows go to a buffer of their own; the context's
+ * alignment, weights and optimiser state are not touched.  n == 0 is DCA_OK; a code >= q is DCA_ERR_ARG; DCA_ERR_STATE before
+ * dca_plm_configure.  Column strips: collective, like dca_plm_scores.  No reference counterpart (pydca only ranks pairs). */
+int dca_plm_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out);
+/* Single-mutant effects of the wild type w (L codes): dE[i*q + a] = E(w with w_i -> a) - E(w)
+ *   = h_i(a) - h_i(w_i) + sum_{j != i} [J_ij(a, w_j) - J_ij(w_i, w_j)]
+ * for every site i and every state a (gap included), summed in double over ascending j; dE[i*q + w_i] = 0.0 exactly. */
+int dca_plm_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out /* L*q */);
+
 /* ------------------------------------------------------------------ DI on caller-provided arrays
  * The module-level functions of the reference: compute_two_site_model_fields + compute_direct_info
  * (meanfield_dca/msa_numerics.py:378-533: layout 1 = couplings as the n x n matrix, n = L(q-1);
@@ -336,6 +358,12 @@ int dca_mf_di_scores(dca_ctx* ctx, int apc, double* scores_out);
 /* local fields of the global model, L*(q-1) doubles (MeanFieldDCA.compute_fields,
  * meanfield_dca.py:588-633); needs the couplings */
 int dca_mf_fields(dca_ctx* ctx, double* fields_out);
+/* dca_plm_energies / dca_plm_mutation_scan under the mean-field model: J_ij(a, b) = couplings[(i,a),(j,b)] (the -inv(C) of
+ * dca_mf_couplings) and h_i(a) = the fields of dca_mf_fields for a, b < q-1; both are 0 when a or b is the gap state q-1 (the
+ * gauge of the mean-field model).  Same formulas, order, determinism and argument checks; DCA_ERR_STATE before
+ * dca_mf_couplings. */
+int dca_mf_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out);
+int dca_mf_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out /* L*q */);
 /* coupling blocks of selected pairs, optionally gauge shifted (MeanFieldDCA.compute_params,
  * meanfield_dca.py:661-752; shift_couplings :636-658) */
 int dca_mf_pair_couplings(dca_ctx* ctx, const int* pairs, int npairs, int shift, double* out);
@@ -357,7 +385,7 @@ int dca_spd_inverse(dca_ctx* ctx, const double* A, int n, double* Ainv_out);
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
- * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores"). */
+ * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it
  * instead of two per stage (an event record costs the stream ~5 us: 14 per plmDCA iteration are 5 % of config C's step, 0.4 % of

@@ -113,6 +113,11 @@ def lib():
         "dca_mf_di_scores": (i, [vp, i, vp]),
         "dca_plm_pair_couplings": (i, [vp, vp, i, i, vp]),
         "dca_mf_fields": (i, [vp, vp]),
+        "dca_encode_sequences": (i, [C.c_char_p, vp, i, i, i, i, vp, C.POINTER(i)]),
+        "dca_plm_energies": (i, [vp, vp, i, vp]),
+        "dca_plm_mutation_scan": (i, [vp, vp, vp]),
+        "dca_mf_energies": (i, [vp, vp, i, vp]),
+        "dca_mf_mutation_scan": (i, [vp, vp, vp]),
         "dca_mf_pair_couplings": (i, [vp, vp, i, i, vp]),
         "dca_mf_single_site_freqs": (i, [vp, vp]),
         "dca_mf_pair_site_freqs": (i, [vp, vp]),
@@ -152,6 +157,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_plm_set_x", "dca_plm_get_x", "dca_plm_release", "dca_plm_gradient", "dca_plm_get_g", "dca_plm_set_reduce_hook", "dca_mf_set_reduce_hook", "dca_di_from_arrays", "dca_di_from_fields", "dca_plm_set_vector_sharding",
            "dca_plm_lbfgs_begin", "dca_plm_lbfgs_iterate", "dca_plm_lbfgs_end", "dca_plm_scores", "dca_plm_di_scores",
            "dca_mf_di_scores", "dca_plm_pair_couplings", "dca_mf_fields", "dca_mf_pair_couplings",
+           "dca_encode_sequences", "dca_plm_energies", "dca_plm_mutation_scan", "dca_mf_energies", "dca_mf_mutation_scan",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
            "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
@@ -259,6 +265,31 @@ def read_fasta(path, biomolecule):
         if rows:
             l.dca_host_free(rows)
     return out, raw.value
+
+
+class EncodeError(ValueError):
+    """A query record that dca_encode_sequences rejected: .record is its 0-based index, .code DCA_ERR_ARG (length) or
+    DCA_ERR_RESIDUE (a character the plm reader's table lacks)."""
+
+    def __init__(self, code, record, msg):
+        super().__init__(msg)
+        self.code, self.record = code, record
+
+
+def encode_sequences(seqs, biomolecule, L, table):
+    """Aligned strings -> uint8[n, L] codes (0-based, gap = q-1), in order, duplicates kept (dca_encode_sequences).
+    table 0: the plm reader's residue table, 1: the mf reader's (unknown characters are the gap)."""
+    enc = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in seqs]
+    offs = np.zeros(len(enc) + 1, dtype=np.int32)
+    if enc:
+        offs[1:] = np.cumsum([len(e) for e in enc])
+    out = np.zeros((len(enc), int(L)), dtype=np.uint8)
+    bad = C.c_int(-1)
+    rc = lib().dca_encode_sequences(b"".join(enc), _ptr(offs), len(enc), int(biomolecule), int(table), int(L), _ptr(out), C.byref(bad))
+    if rc in (DCA_ERR_ARG, DCA_ERR_RESIDUE) and bad.value >= 0:
+        raise EncodeError(rc, bad.value, lib().dca_last_error().decode("utf-8", "replace"))
+    check(rc)
+    return out
 
 
 class Context:
@@ -527,6 +558,33 @@ class Context:
         out = np.zeros((self.L, self.q - 1), dtype=np.float64)
         check(self._l.dca_mf_fields(self._h, _ptr(out)))
         return out
+
+    # ---- Potts energies (energy.hip): X uint8[n, L] codes < q -> float64[n]; wild type uint8[L] -> float64[L, q]
+    def _energies(self, fn, X):
+        X = np.ascontiguousarray(X, dtype=np.uint8).reshape(-1, self.L)
+        out = np.zeros(X.shape[0], dtype=np.float64)
+        check(fn(self._h, _ptr(X), int(X.shape[0]), _ptr(out)))
+        return out
+
+    def _mutation_scan(self, fn, wildtype):
+        w = np.ascontiguousarray(wildtype, dtype=np.uint8).reshape(-1)
+        if w.size != self.L:
+            raise ValueError("the wild type must have L = %d codes" % self.L)
+        out = np.zeros((self.L, self.q), dtype=np.float64)
+        check(fn(self._h, _ptr(w), _ptr(out)))
+        return out
+
+    def plm_energies(self, X):
+        return self._energies(self._l.dca_plm_energies, X)
+
+    def plm_mutation_scan(self, wildtype):
+        return self._mutation_scan(self._l.dca_plm_mutation_scan, wildtype)
+
+    def mf_energies(self, X):
+        return self._energies(self._l.dca_mf_energies, X)
+
+    def mf_mutation_scan(self, wildtype):
+        return self._mutation_scan(self._l.dca_mf_mutation_scan, wildtype)
 
     def mf_di_scores(self, apc=False):
         out = np.zeros(self.L * (self.L - 1) // 2, dtype=np.float64)

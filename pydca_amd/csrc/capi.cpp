@@ -188,6 +188,10 @@ int dca_read_msa(const char* path, int biomolecule, int L, uint8_t* out, int cap
 }
 
 int dca_count_msa_lines(const char* path) { return dca_count_msa_lines_impl(path); }
+int dca_encode_sequences(const char* seqs, const int* offsets, int nseq, int biomolecule, int table, int L, uint8_t* out, int* bad_record)
+{
+    return dca_encode_sequences_impl(seqs, offsets, nseq, biomolecule, table, L, out, bad_record);
+}
 int dca_read_msa_alloc(const char* path, int biomolecule, int L, uint8_t** rows, int* raw_count)
 {
     if (!rows) { dca_set_error("dca_read_msa_alloc: bad arguments"); return DCA_ERR_ARG; }
@@ -484,6 +488,20 @@ int dca_plm_lbfgs_begin(dca_ctx* ctx, int max_iterations, int verbose) { CHECK_C
 int dca_plm_lbfgs_iterate(dca_ctx* ctx, int iterations, dca_plm_stats* st) { CHECK_CTX(ctx); DCA_TRY(need_plm(ctx)); return ctx->plm->lbfgs_iterate(iterations, st); }
 int dca_plm_lbfgs_end(dca_ctx* ctx) { CHECK_CTX(ctx); if (ctx->plm) ctx->plm->lbfgs_end(); return DCA_OK; }
 int dca_plm_scores(dca_ctx* ctx, int apc, double* out) { CHECK_CTX(ctx); DCA_TRY(need_plm(ctx)); return ctx->plm->scores(apc, out); }
+int dca_plm_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    if (n < 0 || (n > 0 && (!X || !energies_out))) return DCA_ERR_ARG;
+    return ctx->plm->energies(X, n, energies_out);
+}
+int dca_plm_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    if (!wildtype || !dE_out) return DCA_ERR_ARG;
+    return ctx->plm->mutation_scan(wildtype, dE_out);
+}
 int dca_plm_di_scores(dca_ctx* ctx, const double* reg_fi, int apc, double* out)
 {
     CHECK_CTX(ctx);
@@ -611,6 +629,20 @@ int dca_mf_set_reduce_hook(dca_ctx* ctx, dca_reduce_hook hook, void* user)
     return DCA_OK;
 }
 int dca_mf_fields(dca_ctx* ctx, double* out) { CHECK_CTX(ctx); DCA_TRY(need_mf(ctx)); if (!out) return DCA_ERR_ARG; return dca_mf_engine_fields(ctx->mf, out); }
+int dca_mf_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_mf(ctx));
+    if (n < 0 || (n > 0 && (!X || !energies_out))) return DCA_ERR_ARG;
+    return dca_mf_engine_energies(ctx->mf, X, n, energies_out);
+}
+int dca_mf_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_mf(ctx));
+    if (!wildtype || !dE_out) return DCA_ERR_ARG;
+    return dca_mf_engine_mutation_scan(ctx->mf, wildtype, dE_out);
+}
 int dca_mf_pair_couplings(dca_ctx* ctx, const int* pairs, int npairs, int shift, double* out)
 {
     CHECK_CTX(ctx);

@@ -166,6 +166,8 @@ struct PlmEngineBase {
     virtual int scores(int apc, double* out) = 0;
     virtual int di_scores(const double* reg_fi, int apc, double* out) = 0;
     virtual int pair_couplings(const int* pairs, int npairs, int shift, double* out) = 0;
+    virtual int energies(const uint8_t* X, int n, double* out) = 0;            // energy.hip on the current x
+    virtual int mutation_scan(const uint8_t* wildtype, double* out) = 0;
     virtual int set_vector_sharding(int rank, int world, dca_comm_hook hook, void* user) = 0;
     dca_reduce_hook hook = nullptr;
     void* hook_user = nullptr;
@@ -188,6 +190,13 @@ int dca_di_scores(dca_ctx* ctx, const void* src, int src_kind, int dtype, const 
 int dca_pair_blocks(dca_ctx* ctx, const void* src, int src_kind, int dtype, int L, int q, int ld, const int* pairs, int npairs,
                     int shift, double* out /* host */);
 
+// ---- energy.hip : Potts energies of host query rows (n x L codes < q) and single-mutant scans of a wild type (L codes).
+// Same source conventions as dca_fn_scores; src_kind 1 also takes the mf fields (device, L*(q-1) doubles).  out: host.
+int dca_potts_energies(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
+                       const uint8_t* X, int n, double* out);
+int dca_potts_mutation_scan(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
+                            const uint8_t* wildtype, double* out /* L*q */);
+
 int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, const double* reg_fi, int L, int q,
                             double* fields_out, double* di_out, const double* fields_in = nullptr);
 
@@ -207,6 +216,8 @@ void dca_mf_engine_set_native(MfEngine*, bool on);
 int dca_mf_engine_set_row_window(MfEngine*, int first, int count);   // count < 0: all rows
 void dca_mf_engine_invalidate(MfEngine*);      // weights changed: counts, frequencies, C and J are recomputed on demand
 int dca_mf_engine_pair_couplings(MfEngine*, const int* pairs, int npairs, int shift, double* out);
+int dca_mf_engine_energies(MfEngine*, const uint8_t* X, int n, double* out);
+int dca_mf_engine_mutation_scan(MfEngine*, const uint8_t* wildtype, double* out);
 
 // ---- cholinv.hip : scale * inverse of an SPD matrix on the device (f64 MFMA)
 // dA: n x n row-major (ld = n), n multiple of 64; destroyed (holds the triangular factor's inverse afterwards).
@@ -218,3 +229,5 @@ int dca_spd_inverse_device(dca_ctx* ctx, double* dA, int n, double* dWork, int* 
 int dca_read_msa_impl(const char* path, int biomolecule, int L, uint8_t* out, int capacity, int* raw_count);
 int dca_read_msa_owned(const char* path, int biomolecule, int L, uint8_t** rows /* malloc'd, caller frees */, int* raw_count);   // one pass, no capacity
 int dca_count_msa_lines_impl(const char* path);
+int dca_encode_sequences_impl(const char* seqs, const int* offsets, int nseq, int biomolecule, int table, int L, uint8_t* out,
+                              int* bad_record);

@@ -1,0 +1,280 @@
+// Statistical energies of query sequences and single-mutant scans under a fitted Potts model:
+//   E(s) = sum_i h_i(s_i) + sum_{i<j} J_ij(s_i, s_j),
+//   dE(i,a) = h_i(a) - h_i(w_i) + sum_{j != i} [J_ij(a, w_j) - J_ij(w_i, w_j)].
+// Parameter sources (as in scoring.hip): kind 0 = the packed plm vector x (fields L*q first, then the upper-triangle q x q
+// blocks in pair order), element type float or double; kind 1 = the dense mf couplings -inv(C) (double, leading dimension ld,
+// (q-1) x (q-1) blocks) with the mf fields (L*(q-1) doubles); both are zero on the gap state q-1.
+//
+// Every term is widened to double and summed in double in an order fixed by (L, q, dtype) alone:
+//   pair kernel: the site pairs are cut into TS x TS tiles (site blocks bi <= bj, row-major), the tiles into G groups of
+//     consecutive tiles; a workgroup holds one tile at a time in LDS and streams a block of query sequences against it,
+//     one thread per sequence; per sequence its group's tiles are added in ascending order, each tile's pairs in (i, j)
+//     order, and the group's sum goes to slab g.  No float atomics; the model is read once per sequence block.
+//   finish kernel: per sequence the fields in ascending site order, then the slabs in ascending g.
+// Neither order depends on the number of query sequences or on a sequence's place among them.
+//
+// The query codes are kept site-major (code of site s of sequence n at s * NqS + n, NqS a multiple of 128): the lanes of a
+// wave, one sequence each, then read one contiguous 64-byte run per site instead of 64 cache lines.
+#include "dca_internal.h"
+
+namespace {
+
+constexpr int kEThreads = 512;                     // pair-kernel workgroup: 8 waves
+constexpr int kESeqPerThread = 8;                  // sequences per thread: one tile load serves 4096 sequences
+constexpr int kESeqBlock = kEThreads * kESeqPerThread;
+constexpr size_t kETileBudget = 72 * 1024;         // LDS per tile: two workgroups per CU (160 KiB), one loads while one gathers
+constexpr int kETargetGroups = 128;                // tile groups (slabs) for large L
+constexpr int kEChunk = 16 * kESeqBlock;           // query sequences per pass (bounds the slabs: G x 65536 doubles)
+
+__host__ __device__ __forceinline__ size_t pair_index(int L, int i, int j)
+{
+    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
+}
+
+// J_ij(a, b) for i < j, widened to double
+template <typename S>
+__device__ __forceinline__ double coupling(const S* src, int kind, int L, int q, int ld, int i, int j, int a, int b)
+{
+    if (kind == 0) return (double)src[(size_t)L * q + pair_index(L, i, j) * (size_t)q * q + (size_t)a * q + b];
+    const int qm = q - 1;
+    if (a == qm || b == qm) return 0.0;
+    return (double)src[(size_t)(i * qm + a) * ld + (size_t)j * qm + b];
+}
+
+template <typename S>
+__device__ __forceinline__ double field(const S* src, const double* mfh, int kind, int q, int i, int a)
+{
+    if (kind == 0) return (double)src[(size_t)i * q + a];
+    return a == q - 1 ? 0.0 : mfh[(size_t)i * (q - 1) + a];
+}
+
+// site-major copy of n query rows (n x L bytes): QT[s * NqS + k], zero past n
+__global__ void query_sites_kernel(const uint8_t* __restrict__ rows, int n, int L, int NqS, uint8_t* __restrict__ QT)
+{
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t >= (size_t)L * NqS) return;
+    const int s = (int)(t / NqS), k = (int)(t % NqS);
+    QT[t] = k < n ? rows[(size_t)k * L + s] : 0;
+}
+
+// grid (G, sequence blocks).  LDS: one tile, TS*TS pairs of q*q values of type S (pair (ii, jj) at (ii*TS + jj) * q*q).
+template <typename S, int TS>
+__global__ __launch_bounds__(kEThreads)
+void energy_pairs_kernel(const S* __restrict__ src, int kind, int L, int q, int ld, const uint8_t* __restrict__ QT, int nq,
+                         int NqS, int nb, int ntiles, int tpg, double* __restrict__ slabs)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char energy_smem[];
+    S* tile = reinterpret_cast<S*>(energy_smem);
+    const int qq = q * q;
+    const int g = blockIdx.x;
+    const int seq0 = blockIdx.y * kESeqBlock + threadIdx.x;
+    int t = g * tpg;
+    const int tEnd = min(ntiles, t + tpg);
+    int bi = 0, rowStart = 0;                      // tile t = (bi, bj): row bi holds tiles rowStart .. rowStart + nb - bi - 1
+    while (t >= rowStart + nb - bi) { rowStart += nb - bi; ++bi; }
+    int bj = bi + (t - rowStart);
+    double acc[kESeqPerThread];
+#pragma unroll
+    for (int r = 0; r < kESeqPerThread; ++r) acc[r] = 0.0;
+
+    for (; t < tEnd; ++t) {
+        const int i0 = bi * TS, j0 = bj * TS;
+        const int ni = min(TS, L - i0), nj = min(TS, L - j0);
+        const bool diag = bi == bj;
+        __syncthreads();                           // the previous tile is no longer read
+        for (int e = threadIdx.x; e < TS * TS * qq; e += kEThreads) {
+            const int k = e / qq, ab = e - k * qq;
+            const int ii = k / TS, jj = k - ii * TS;
+            S v = (S)0;
+            if (ii < ni && jj < nj && (!diag || jj > ii)) v = (S)coupling(src, kind, L, q, ld, i0 + ii, j0 + jj, ab / q, ab % q);
+            tile[e] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < kESeqPerThread; ++r) {
+            const int n = seq0 + r * kEThreads;
+            if (n < nq) {
+                int cjo[TS];
+#pragma unroll
+                for (int jj = 0; jj < TS; ++jj) cjo[jj] = jj * qq + (jj < nj ? (int)QT[(size_t)(j0 + jj) * NqS + n] : 0);
+                double s = acc[r];
+#pragma unroll 1
+                for (int ii = 0; ii < ni; ++ii) {
+                    const S* row = tile + ii * TS * qq + (int)QT[(size_t)(i0 + ii) * NqS + n] * q;
+#pragma unroll
+                    for (int jj = 0; jj < TS; ++jj)
+                        if (jj < nj && (!diag || jj > ii)) s += (double)row[cjo[jj]];
+                }
+                acc[r] = s;
+            }
+        }
+        if (++bj == nb) { ++bi; bj = bi; }
+    }
+#pragma unroll
+    for (int r = 0; r < kESeqPerThread; ++r) {
+        const int n = seq0 + r * kEThreads;
+        if (n < nq) slabs[(size_t)g * NqS + n] = acc[r];
+    }
+}
+
+// E(n) = sum_i h_i(s_i) (ascending i) + sum_g slab[g][n] (ascending g)
+template <typename S>
+__global__ __launch_bounds__(256)
+void energy_finish_kernel(const S* __restrict__ src, const double* __restrict__ mfh, int kind, int L, int q,
+                          const uint8_t* __restrict__ QT, int nq, int NqS, const double* __restrict__ slabs, int G,
+                          double* __restrict__ out)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= nq) return;
+    double e = 0.0;
+    for (int i = 0; i < L; ++i) e += field(src, mfh, kind, q, i, QT[(size_t)i * NqS + n]);
+    for (int g = 0; g < G; ++g) e += slabs[(size_t)g * NqS + n];
+    out[n] = e;
+}
+
+// One 64-lane workgroup per site i; lane a < q: S(a) = sum_{j != i, ascending} J_ij(a, w_j) (block (min, max) of the
+// pair, as the energy reads it), dE(i, a) = (h_i(a) - h_i(w_i)) + (S(a) - S(w_i)); dE(i, w_i) = 0.
+template <typename S>
+__global__ __launch_bounds__(64)
+void mutation_scan_kernel(const S* __restrict__ src, const double* __restrict__ mfh, int kind, int L, int q, int ld,
+                          const uint8_t* __restrict__ wt, double* __restrict__ dE)
+{
+    __shared__ double sumW, hW;
+    const int i = blockIdx.x, a = threadIdx.x;
+    const int wi = wt[i];
+    double s = 0.0, h = 0.0;
+    if (a < q) {
+        for (int j = 0; j < L; ++j) {
+            if (j == i) continue;
+            s += j > i ? coupling(src, kind, L, q, ld, i, j, a, wt[j]) : coupling(src, kind, L, q, ld, j, i, wt[j], a);
+        }
+        h = field(src, mfh, kind, q, i, a);
+        if (a == wi) { sumW = s; hW = h; }
+    }
+    __syncthreads();
+    if (a < q) dE[(size_t)i * q + a] = a == wi ? 0.0 : (h - hW) + (s - sumW);
+}
+
+struct EnergyGeom { int TS, nb, ntiles, tpg, G; };
+
+EnergyGeom energy_geometry(int L, int q, size_t elem)
+{
+    static const int kSizes[] = {24, 16, 12, 8, 6, 4, 3};
+    EnergyGeom g{};
+    for (int ts : kSizes)
+        if ((size_t)ts * ts * q * q * elem <= kETileBudget) { g.TS = ts; break; }
+    g.nb = ceil_div(L, g.TS);
+    g.ntiles = g.nb * (g.nb + 1) / 2;
+    g.tpg = ceil_div(g.ntiles, kETargetGroups);
+    g.G = ceil_div(g.ntiles, g.tpg);
+    return g;
+}
+
+template <typename S, int TS>
+hipError_t launch_pairs(dca_ctx* ctx, const EnergyGeom& eg, const S* src, int kind, int L, int q, int ld, const uint8_t* QT, int nq,
+                        int NqS, double* slabs)
+{
+    const size_t lds = (size_t)TS * TS * q * q * sizeof(S);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(energy_pairs_kernel<S, TS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((energy_pairs_kernel<S, TS>), dim3(eg.G, ceil_div(nq, kESeqBlock)), dim3(kEThreads), lds, ctx->stream,
+                       src, kind, L, q, ld, QT, nq, NqS, eg.nb, eg.ntiles, eg.tpg, slabs);
+    return hipGetLastError();
+}
+
+template <typename S>
+hipError_t dispatch_pairs(dca_ctx* ctx, const EnergyGeom& eg, const S* src, int kind, int L, int q, int ld, const uint8_t* QT, int nq,
+                          int NqS, double* slabs)
+{
+    switch (eg.TS) {
+    case 24: return launch_pairs<S, 24>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
+    case 16: return launch_pairs<S, 16>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
+    case 12: return launch_pairs<S, 12>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
+    case 8: return launch_pairs<S, 8>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
+    case 6: return launch_pairs<S, 6>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
+    case 4: return launch_pairs<S, 4>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
+    default: return launch_pairs<S, 3>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
+    }
+}
+
+int check_codes(const uint8_t* X, size_t count, int q)
+{
+    for (size_t k = 0; k < count; ++k)
+        if (X[k] >= q) { dca_set_error("code %d >= q at element %zu", (int)X[k], k); return DCA_ERR_ARG; }
+    return DCA_OK;
+}
+
+template <typename S>
+int energies_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q, int ld, const uint8_t* X, int n, double* out)
+{
+    const EnergyGeom eg = energy_geometry(L, q, sizeof(S));
+    const int cap = std::min(n, kEChunk);
+    const int NqS = (int)round_up((size_t)cap, 128);
+    uint8_t *dRows = nullptr, *dQT = nullptr;
+    double *dSlabs = nullptr, *dOut = nullptr;
+    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)cap * L, false);
+    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dQT), (size_t)L * NqS, false);
+    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dSlabs), (size_t)eg.G * NqS * sizeof(double), false);
+    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dOut), (size_t)NqS * sizeof(double), false);
+    for (int first = 0; first < n && e == hipSuccess; first += cap) {
+        const int nq = std::min(cap, n - first);
+        e = hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream);
+        if (e != hipSuccess) break;
+        const size_t total = (size_t)L * NqS;
+        hipLaunchKernelGGL(query_sites_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dRows, nq, L, NqS, dQT);
+        {
+            ScopedKernelClock kc(ctx, "energies");
+            e = dispatch_pairs<S>(ctx, eg, src, kind, L, q, ld, dQT, nq, NqS, dSlabs);
+            if (e == hipSuccess)
+                hipLaunchKernelGGL(energy_finish_kernel<S>, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, src, mfh, kind, L, q, dQT, nq,
+                                   NqS, dSlabs, eg.G, dOut);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(out + first, dOut, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    }
+    dca_dev_free(dRows); dca_dev_free(dQT); dca_dev_free(dSlabs); dca_dev_free(dOut);
+    if (e != hipSuccess) { dca_set_error("energies: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    return DCA_OK;
+}
+
+template <typename S>
+int mutation_scan_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q, int ld, const uint8_t* wt, double* out)
+{
+    uint8_t* dWt = nullptr;
+    double* dOut = nullptr;
+    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dWt), (size_t)L);
+    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dOut), (size_t)L * q * sizeof(double), false);
+    if (e == hipSuccess) e = hipMemcpyAsync(dWt, wt, (size_t)L, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) {
+        ScopedKernelClock kc(ctx, "mutation_scan");
+        hipLaunchKernelGGL(mutation_scan_kernel<S>, dim3(L), dim3(64), 0, ctx->stream, src, mfh, kind, L, q, ld, dWt, dOut);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t)L * q * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dca_dev_free(dWt); dca_dev_free(dOut);
+    if (e != hipSuccess) { dca_set_error("mutation scan: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    return DCA_OK;
+}
+
+}  // namespace
+
+int dca_potts_energies(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
+                       const uint8_t* X, int n, double* out)
+{
+    if (n < 0 || (n > 0 && (!X || !out))) { dca_set_error("energies: bad arguments"); return DCA_ERR_ARG; }
+    if (n == 0) return DCA_OK;
+    DCA_TRY(check_codes(X, (size_t)n * L, q));
+    if (dtype == DCA_F32) return energies_t(ctx, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, X, n, out);
+    return energies_t(ctx, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, X, n, out);
+}
+
+int dca_potts_mutation_scan(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
+                            const uint8_t* wt, double* out)
+{
+    if (!wt || !out) { dca_set_error("mutation scan: bad arguments"); return DCA_ERR_ARG; }
+    DCA_TRY(check_codes(wt, (size_t)L, q));
+    if (dtype == DCA_F32) return mutation_scan_t(ctx, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, wt, out);
+    return mutation_scan_t(ctx, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, wt, out);
+}

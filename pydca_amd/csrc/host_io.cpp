@@ -300,6 +300,42 @@ int dca_read_msa_impl(const char* path, int biomolecule, int L, uint8_t* out, in
     return read_msa_core(path, biomolecule, L, out, capacity, nullptr, raw_count);
 }
 
+// Query sequences for the energy entries: record k = seqs[offsets[k] .. offsets[k+1]), encoded in order, nothing dropped.
+// table 0: the plm reader's table (a character it rejects is DCA_ERR_RESIDUE); 1: the mf reader's (unknown -> gap).
+// A record whose length is not L is DCA_ERR_ARG.  *bad_record: 0-based index of the first offending record.
+int dca_encode_sequences_impl(const char* seqs, const int* offsets, int nseq, int biomolecule, int table, int L, uint8_t* out,
+                              int* bad_record)
+{
+    if (bad_record) *bad_record = -1;
+    if (nseq < 0 || L <= 0 || (nseq > 0 && (!seqs || !offsets || !out)) || (table != 0 && table != 1) ||
+        (biomolecule != DCA_BIOMOLECULE_PROTEIN && biomolecule != DCA_BIOMOLECULE_RNA)) {
+        dca_set_error("dca_encode_sequences: bad arguments");
+        return DCA_ERR_ARG;
+    }
+    const bool protein = biomolecule == DCA_BIOMOLECULE_PROTEIN;
+    const int8_t* codes = table == 0 ? (protein ? kCodes.protein : kCodes.rna) : (protein ? kCodes.mf_protein : kCodes.mf_rna);
+    for (int k = 0; k < nseq; ++k) {
+        const long long len = (long long)offsets[k + 1] - offsets[k];
+        if (len != L) {
+            if (bad_record) *bad_record = k;
+            dca_set_error("record %d has length %lld, expected %d", k + 1, len, L);
+            return DCA_ERR_ARG;
+        }
+        const unsigned char* src = reinterpret_cast<const unsigned char*>(seqs + offsets[k]);
+        uint8_t* dst = out + (size_t)k * L;
+        for (int s = 0; s < L; ++s) {
+            const int8_t c = codes[src[s]];
+            if (c < 0) {
+                if (bad_record) *bad_record = k;
+                dca_set_error("character '%c' of record %d is not in the residue table", src[s], k + 1);
+                return DCA_ERR_RESIDUE;
+            }
+            dst[s] = (uint8_t)c;
+        }
+    }
+    return DCA_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // FASTA reader of the mfDCA path: the semantics of pydca/fasta_reader/fasta_reader.py:81-163 as read through
 // Biopython -- records start at '>' lines, a record's sequence is the concatenation of its stripped lines, records

@@ -578,21 +578,51 @@ void mf_fields_kernel(const double* __restrict__ J, const double* __restrict__ r
 }
 }  // namespace
 
-int dca_mf_engine_fields(MfEngine* m, double* out)
+// fields of the global model into a device buffer of L*(q-1) doubles (allocated here; the caller frees it)
+static int mf_fields_device(MfEngine* m, double** dOut)
 {
+    *dOut = nullptr;
     if (!m->have_J) { dca_set_error("dca_mf_couplings first"); return DCA_ERR_STATE; }
     dca_ctx* ctx = m->ctx;
     if (!m->dRegFi) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dRegFi), (size_t)m->Lq * sizeof(double)));
     hipLaunchKernelGGL(mf_regfi_kernel, dim3(ceil_div(m->Lq, 256)), dim3(256), 0, ctx->stream, m->dFi, m->dRegFi, m->Lq, m->q, m->theta);
     const int n = m->L * (m->q - 1);
+    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(dOut), (size_t)n * sizeof(double)));
+    hipLaunchKernelGGL(mf_fields_kernel, dim3(n), dim3(256), 0, ctx->stream, m->dJ, m->dRegFi, m->L, m->q, m->np, *dOut);
+    return DCA_OK;
+}
+
+int dca_mf_engine_fields(MfEngine* m, double* out)
+{
     double* dOut = nullptr;
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dOut), (size_t)n * sizeof(double)));
-    hipLaunchKernelGGL(mf_fields_kernel, dim3(n), dim3(256), 0, ctx->stream, m->dJ, m->dRegFi, m->L, m->q, m->np, dOut);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
+    DCA_TRY(mf_fields_device(m, &dOut));
+    const int n = m->L * (m->q - 1);
+    hipError_t e = hipStreamSynchronize(m->ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(out, dOut, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
     dca_dev_free(dOut);
     if (e != hipSuccess) { dca_set_error("fields: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
     return DCA_OK;
+}
+
+// Potts energies / single-mutant scan under the mean-field model: J = dJ, h = the fields above, both zero on the gap state
+int dca_mf_engine_energies(MfEngine* m, const uint8_t* X, int n, double* out)
+{
+    double* dH = nullptr;
+    DCA_TRY(mf_fields_device(m, &dH));
+    const int rc = dca_potts_energies(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, X, n, out);
+    hipStreamSynchronize(m->ctx->stream);
+    dca_dev_free(dH);
+    return rc;
+}
+
+int dca_mf_engine_mutation_scan(MfEngine* m, const uint8_t* wildtype, double* out)
+{
+    double* dH = nullptr;
+    DCA_TRY(mf_fields_device(m, &dH));
+    const int rc = dca_potts_mutation_scan(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, wildtype, out);
+    hipStreamSynchronize(m->ctx->stream);
+    dca_dev_free(dH);
+    return rc;
 }
 
 int dca_mf_engine_pair_couplings(MfEngine* m, const int* pairs, int npairs, int shift, double* out)

@@ -2527,6 +2527,20 @@ struct PlmEngine : PlmEngineBase {
         return dca_pair_blocks(ctx, dx, 0, (int)sizeof(T) * 8, L, q, 0, pairs, npairs, shift, out);
     }
 
+    // Potts energies / single-mutant scan of the current x (energy.hip); column strips gather x first, as scores() does
+    int energies(const uint8_t* X, int n, double* out) override
+    {
+        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
+        if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
+        return dca_potts_energies(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, X, n, out);
+    }
+    int mutation_scan(const uint8_t* wildtype, double* out) override
+    {
+        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
+        if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
+        return dca_potts_mutation_scan(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, wildtype, out);
+    }
+
     // DI of the current x (plmdca.py:683-790); reg_fi: host, L*q regularised single-site frequencies
     int di_scores(const double* reg_fi, int apc, double* out) override
     {

@@ -83,6 +83,30 @@ def write_sorted_dca_scores(file_name, sorted_DI, metadata=None, score_type=None
     _stream(file_name, header, rows, 'ranked scores')
 
 
+def write_sequence_energies(file_name, energies, metadata=None, query_file=None):
+    """One row per query record: its number (1-based, input order) and its statistical energy (no reference counterpart)."""
+    header = [_RULE] + list(metadata or [])
+    if query_file:
+        header.append('#\tQuery sequences: {}'.format(query_file))
+    header += ['# The First column is the record number (1-based) of the query sequence and the',
+               '# Second its statistical energy E(s) = sum_i h_i(s_i) + sum_{i<j} J_ij(s_i, s_j) (higher is more probable)', _RULE]
+    rows = ('{0:<7} {1}'.format(k + 1, float(e)) for k, e in enumerate(energies))
+    _stream(file_name, header, rows, 'sequence energies')
+
+
+def write_mutation_effects(file_name, dE, wildtype_letters, state_letters, metadata=None, wildtype_file=None):
+    """One row per (site, state), site-major: site (1-based), wild-type letter, mutant letter and
+    dE = E(mutant) - E(wild type) (no reference counterpart)."""
+    header = [_RULE] + list(metadata or [])
+    if wildtype_file:
+        header.append('#\tWild-type sequence: {}'.format(wildtype_file))
+    header += ['# The First column is the site (1-based), the Second the wild-type residue, the Third the',
+               '# mutant residue and the Fourth dE = E(mutant) - E(wild type) (positive: the mutant is more probable)', _RULE]
+    L, q = dE.shape
+    rows = ('{0:<7} {1} {2} {3}'.format(i + 1, wildtype_letters[i], state_letters[a], float(dE[i, a])) for i in range(L) for a in range(q))
+    _stream(file_name, header, rows, 'single-mutant effects')
+
+
 def _csv(prefix_values, values):
     # '{}'.format(v), not str(v): numpy scalars of the two print differently (a float32 is widened by format)
     return ','.join('{}'.format(v) for v in list(prefix_values) + list(values))

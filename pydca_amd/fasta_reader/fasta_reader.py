@@ -29,8 +29,9 @@ def res_to_char(biomolecule):
     return {val: key for key, val in RES_TO_INT.items() if key not in ('.', '~')}
 
 
-def get_alignment_from_fasta_file(file_name):
-    """-> list of upper-cased sequence strings (fasta_reader.py:81-119)."""
+def get_alignment_from_fasta_file(file_name, same_length=True):
+    """-> list of upper-cased sequence strings (fasta_reader.py:81-119).  same_length=False leaves the length check to the
+    caller (the query sequences of the energy methods, whose encoder names the record of a wrong length)."""
     alignment, name, cur = [], None, []
     try:
         with open(file_name) as fh:
@@ -55,7 +56,7 @@ def get_alignment_from_fasta_file(file_name):
         logger.error('\n\tNo sequences found in {}'.format(file_name))
         raise ValueError
     lengths = {len(s) for s in alignment}
-    if len(lengths) != 1:
+    if same_length and len(lengths) != 1:
         raise ValueError('Sequences in {} do not all have the same length'.format(file_name))
     return alignment
 

@@ -6,7 +6,7 @@ import time
 
 import numpy as np
 
-from .. import _lib, _ranking, multi_gpu
+from .. import _lib, _potts, _ranking, multi_gpu
 from ..fasta_reader import fasta_reader
 from . import msa_numerics
 
@@ -251,6 +251,41 @@ class MeanFieldDCA:
             total = np.einsum('iajb,jb->ia', J4, p) - np.einsum('iaib,ib->ia', J4, p)
             f = np.log(p / reg_fi[:, qm1:q]) - total
         return {i: f[i] for i in range(self.__sequences_len)}
+
+    # ---- the fitted model as a sequence model (no reference counterpart)
+    def _with_couplings(self, call):
+        """call() on the context; the couplings of the current pseudocount are computed first if none are there yet."""
+        try:
+            return call()
+        except _lib.DcaBackendError as exc:
+            if exc.code != _lib.DCA_ERR_STATE:
+                raise
+        self.__ctx.mf_corr_mat(self.__pseudocount, want=False)
+        try:
+            self.__ctx.mf_couplings(want=False)
+        except _lib.DcaBackendError as exc:
+            if exc.code == _lib.DCA_ERR_NOT_SPD:
+                raise np.linalg.LinAlgError('Singular matrix')
+            raise
+        return call()
+
+    def compute_sequence_energies(self, sequences=None):
+        """Statistical energies E(s) = sum_i h_i(s_i) + sum_{i<j} J_ij(s_i, s_j) with J the couplings and h the fields of
+        compute_fields (both zero on the gap state) -> float64[n], higher is more probable.  sequences: None (every record
+        of the training alignment, in file order, duplicates kept), a FASTA path or a list of aligned strings."""
+        src = self.__msa if sequences is None else sequences
+        bio = _lib.DCA_BIOMOLECULE_PROTEIN if self.__num_site_states == 21 else _lib.DCA_BIOMOLECULE_RNA
+        X = _potts.query_codes(src, bio, self.__sequences_len, 1, MeanFieldDCAException)
+        logger.info('\n\tStatistical energies of {} sequences'.format(X.shape[0]))
+        return self._with_couplings(lambda: self.__ctx.mf_energies(X))
+
+    def compute_single_mutant_effects(self, wildtype):
+        """dE(i, a) = E(wildtype with site i set to state a) - E(wildtype) for every site and state (gap last)
+        -> float64[L, q]; dE(i, w_i) = 0.  wildtype: an aligned string of length L or a FASTA file with one record."""
+        bio = _lib.DCA_BIOMOLECULE_PROTEIN if self.__num_site_states == 21 else _lib.DCA_BIOMOLECULE_RNA
+        w = _potts.wildtype_codes(wildtype, bio, self.__sequences_len, 1, MeanFieldDCAException)
+        logger.info('\n\tSingle-mutant effects of the wild type')
+        return self._with_couplings(lambda: self.__ctx.mf_mutation_scan(w))
 
     def shift_couplings(self, couplings_ij):
         """meanfield_dca.py:636-658 (zero-sum gauge of one block)."""

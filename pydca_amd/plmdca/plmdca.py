@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from .. import _lib, _ranking, multi_gpu
+from .. import _lib, _potts, _ranking, multi_gpu
 
 logger = logging.getLogger(__name__)
 
@@ -290,6 +290,27 @@ class PlmDCA:
         blocks = ctx.plm_pair_couplings(pairs, shift=True).astype(np.float32)
         couplings_ranked = [(pair, blocks[k].reshape(-1)) for k, pair in enumerate(names)]
         return tuple(fields_mapped), tuple(couplings_ranked)
+
+    # ---- the fitted model as a sequence model (no reference counterpart)
+    def _fitted_context(self):
+        """The model this instance holds from an earlier compute_* call; fitted once here if there is none."""
+        return self.__ctx if self.__ctx is not None else self._run_backend()
+
+    def compute_sequence_energies(self, sequences=None):
+        """Statistical energies E(s) = sum_i h_i(s_i) + sum_{i<j} J_ij(s_i, s_j) of the fitted parameters (gap state
+        included) -> float64[n], higher is more probable.  sequences: None (every record of the training file, in file
+        order, duplicates kept), a FASTA path or a list of aligned strings."""
+        src = self.__msa_file if sequences is None else sequences
+        X = _potts.query_codes(src, self.__biomolecule_int, self.__seqs_len, 0, PlmDCAException)
+        logger.info('\n\tStatistical energies of {} sequences'.format(X.shape[0]))
+        return self._fitted_context().plm_energies(X)
+
+    def compute_single_mutant_effects(self, wildtype):
+        """dE(i, a) = E(wildtype with site i set to state a) - E(wildtype) for every site and state (gap last)
+        -> float64[L, q]; dE(i, w_i) = 0.  wildtype: an aligned string of length L or a FASTA file with one record."""
+        w = _potts.wildtype_codes(wildtype, self.__biomolecule_int, self.__seqs_len, 0, PlmDCAException)
+        logger.info('\n\tSingle-mutant effects of the wild type')
+        return self._fitted_context().plm_mutation_scan(w)
 
     def compute_seqs_weight(self):
         """plmdca.py:565-591: weights of the PYTHON reader's alignment (float64 comparison,

@@ -5,6 +5,7 @@ import os
 import sys
 from argparse import ArgumentParser
 
+from . import _lib, _potts
 from .dca_utilities import dca_utilities
 from .plmdca import plmdca
 from .sequence_backmapper.sequence_backmapper import SequenceBackmapper
@@ -20,12 +21,19 @@ def configure_logging():
 def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_file=None, seqid=None, lambda_h=None,
                               lambda_J=None, max_iterations=None, apc=False, verbose=False, output_dir=None,
                               num_threads=None, ranked_by=None, linear_dist=None, num_site_pairs=None, device=0,
-                              exact_gradient=False, precision=32, devices=None):
+                              exact_gradient=False, precision=32, devices=None, query_file=None, wildtype_file=None):
     if verbose:
         configure_logging()
     plmdca_instance = plmdca.PlmDCA(msa_file, biomolecule, seqid=seqid, lambda_h=lambda_h, lambda_J=lambda_J,
                                     max_iterations=max_iterations, num_threads=num_threads, verbose=verbose,
                                     device=device, exact_gradient=exact_gradient, precision=precision or 32, devices=devices)
+    if the_command in _potts.POTTS_SUBCOMMANDS:
+        if not output_dir:
+            output_dir = 'PLMDCA_output_' + os.path.splitext(os.path.basename(msa_file))[0]
+        return _potts.run_subcommand(plmdca_instance, the_command, 'PLMDCA', msa_file, output_dir,
+                                     dca_utilities.plmdca_param_metadata(plmdca_instance),
+                                     _lib.DCA_BIOMOLECULE_PROTEIN if plmdca_instance.biomolecule == 'PROTEIN' else _lib.DCA_BIOMOLECULE_RNA, 0,
+                                     plmdca.PlmDCAException, query_file=query_file, wildtype_file=wildtype_file)
     if the_command in DCA_COMPUTATION_SUBCOMMANDS:
         param_metadata = dca_utilities.plmdca_param_metadata(plmdca_instance)
         if not output_dir:
@@ -81,7 +89,7 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
 def run_plm_dca(argv=None):
     parser = ArgumentParser(prog='plmdca')
     subparsers = parser.add_subparsers(dest='subcommand_name')
-    for name in DCA_COMPUTATION_SUBCOMMANDS:
+    for name in DCA_COMPUTATION_SUBCOMMANDS + _potts.POTTS_SUBCOMMANDS:
         p = subparsers.add_parser(name)
         p.add_argument('biomolecule', help='protein or rna (case insensitive)')
         p.add_argument('msa_file', help='FASTA formatted multiple sequence alignment, one sequence per line')
@@ -92,8 +100,12 @@ def run_plm_dca(argv=None):
         p.add_argument('--num_threads', type=int, help='accepted for compatibility; the work runs on the GPU')
         p.add_argument('--refseq_file')
         p.add_argument('--verbose', action='store_true')
-        if name != 'compute_params':
+        if name in ('compute_fn', 'compute_di'):
             p.add_argument('--apc', action='store_true')
+        if name == 'compute_energies':
+            p.add_argument('--query_file', help='FASTA file of aligned query sequences (default: the records of msa_file) (addition)')
+        if name == 'compute_mutation_effects':
+            p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence (addition)')
         p.add_argument('--output_dir')
         p.add_argument('--device', type=int, default=0, help='GPU index (addition)')
         p.add_argument('--devices', help='comma-separated GPU indices, e.g. 0,1,2,3,4,5,6,7: one rank per GPU, sequences (or sites) '
@@ -115,7 +127,7 @@ def run_plm_dca(argv=None):
         apc=args.get('apc'), output_dir=args.get('output_dir'), verbose=args.get('verbose'),
         ranked_by=args.get('ranked_by'), linear_dist=args.get('linear_dist'), num_site_pairs=args.get('num_site_pairs'),
         device=args.get('device'), exact_gradient=args.get('exact_gradient'), precision=args.get('precision'),
-        devices=args.get('devices'))
+        devices=args.get('devices'), query_file=args.get('query_file'), wildtype_file=args.get('wildtype_file'))
 
 
 if __name__ == '__main__':
