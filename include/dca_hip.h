@@ -319,6 +319,21 @@ int dca_plm_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out
  *   = h_i(a) - h_i(w_i) + sum_{j != i} [J_ij(a, w_j) - J_ij(w_i, w_j)]
  * for every site i and every state a (gap included), summed in double over ascending j; dE[i*q + w_i] = 0.0 exactly. */
 int dca_plm_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out /* L*q */);
+/* Systematic-scan Gibbs sampling of n independent chains from P(s) ~ exp(beta * E(s)) under the current x (E as in
+ * dca_plm_energies).  One sweep visits sites i = 0 .. L-1 in order; at site i a chain forms u_i(a) = h_i(a) + sum_{j != i} J(a, s_j)
+ * for every state a < q (gap included; every term in double, in an order fixed by (L, q, precision)), sets
+ * p_a = exp(beta * (u_i(a) - max_b u_i(b))), T = sum_a p_a (ascending a), r = U * T, and takes the smallest a whose ascending
+ * cumulative sum exceeds r (the largest a with p_a > 0 if rounding leaves none).  U is the uniform of Philox4x32-10 with
+ * key (seed & 0xffffffff, seed >> 32) and counter (chain, sweep, site, 0), chain = first_chain + k, sweep = first_sweep + t
+ * (each word mod 2^32): U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  initial: n x L codes < q (host), or NULL: chain k starts
+ * from s_i = floor(U * q) with counter (chain, 0, i, 1).  out: n x L codes (host) after `sweeps` sweeps (sweeps = 0 returns the
+ * start).  Chain k's result depends only on the model, seed, first_chain + k, first_sweep, sweeps, its start and beta: the same
+ * bits in any batch or split of one, and a + b sweeps equal a sweeps continued with first_sweep = a from their output.
+ * One launch per sweep on the context's stream.  The alignment, weights, x, g and the optimiser are not touched.
+ * DCA_ERR_ARG: n < 0, sweeps < 0, beta < 0, NaN or infinite, an initial code >= q, out NULL with n > 0; n == 0 is DCA_OK;
+ * DCA_ERR_STATE before dca_plm_configure.  Column strips: collective, like dca_plm_energies.  No reference counterpart. */
+int dca_plm_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                   const uint8_t* initial, uint8_t* out);
 
 /* ------------------------------------------------------------------ DI on caller-provided arrays
  * The module-level functions of the reference: compute_two_site_model_fields + compute_direct_info
@@ -364,6 +379,13 @@ int dca_mf_fields(dca_ctx* ctx, double* fields_out);
  * dca_mf_couplings. */
 int dca_mf_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out);
 int dca_mf_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out /* L*q */);
+/* dca_plm_sample under the mean-field model (J, h as in dca_mf_energies; zero on the gap state).  Same rule, RNG layout,
+ * determinism and argument checks; DCA_ERR_STATE before dca_mf_couplings. */
+int dca_mf_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                  const uint8_t* initial, uint8_t* out);
+/* The counter-based generator of the samplers, on the host: Philox4x32-10 (Salmon et al., SC 2011; 10 rounds, multipliers
+ * 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 / 0xBB67AE85).  Needs no device. */
+int dca_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
 /* coupling blocks of selected pairs, optionally gauge shifted (MeanFieldDCA.compute_params,
  * meanfield_dca.py:661-752; shift_couplings :636-658) */
 int dca_mf_pair_couplings(dca_ctx* ctx, const int* pairs, int npairs, int shift, double* out);
@@ -385,7 +407,7 @@ int dca_spd_inverse(dca_ctx* ctx, const double* A, int n, double* Ainv_out);
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
- * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan"). */
+ * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "sample"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it
  * instead of two per stage (an event record costs the stream ~5 us: 14 per plmDCA iteration are 5 % of config C's step, 0.4 % of

@@ -118,6 +118,9 @@ def lib():
         "dca_plm_mutation_scan": (i, [vp, vp, vp]),
         "dca_mf_energies": (i, [vp, vp, i, vp]),
         "dca_mf_mutation_scan": (i, [vp, vp, vp]),
+        "dca_plm_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
+        "dca_mf_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
+        "dca_philox4x32_10": (i, [vp, vp, vp]),
         "dca_mf_pair_couplings": (i, [vp, vp, i, i, vp]),
         "dca_mf_single_site_freqs": (i, [vp, vp]),
         "dca_mf_pair_site_freqs": (i, [vp, vp]),
@@ -158,6 +161,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_plm_lbfgs_begin", "dca_plm_lbfgs_iterate", "dca_plm_lbfgs_end", "dca_plm_scores", "dca_plm_di_scores",
            "dca_mf_di_scores", "dca_plm_pair_couplings", "dca_mf_fields", "dca_mf_pair_couplings",
            "dca_encode_sequences", "dca_plm_energies", "dca_plm_mutation_scan", "dca_mf_energies", "dca_mf_mutation_scan",
+           "dca_plm_sample", "dca_mf_sample", "dca_philox4x32_10",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
            "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
@@ -289,6 +293,15 @@ def encode_sequences(seqs, biomolecule, L, table):
     if rc in (DCA_ERR_ARG, DCA_ERR_RESIDUE) and bad.value >= 0:
         raise EncodeError(rc, bad.value, lib().dca_last_error().decode("utf-8", "replace"))
     check(rc)
+    return out
+
+
+def philox4x32_10(ctr, key):
+    """Philox4x32-10 of the samplers on the host (dca_philox4x32_10): 4 counter words, 2 key words -> uint32[4]."""
+    c = np.ascontiguousarray(ctr, dtype=np.uint32).reshape(4)
+    k = np.ascontiguousarray(key, dtype=np.uint32).reshape(2)
+    out = np.zeros(4, dtype=np.uint32)
+    check(lib().dca_philox4x32_10(_ptr(c), _ptr(k), _ptr(out)))
     return out
 
 
@@ -585,6 +598,25 @@ class Context:
 
     def mf_mutation_scan(self, wildtype):
         return self._mutation_scan(self._l.dca_mf_mutation_scan, wildtype)
+
+    # ---- Gibbs sampling (sample.hip): n chains, `sweeps` systematic sweeps -> uint8[n, L] codes
+    def _sample(self, fn, n, sweeps, seed, beta, initial, first_chain, first_sweep):
+        n = int(n)
+        init = None
+        if initial is not None:
+            init = np.ascontiguousarray(initial, dtype=np.uint8)
+            if init.shape != (n, self.L):
+                raise ValueError("initial must be uint8[%d, %d]" % (n, self.L))
+        out = np.zeros((max(n, 0), self.L), dtype=np.uint8)
+        check(fn(self._h, n, int(sweeps), int(seed), int(first_chain), int(first_sweep), float(beta),
+                 None if init is None else _ptr(init), _ptr(out)))
+        return out
+
+    def plm_sample(self, n, sweeps, seed=0, beta=1.0, initial=None, first_chain=0, first_sweep=0):
+        return self._sample(self._l.dca_plm_sample, n, sweeps, seed, beta, initial, first_chain, first_sweep)
+
+    def mf_sample(self, n, sweeps, seed=0, beta=1.0, initial=None, first_chain=0, first_sweep=0):
+        return self._sample(self._l.dca_mf_sample, n, sweeps, seed, beta, initial, first_chain, first_sweep)
 
     def mf_di_scores(self, apc=False):
         out = np.zeros(self.L * (self.L - 1) // 2, dtype=np.float64)

@@ -1,6 +1,8 @@
 """Query sequences of the energy methods of PlmDCA and MeanFieldDCA, encoded for the context (dca_encode_sequences)."""
 import os
 
+import numpy as np
+
 from . import _lib
 from .fasta_reader import fasta_reader
 
@@ -34,21 +36,75 @@ def wildtype_codes(wildtype, biomolecule, L, table, exc_type):
     return query_codes(seqs, biomolecule, L, table, exc_type)[0]
 
 
+def initial_codes(initial, num_sequences, biomolecule, L, table, exc_type):
+    """Starting sequences of the samplers -> uint8[num_sequences, L], or None (random starts).  initial: None, an aligned
+    string (every chain starts from it), a list of num_sequences aligned strings, or a FASTA file holding 1 or
+    num_sequences records (one record is replicated)."""
+    if initial is None:
+        return None
+    if isinstance(initial, (str, bytes, os.PathLike)) and os.path.isfile(os.fsdecode(initial)):
+        seqs = fasta_reader.get_alignment_from_fasta_file(os.fsdecode(initial), same_length=False)
+        where = 'the initial-sequence file {}'.format(os.fsdecode(initial))
+    elif isinstance(initial, str):
+        seqs, where = [initial], 'the initial sequence'
+    else:
+        seqs, where = [str(getattr(rec, 'seq', rec)) for rec in initial], 'the list of initial sequences'
+    if len(seqs) not in (1, num_sequences):
+        raise exc_type('{} holds {} records; sampling {} sequences needs 1 or {}'.format(where, len(seqs), num_sequences,
+                                                                                       num_sequences))
+    X = query_codes(seqs, biomolecule, L, table, exc_type)
+    return X if X.shape[0] == num_sequences else np.repeat(X, num_sequences, axis=0)
+
+
+def sampling_beta(temperature, exc_type):
+    """beta = 1 / temperature for a finite temperature > 0."""
+    t = float(temperature)
+    if not (0.0 < t < float('inf')):
+        raise exc_type('the temperature must be finite and > 0, not {}'.format(temperature))
+    return 1.0 / t
+
+
 def state_letters(biomolecule):
-    """Letter of every 0-based state (gap last), for the CLI's mutation-effect rows."""
+    """Letter of every 0-based state (gap last), for the CLI's mutation-effect rows and sampled sequences."""
     return list('ACDEFGHIKLMNPQRSTVWY-') if biomolecule == _lib.DCA_BIOMOLECULE_PROTEIN else list('ACGU-')
 
 
 
-POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects')
+POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences')
+
+
+def add_sampling_arguments(p):
+    """The options of the sample_sequences sub-command (plmdca and mfdca command lines)."""
+    p.add_argument('--num_sequences', type=int, required=True, help='number of sequences (independent chains) to draw (addition)')
+    p.add_argument('--num_sweeps', type=int, default=1000, help='Gibbs sweeps over all sites per chain (addition)')
+    p.add_argument('--seed', type=int, default=0, help='seed of the counter-based generator (addition)')
+    p.add_argument('--temperature', type=float, default=1.0, help='sampling temperature T, P(s) ~ exp(E(s) / T) (addition)')
+    p.add_argument('--initial_file', help='FASTA file with 1 or num_sequences aligned starting sequences (default: random) (addition)')
 
 
 def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata, biomolecule, table, exc_type,
-                   query_file=None, wildtype_file=None):
-    """compute_energies / compute_mutation_effects of the plmdca and mfdca command lines -> the path of the file written:
-    <output_dir>/<prefix>_energies_<alignment base>.txt or <prefix>_mutation_effects_<alignment base>.txt."""
+                   query_file=None, wildtype_file=None, sampling=None):
+    """compute_energies / compute_mutation_effects / sample_sequences of the plmdca and mfdca command lines -> the path of
+    the file written: <output_dir>/<prefix>_energies_<alignment base>.txt, <prefix>_mutation_effects_<alignment base>.txt
+    or <prefix>_samples_<alignment base>.fa.  sampling: the sample_sequences options (num_sequences, num_sweeps, seed,
+    temperature, initial_file)."""
     from .dca_utilities import dca_utilities
     dca_utilities.create_directories(output_dir)
+    if the_command == 'sample_sequences':
+        opts = dict(sampling or {})
+        if opts.get('num_sequences') is None:
+            raise exc_type('sample_sequences needs --num_sequences')
+
+        def opt(name, default):
+            return default if opts.get(name) is None else opts[name]
+        codes = instance.sample_sequences(opts['num_sequences'], num_sweeps=opt('num_sweeps', 1000), seed=opt('seed', 0),
+                                          temperature=opt('temperature', 1.0), initial=opts.get('initial_file'), return_codes=True)
+        letters = state_letters(biomolecule)
+        seqs = [''.join(letters[c] for c in row) for row in codes]
+        energies = instance.compute_sequence_energies(seqs) if seqs else []
+        path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_samples_', postfix='.fa')
+        dca_utilities.write_sampled_sequences(path, seqs, energies)
+        return path
     if the_command == 'compute_energies':
         energies = instance.compute_sequence_energies(query_file)
         path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_energies_', postfix='.txt')

@@ -502,6 +502,13 @@ int dca_plm_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out)
     if (!wildtype || !dE_out) return DCA_ERR_ARG;
     return ctx->plm->mutation_scan(wildtype, dE_out);
 }
+int dca_plm_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                   const uint8_t* initial, uint8_t* out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    return ctx->plm->sample(n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
+}
 int dca_plm_di_scores(dca_ctx* ctx, const double* reg_fi, int apc, double* out)
 {
     CHECK_CTX(ctx);
@@ -642,6 +649,13 @@ int dca_mf_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out)
     DCA_TRY(need_mf(ctx));
     if (!wildtype || !dE_out) return DCA_ERR_ARG;
     return dca_mf_engine_mutation_scan(ctx->mf, wildtype, dE_out);
+}
+int dca_mf_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                  const uint8_t* initial, uint8_t* out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_mf(ctx));
+    return dca_mf_engine_sample(ctx->mf, n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
 }
 int dca_mf_pair_couplings(dca_ctx* ctx, const int* pairs, int npairs, int shift, double* out)
 {

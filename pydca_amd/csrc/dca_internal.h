@@ -168,6 +168,8 @@ struct PlmEngineBase {
     virtual int pair_couplings(const int* pairs, int npairs, int shift, double* out) = 0;
     virtual int energies(const uint8_t* X, int n, double* out) = 0;            // energy.hip on the current x
     virtual int mutation_scan(const uint8_t* wildtype, double* out) = 0;
+    virtual int sample(int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                       const uint8_t* initial, uint8_t* out) = 0;                  // sample.hip on the current x
     virtual int set_vector_sharding(int rank, int world, dca_comm_hook hook, void* user) = 0;
     dca_reduce_hook hook = nullptr;
     void* hook_user = nullptr;
@@ -197,6 +199,11 @@ int dca_potts_energies(dca_ctx* ctx, const void* src, int src_kind, int dtype, c
 int dca_potts_mutation_scan(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
                             const uint8_t* wildtype, double* out /* L*q */);
 
+// ---- sample.hip : Gibbs sampling of n chains (one launch per sweep) under the same sources.  initial / out: host, n x L.
+int dca_potts_sample(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld, int n,
+                     int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                     const uint8_t* initial /* host n*L or NULL */, uint8_t* out /* host n*L */);
+
 int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, const double* reg_fi, int L, int q,
                             double* fields_out, double* di_out, const double* fields_in = nullptr);
 
@@ -218,6 +225,8 @@ void dca_mf_engine_invalidate(MfEngine*);      // weights changed: counts, frequ
 int dca_mf_engine_pair_couplings(MfEngine*, const int* pairs, int npairs, int shift, double* out);
 int dca_mf_engine_energies(MfEngine*, const uint8_t* X, int n, double* out);
 int dca_mf_engine_mutation_scan(MfEngine*, const uint8_t* wildtype, double* out);
+int dca_mf_engine_sample(MfEngine*, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                         const uint8_t* initial, uint8_t* out);
 
 // ---- cholinv.hip : scale * inverse of an SPD matrix on the device (f64 MFMA)
 // dA: n x n row-major (ld = n), n multiple of 64; destroyed (holds the triangular factor's inverse afterwards).

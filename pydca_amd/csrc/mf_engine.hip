@@ -625,6 +625,18 @@ int dca_mf_engine_mutation_scan(MfEngine* m, const uint8_t* wildtype, double* ou
     return rc;
 }
 
+int dca_mf_engine_sample(MfEngine* m, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                         const uint8_t* initial, uint8_t* out)
+{
+    double* dH = nullptr;
+    DCA_TRY(mf_fields_device(m, &dH));
+    const int rc = dca_potts_sample(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, n, sweeps, seed, first_chain, first_sweep, beta,
+                                    initial, out);
+    hipStreamSynchronize(m->ctx->stream);
+    dca_dev_free(dH);
+    return rc;
+}
+
 int dca_mf_engine_pair_couplings(MfEngine* m, const int* pairs, int npairs, int shift, double* out)
 {
     if (!m->have_J) { dca_set_error("dca_mf_couplings first"); return DCA_ERR_STATE; }

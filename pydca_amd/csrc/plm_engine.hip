@@ -2540,6 +2540,15 @@ struct PlmEngine : PlmEngineBase {
         if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
         return dca_potts_mutation_scan(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, wildtype, out);
     }
+    // Gibbs samples of the current x (sample.hip); column strips gather x first, as energies() does
+    int sample(int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta, const uint8_t* initial,
+               uint8_t* out) override
+    {
+        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
+        if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
+        return dca_potts_sample(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, n, sweeps, seed, first_chain, first_sweep, beta,
+                                initial, out);
+    }
 
     // DI of the current x (plmdca.py:683-790); reg_fi: host, L*q regularised single-site frequencies
     int di_scores(const double* reg_fi, int apc, double* out) override

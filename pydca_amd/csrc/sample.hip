@@ -1,0 +1,342 @@
+// Systematic-scan Gibbs sampling of a fitted Potts model, P(s) ~ exp(beta * E(s)), E as in energy.hip:
+//   one sweep visits sites i = 0 .. L-1 in order; at site i chain c forms
+//     u_i(a) = h_i(a) + sum_{j != i} J(a, s_j)        (J read from the pair block (min(i,j), max(i,j)), as energy.hip reads it)
+//   for every state a < q (gap included) and draws s_i from p_a = exp(beta * (u_i(a) - max_b u_i(b))).
+// Parameter sources: kind 0 = the packed plm vector x (float or double), kind 1 = the dense mf -inv(C) (double, leading
+// dimension ld) with the mf fields; both zero on the gap state q-1.
+//
+// Summation order (depends on (L, q, dtype) only): every term widened to double;
+//   u(a) = (((h_i(a) + S_0(a)) + S_1(a)) + S_2(a)) + S_3(a),  S_w(a) = sum over j = w (mod 4), j != i, ascending j.
+// Draw rule (restated by the tests): T = sum_a p_a ascending; r = U * T; s_i = the smallest a with p_0 + ... + p_a > r
+// (ascending sums), or the largest a with p_a > 0 if rounding leaves none.  U = Philox4x32-10 of
+//   key = (seed lo, seed hi), counter = (chain, sweep, site, tag) (each word the value mod 2^32), tag 0: Gibbs draw,
+//   tag 1: initial state (sweep word 0, s_i = floor(U * q)); U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.
+//
+// Geometry: one workgroup of 4 waves holds 64 chains (lane = chain) in lockstep over the sites.  Wave w sums the j = w
+// (mod 4) terms; the partials meet in LDS in ascending w and wave 0 draws.  Row i of J (L blocks of q x q) streams through
+// LDS in double-buffered chunks of CJ blocks (CJ a multiple of 4), each block stored transposed, T[b][a] = J(a, b) with rows
+// padded to QM values, so that a lane reads J(., s_j) as QM contiguous values; the next chunk's loads are in flight in
+// registers while the current one is summed.  Chain codes live in LDS (64 x L bytes) when L <= kSResidentL, otherwise in
+// the global site-major state buffer.  One launch is one sweep; no atomics, no inter-workgroup communication.
+#include "dca_internal.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int kSThreads = 256;                    // 4 waves, 64 chains
+constexpr int kSChains = 64;
+constexpr int kSResidentL = 512;                  // chain codes in LDS up to 32 KiB
+constexpr size_t kSChunkBudget = 40 * 1024;       // LDS per J chunk buffer (two of them)
+
+__host__ __device__ __forceinline__ void philox4x32_10(const uint32_t in[4], const uint32_t k[2], uint32_t out[4])
+{
+    uint32_t c0 = in[0], c1 = in[1], c2 = in[2], c3 = in[3], k0 = k[0], k1 = k[1];
+    for (int r = 0; r < 10; ++r) {
+        if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+__device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t chain, uint64_t sweep, int site, uint32_t tag)
+{
+    const uint32_t ctr[4] = {(uint32_t)chain, (uint32_t)sweep, (uint32_t)site, tag};
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    uint32_t w[4];
+    philox4x32_10(ctr, key, w);
+    return (double)((uint64_t)(w[0] >> 5) * 67108864ull + (w[1] >> 6)) * 0x1.0p-53;
+}
+
+__device__ __forceinline__ size_t pair_index(int L, int i, int j)
+{
+    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
+}
+
+// J_ij(a, b) for i < j, widened to double (energy.hip's coupling())
+template <typename S>
+__device__ __forceinline__ double coupling(const S* src, int kind, int L, int q, int ld, int i, int j, int a, int b)
+{
+    if (kind == 0) return (double)src[(size_t)L * q + pair_index(L, i, j) * (size_t)q * q + (size_t)a * q + b];
+    const int qm = q - 1;
+    if (a == qm || b == qm) return 0.0;
+    return (double)src[(size_t)(i * qm + a) * ld + (size_t)j * qm + b];
+}
+
+template <typename S>
+__device__ __forceinline__ double field(const S* src, const double* mfh, int kind, int q, int i, int a)
+{
+    if (kind == 0) return (double)src[(size_t)i * q + a];
+    return a == q - 1 ? 0.0 : mfh[(size_t)i * (q - 1) + a];
+}
+
+// floor(e / d) for e * d < 2^32: m = floor(2^32 / d) + 1
+__device__ __forceinline__ int fast_div(int e, uint32_t m) { return (int)__umulhi((uint32_t)e, m); }
+
+// rows (n x L) <-> site-major state (st[s * nS + c], nS a multiple of 64; chains past n start at code 0)
+__global__ void rows_to_sites_kernel(const uint8_t* __restrict__ rows, int n, int L, int nS, uint8_t* __restrict__ st)
+{
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t >= (size_t)L * nS) return;
+    const int s = (int)(t / nS), c = (int)(t % nS);
+    st[t] = c < n ? rows[(size_t)c * L + s] : 0;
+}
+
+__global__ void sites_to_rows_kernel(const uint8_t* __restrict__ st, int n, int L, int nS, uint8_t* __restrict__ rows)
+{
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t >= (size_t)n * L) return;
+    const int c = (int)(t / L), s = (int)(t % L);
+    rows[t] = st[(size_t)s * nS + c];
+}
+
+// initial state of tag 1: s_i = floor(U * q) (sweep word 0)
+__global__ void initial_state_kernel(int n, int L, int q, int nS, uint64_t seed, uint64_t first_chain, uint8_t* __restrict__ st)
+{
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t >= (size_t)L * nS) return;
+    const int s = (int)(t / nS), c = (int)(t % nS);
+    st[t] = c < n ? (uint8_t)(int)(philox_uniform(seed, first_chain + c, 0, s, 1) * q) : 0;
+}
+
+// One sweep.  grid: nS / 64 workgroups.  LDS: two chunk buffers (CJ blocks of q x QM values of S each), the partial
+// buffer (QM x 64 doubles), and with RES the chain codes (L x 64 bytes, site-major).  R: chunk elements per thread.
+template <typename S, int QM, bool RES, int R>
+__global__ __launch_bounds__(kSThreads)
+void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __restrict__ mfh, int L, int q, int ld, int CJ,
+                        uint8_t* __restrict__ state, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char sample_smem[];
+    const int blk = q * QM;                                   // values of one staged block
+    const int bufVals = CJ * blk;
+    S* buf0 = reinterpret_cast<S*>(sample_smem);
+    double* P = reinterpret_cast<double*>(sample_smem + ((size_t)2 * bufVals * sizeof(S) + 15) / 16 * 16);
+    uint8_t* stL = reinterpret_cast<uint8_t*>(P + QM * kSChains);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int c0 = blockIdx.x * kSChains;
+    const uint64_t chain = first_chain + (uint64_t)(c0 + lane);
+    const int qq = q * q;
+    const uint32_t mqq = 0xffffffffu / (uint32_t)qq + 1, mq = 0xffffffffu / (uint32_t)q + 1;
+    const int nch = (L + CJ - 1) / CJ;
+    const int steps = L * nch;
+    const int chunkVals = CJ * qq;
+
+    for (int e = tid; e < 2 * bufVals; e += kSThreads) buf0[e] = (S)0;      // the row padding stays zero
+    if (RES)
+        for (int e = tid; e < L * kSChains; e += kSThreads) stL[e] = state[(size_t)(e >> 6) * nS + c0 + (e & 63)];
+
+    S val[R];
+    int dst[R];
+    // registers <- the chunk of step t (site t / nch, blocks j0 .. j0 + CJ - 1)
+    auto load = [&](int t) {
+        const int i = t / nch, j0 = (t - i * nch) * CJ;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int e = tid + r * kSThreads;
+            dst[r] = -1;
+            if (e >= chunkVals) continue;
+            const int jj = fast_div(e, mqq), k = e - jj * qq;
+            const int j = j0 + jj;
+            if (j >= L || j == i) continue;
+            const int hi = fast_div(k, mq), lo = k - hi * q;
+            const int a = j > i ? hi : lo, b = j > i ? lo : hi;          // source order: (a, b) rows for j > i, (b, a) for j < i
+            val[r] = (S)(j > i ? coupling(src, kind, L, q, ld, i, j, a, b) : coupling(src, kind, L, q, ld, j, i, b, a));
+            dst[r] = jj * blk + b * QM + a;
+        }
+    };
+    auto store = [&](S* buf) {
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            if (dst[r] >= 0) buf[dst[r]] = val[r];
+    };
+    auto code = [&](int j) -> int { return RES ? stL[j * kSChains + lane] : state[(size_t)j * nS + c0 + lane]; };
+
+    __syncthreads();
+    load(0);
+    store(buf0);
+    __syncthreads();
+
+    double u[QM];
+    for (int t = 0; t < steps; ++t) {
+        const int i = t / nch, ch = t - i * nch, j0 = ch * CJ;
+        if (ch == 0) {
+#pragma unroll
+            for (int a = 0; a < QM; ++a) u[a] = (wave == 0 && a < q) ? field(src, mfh, kind, q, i, a) : 0.0;
+        }
+        if (t + 1 < steps) load(t + 1);
+        const S* cur = buf0 + (t & 1) * bufVals;
+        for (int jj = wave; jj < CJ; jj += 4) {
+            const int j = j0 + jj;
+            if (j >= L) break;
+            if (j == i) continue;
+            const S* row = cur + jj * blk + code(j) * QM;
+            if constexpr (sizeof(S) == 4) {
+#pragma unroll
+                for (int a = 0; a < QM; a += 4) {
+                    const float4 v = *reinterpret_cast<const float4*>(row + a);
+                    u[a] += (double)v.x; u[a + 1] += (double)v.y; u[a + 2] += (double)v.z; u[a + 3] += (double)v.w;
+                }
+            } else {
+#pragma unroll
+                for (int a = 0; a < QM; a += 2) {
+                    const double2 v = *reinterpret_cast<const double2*>(row + a);
+                    u[a] += v.x; u[a + 1] += v.y;
+                }
+            }
+        }
+        if (t + 1 < steps) store(buf0 + ((t + 1) & 1) * bufVals);
+        if (ch == nch - 1) {                                  // site i complete: S_1, S_2, S_3 join wave 0's h + S_0 in order
+            for (int w = 1; w < 4; ++w) {
+                if (wave == w)
+#pragma unroll
+                    for (int a = 0; a < QM; ++a) P[a * kSChains + lane] = u[a];
+                __syncthreads();
+                if (wave == 0)
+#pragma unroll
+                    for (int a = 0; a < QM; ++a) u[a] += P[a * kSChains + lane];
+                __syncthreads();
+            }
+            if (wave == 0) {
+                double m = u[0];
+#pragma unroll
+                for (int a = 1; a < QM; ++a) if (a < q) m = fmax(m, u[a]);
+                double T = 0.0;
+#pragma unroll
+                for (int a = 0; a < QM; ++a) {
+                    u[a] = a < q ? exp(beta * (u[a] - m)) : 0.0;
+                    T += u[a];
+                }
+                const double r = philox_uniform(seed, chain, sweep, i, 0) * T;
+                int pick = -1, last = 0;
+                double cum = 0.0;
+#pragma unroll
+                for (int a = 0; a < QM; ++a) {
+                    if (a < q) {
+                        cum += u[a];
+                        if (pick < 0 && cum > r) pick = a;
+                        if (u[a] > 0.0) last = a;
+                    }
+                }
+                if (pick < 0) pick = last;
+                if (RES) stL[i * kSChains + lane] = (uint8_t)pick;
+                else state[(size_t)i * nS + c0 + lane] = (uint8_t)pick;
+            }
+        }
+        __syncthreads();
+    }
+    if (RES)
+        for (int e = tid; e < L * kSChains; e += kSThreads) state[(size_t)(e >> 6) * nS + c0 + (e & 63)] = stL[e];
+}
+
+struct SampleGeom { int QM, CJ; bool res; size_t lds; };
+
+SampleGeom sample_geometry(int L, int q, size_t elem)
+{
+    SampleGeom g{};
+    g.QM = q <= 8 ? 8 : q <= 24 ? 24 : 32;
+    const size_t blkBytes = (size_t)q * g.QM * elem;
+    const int R = elem == 4 ? 32 : 16;
+    int cj = std::min((int)(kSThreads * R / (q * q)), (int)(kSChunkBudget / blkBytes));
+    g.CJ = std::max(4, cj / 4 * 4);
+    g.res = L <= kSResidentL;
+    g.lds = round_up(2 * (size_t)g.CJ * blkBytes, 16) + (size_t)g.QM * kSChains * sizeof(double) + (g.res ? (size_t)L * kSChains : 0);
+    return g;
+}
+
+template <typename S, int QM, bool RES>
+hipError_t launch_sweep(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
+                        uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta)
+{
+    constexpr int R = sizeof(S) == 4 ? 32 : 16;
+    auto kern = gibbs_sweep_kernel<S, QM, RES, R>;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(nS / kSChains), dim3(kSThreads), sg.lds, ctx->stream, src, kind, mfh, L, q, ld, sg.CJ, dState, nS,
+                       seed, first_chain, sweep, beta);
+    return hipGetLastError();
+}
+
+template <typename S, int QM>
+hipError_t dispatch_res(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
+                        uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta)
+{
+    if (sg.res) return launch_sweep<S, QM, true>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
+    return launch_sweep<S, QM, false>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
+}
+
+template <typename S>
+hipError_t dispatch_sweep(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
+                          uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta)
+{
+    switch (sg.QM) {
+    case 8: return dispatch_res<S, 8>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
+    case 24: return dispatch_res<S, 24>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
+    default: return dispatch_res<S, 32>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
+    }
+}
+
+template <typename S>
+int sample_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q, int ld, int n, int sweeps, uint64_t seed,
+             uint64_t first_chain, uint64_t first_sweep, double beta, const uint8_t* initial, uint8_t* out)
+{
+    const SampleGeom sg = sample_geometry(L, q, sizeof(S));
+    const int nS = (int)round_up((size_t)n, kSChains);
+    const size_t sites = (size_t)L * nS;
+    uint8_t *dRows = nullptr, *dState = nullptr;
+    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)n * L, false);
+    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dState), sites, false);
+    if (e == hipSuccess) {
+        if (initial) {
+            e = hipMemcpyAsync(dRows, initial, (size_t)n * L, hipMemcpyHostToDevice, ctx->stream);
+            if (e == hipSuccess)
+                hipLaunchKernelGGL(rows_to_sites_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, dRows, n, L, nS, dState);
+        } else {
+            hipLaunchKernelGGL(initial_state_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, n, L, q, nS, seed,
+                               first_chain, dState);
+        }
+        if (e == hipSuccess) e = hipGetLastError();
+    }
+    for (int t = 0; t < sweeps && e == hipSuccess; ++t) {       // one launch per sweep
+        ScopedKernelClock kc(ctx, "sample");
+        e = dispatch_sweep<S>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, first_sweep + (uint64_t)t, beta);
+    }
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(sites_to_rows_kernel, dim3((unsigned)(((size_t)n * L + 255) / 256)), dim3(256), 0, ctx->stream, dState, n, L, nS, dRows);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dRows, (size_t)n * L, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dca_dev_free(dRows); dca_dev_free(dState);
+    if (e != hipSuccess) { dca_set_error("sample: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    return DCA_OK;
+}
+
+}  // namespace
+
+int dca_potts_sample(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld, int n,
+                     int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta, const uint8_t* initial,
+                     uint8_t* out)
+{
+    if (n < 0 || sweeps < 0 || !(beta >= 0.0) || std::isinf(beta) || (n > 0 && !out)) {
+        dca_set_error("sample: bad arguments (n %d, sweeps %d, beta %g)", n, sweeps, beta);
+        return DCA_ERR_ARG;
+    }
+    if (n == 0) return DCA_OK;
+    if (initial)
+        for (size_t k = 0; k < (size_t)n * L; ++k)
+            if (initial[k] >= q) { dca_set_error("sample: initial code %d >= q at element %zu", (int)initial[k], k); return DCA_ERR_ARG; }
+    if (dtype == DCA_F32)
+        return sample_t(ctx, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, n, sweeps, seed, first_chain, first_sweep, beta,
+                        initial, out);
+    return sample_t(ctx, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, n, sweeps, seed, first_chain, first_sweep, beta,
+                    initial, out);
+}
+
+int dca_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])
+{
+    if (!ctr || !key || !out) { dca_set_error("philox: bad arguments"); return DCA_ERR_ARG; }
+    philox4x32_10(ctr, key, out);
+    return DCA_OK;
+}

@@ -107,6 +107,13 @@ def write_mutation_effects(file_name, dE, wildtype_letters, state_letters, metad
     _stream(file_name, header, rows, 'single-mutant effects')
 
 
+def write_sampled_sequences(file_name, sequences, energies):
+    """FASTA of sampled sequences: one record '>sample_<k> energy=<E>' per sequence (k from 1, E written with %.17g so
+    that it reads back to the same double), the aligned sequence on one line (no reference counterpart)."""
+    rows = ('>sample_{} energy={}\n{}'.format(k + 1, '%.17g' % float(e), seq) for k, (seq, e) in enumerate(zip(sequences, energies)))
+    _stream(file_name, [], rows, 'sampled sequences')
+
+
 def _csv(prefix_values, values):
     # '{}'.format(v), not str(v): numpy scalars of the two print differently (a float32 is widened by format)
     return ','.join('{}'.format(v) for v in list(prefix_values) + list(values))

@@ -287,6 +287,25 @@ class MeanFieldDCA:
         logger.info('\n\tSingle-mutant effects of the wild type')
         return self._with_couplings(lambda: self.__ctx.mf_mutation_scan(w))
 
+    def sample_sequences(self, num_sequences, num_sweeps=1000, seed=0, temperature=1.0, initial=None, return_codes=False):
+        """Draws num_sequences sequences from P(s) ~ exp(E(s) / temperature) by systematic-scan Gibbs sampling on the GPU:
+        one independent chain per sequence, num_sweeps sweeps over all sites (E as in compute_sequence_energies; the couplings are computed first if
+        none are there yet).
+        initial: None (random starts), an aligned string (every chain starts from it), a list of num_sequences aligned
+        strings, or a FASTA file with 1 or num_sequences records.  The draws follow a counter-based generator of `seed`:
+        the same arguments give the same sequences.  -> aligned strings (gap '-'), or uint8[n, L] codes with
+        return_codes."""
+        n = int(num_sequences)
+        beta = _potts.sampling_beta(temperature, MeanFieldDCAException)
+        bio = _lib.DCA_BIOMOLECULE_PROTEIN if self.__num_site_states == 21 else _lib.DCA_BIOMOLECULE_RNA
+        X0 = _potts.initial_codes(initial, n, bio, self.__sequences_len, 1, MeanFieldDCAException)
+        logger.info('\n\tGibbs sampling of {} sequences, {} sweeps'.format(n, num_sweeps))
+        codes = self._with_couplings(lambda: self.__ctx.mf_sample(n, num_sweeps, seed=seed, beta=beta, initial=X0))
+        if return_codes:
+            return codes
+        letters = _potts.state_letters(bio)
+        return [''.join(letters[c] for c in row) for row in codes]
+
     def shift_couplings(self, couplings_ij):
         """meanfield_dca.py:636-658 (zero-sum gauge of one block)."""
         qm1 = self.__num_site_states - 1

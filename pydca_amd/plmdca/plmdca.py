@@ -312,6 +312,23 @@ class PlmDCA:
         logger.info('\n\tSingle-mutant effects of the wild type')
         return self._fitted_context().plm_mutation_scan(w)
 
+    def sample_sequences(self, num_sequences, num_sweeps=1000, seed=0, temperature=1.0, initial=None, return_codes=False):
+        """Draws num_sequences sequences from P(s) ~ exp(E(s) / temperature) by systematic-scan Gibbs sampling on the GPU:
+        one independent chain per sequence, num_sweeps sweeps over all sites (E as in compute_sequence_energies).
+        initial: None (random starts), an aligned string (every chain starts from it), a list of num_sequences aligned
+        strings, or a FASTA file with 1 or num_sequences records.  The draws follow a counter-based generator of `seed`:
+        the same arguments give the same sequences.  -> aligned strings (gap '-'), or uint8[n, L] codes with
+        return_codes."""
+        n = int(num_sequences)
+        beta = _potts.sampling_beta(temperature, PlmDCAException)
+        X0 = _potts.initial_codes(initial, n, self.__biomolecule_int, self.__seqs_len, 0, PlmDCAException)
+        logger.info('\n\tGibbs sampling of {} sequences, {} sweeps'.format(n, num_sweeps))
+        codes = self._fitted_context().plm_sample(n, num_sweeps, seed=seed, beta=beta, initial=X0)
+        if return_codes:
+            return codes
+        letters = _potts.state_letters(self.__biomolecule_int)
+        return [''.join(letters[c] for c in row) for row in codes]
+
     def compute_seqs_weight(self):
         """plmdca.py:565-591: weights of the PYTHON reader's alignment (float64 comparison,
         plmdca/msa_numerics.py:13-49), computed on the device; remembered with their sum like the

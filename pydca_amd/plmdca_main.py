@@ -21,7 +21,7 @@ def configure_logging():
 def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_file=None, seqid=None, lambda_h=None,
                               lambda_J=None, max_iterations=None, apc=False, verbose=False, output_dir=None,
                               num_threads=None, ranked_by=None, linear_dist=None, num_site_pairs=None, device=0,
-                              exact_gradient=False, precision=32, devices=None, query_file=None, wildtype_file=None):
+                              exact_gradient=False, precision=32, devices=None, query_file=None, wildtype_file=None, sampling=None):
     if verbose:
         configure_logging()
     plmdca_instance = plmdca.PlmDCA(msa_file, biomolecule, seqid=seqid, lambda_h=lambda_h, lambda_J=lambda_J,
@@ -33,7 +33,7 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
         return _potts.run_subcommand(plmdca_instance, the_command, 'PLMDCA', msa_file, output_dir,
                                      dca_utilities.plmdca_param_metadata(plmdca_instance),
                                      _lib.DCA_BIOMOLECULE_PROTEIN if plmdca_instance.biomolecule == 'PROTEIN' else _lib.DCA_BIOMOLECULE_RNA, 0,
-                                     plmdca.PlmDCAException, query_file=query_file, wildtype_file=wildtype_file)
+                                     plmdca.PlmDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling)
     if the_command in DCA_COMPUTATION_SUBCOMMANDS:
         param_metadata = dca_utilities.plmdca_param_metadata(plmdca_instance)
         if not output_dir:
@@ -106,6 +106,8 @@ def run_plm_dca(argv=None):
             p.add_argument('--query_file', help='FASTA file of aligned query sequences (default: the records of msa_file) (addition)')
         if name == 'compute_mutation_effects':
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence (addition)')
+        if name == 'sample_sequences':
+            _potts.add_sampling_arguments(p)
         p.add_argument('--output_dir')
         p.add_argument('--device', type=int, default=0, help='GPU index (addition)')
         p.add_argument('--devices', help='comma-separated GPU indices, e.g. 0,1,2,3,4,5,6,7: one rank per GPU, sequences (or sites) '
@@ -127,7 +129,8 @@ def run_plm_dca(argv=None):
         apc=args.get('apc'), output_dir=args.get('output_dir'), verbose=args.get('verbose'),
         ranked_by=args.get('ranked_by'), linear_dist=args.get('linear_dist'), num_site_pairs=args.get('num_site_pairs'),
         device=args.get('device'), exact_gradient=args.get('exact_gradient'), precision=args.get('precision'),
-        devices=args.get('devices'), query_file=args.get('query_file'), wildtype_file=args.get('wildtype_file'))
+        devices=args.get('devices'), query_file=args.get('query_file'), wildtype_file=args.get('wildtype_file'),
+        sampling={k: args.get(k) for k in ('num_sequences', 'num_sweeps', 'seed', 'temperature', 'initial_file')})
 
 
 if __name__ == '__main__':
