@@ -335,6 +335,58 @@ int dca_plm_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out 
 int dca_plm_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                    const uint8_t* initial, uint8_t* out);
 
+/* ------------------------------------------------------------------ Boltzmann machine learning (bmDCA) of the plm model
+ * Refines the context's x (fields h: L*q, then the q x q blocks J_ij, i < j, pair order; storage precision P = the context's
+ * float32 / float64) by gradient ascent on the L2-regularised log-likelihood per effective sequence, with the model's
+ * frequencies estimated from n persistent Gibbs chains kept on the device.  q states, gap (q-1) included everywhere.
+ *
+ * Data statistics, formed once by dca_plm_bm_begin from the alignment X (N x L) and its current weights w: Meff = sum_n w_n,
+ * f_i(a) = sum_n w_n [X_ni = a] / Meff, f_ij(a,b) likewise (i < j), then f^_i = (1 - lambda) f_i + lambda / q and
+ * f^_ij = (1 - lambda) f_ij + lambda / q^2 (lambda = pseudocount); every operation rounded in double in the order written.
+ * With integer weights every count is exact.
+ *
+ * Chains and sweeps: chain k is Philox chain k and follows dca_plm_sample's draw rule with beta = 1; it starts at the tag-1 random
+ * state or at row k of `initial`.  Sweeps 0 .. E-1 (equilibration) run under the starting x.  Iteration t (counted from begin
+ * across iterate calls) runs sweeps E + t k .. E + t k + k - 1 under the current x.  So with eta_h = eta_J = 0 the chains after
+ * T iterations are bit for bit dca_plm_sample(n, E + T k, seed, 0, 0, 1.0, initial), and x does not change.
+ *
+ * Model statistics after iteration t's sweeps: integer counts c_i(a), c_ij(a,b) over the n chains, g_i = c_i / n,
+ * g_ij = c_ij / n (one correctly rounded division each).
+ * Update of every parameter theta with its f^, g, rate eta (eta_h fields, eta_J couplings) and L2 weight mu (mu_h, mu_J):
+ * d = f^ - g, r = mu * theta, s = d - r, theta' = theta + eta * s, in double with theta widened, rounded once to P.
+ *
+ * Record of iteration t (the chains after its sweeps, before its update: it describes the x the sweeps ran under):
+ * eps_h = max |f^_i(a) - g_i(a)|, eps_J = max over i < j, a, b of |f^_ij - g_ij|, pearson = the Pearson correlation over the
+ * M = pairs * q^2 values of C^d = f^_ij - f^_i f^_j and C^m = g_ij - g_i g_j:  with the sums S_d, S_m, S_dd, S_mm, S_dm,
+ * cov = S_dm / M - (S_d / M)(S_m / M), v_d = S_dd / M - (S_d / M)^2, v_m likewise, pearson = cov / sqrt(v_d v_m) (0 when
+ * v_d v_m <= 0).  The sums run in double in an order fixed by (L, q): repeated runs give the same bits.
+ *
+ * State: DCA_ERR_STATE before dca_plm_configure, during an L-BFGS run (dca_plm_lbfgs_end first), under column strips, vector
+ * sharding, a reduce / comm hook or a native-comm mode (one GPU only); iterate / freqs / chains without a run.  A run ends with
+ * dca_set_msa, any weights call, dca_plm_configure(_strips), dca_plm_lbfgs_begin, dca_plm_release and dca_plm_bm_end;
+ * dca_plm_bm_begin during a run starts a new one.  dca_plm_set_x during a run is allowed: the next iteration continues from it.
+ * The run never touches the alignment, the weights or g; x is the context's x, so energies, scans, sampling and scores read the
+ * refined model.  Profiling tags: the sweeps "sample", the statistics and update launches "bm_stats".  No reference counterpart. */
+typedef struct dca_bm_args {
+    int chains, sweeps, equilibration_sweeps;   /* n >= 1, k >= 1, E >= 0 */
+    uint64_t seed;
+    double eta_h, eta_J, mu_h, mu_J;            /* >= 0, finite */
+    double pseudocount;                         /* [0, 1) */
+    const uint8_t* initial;                     /* n x L host codes < q, or NULL: random starts */
+} dca_bm_args;
+typedef struct { double eps_h, eps_J, pearson; } dca_bm_record;
+/* data statistics, chains, E sweeps.  DCA_ERR_ARG: args NULL or out of range, an initial code >= q */
+int dca_plm_bm_begin(dca_ctx* ctx, const dca_bm_args* args);
+/* `iterations` iterations (0: nothing; < 0: DCA_ERR_ARG); records_out: iterations records, or NULL */
+int dca_plm_bm_iterate(dca_ctx* ctx, int iterations, dca_bm_record* records_out);
+/* which 0: f^ (the data); 1: g of the last iteration (DCA_ERR_STATE before the first); either output may be NULL.
+ * fi_out: L*q, fij_out: pairs*q*q in pair order.  DCA_ERR_ARG for another `which` */
+int dca_plm_bm_freqs(dca_ctx* ctx, int which, double* fi_out, double* fij_out);
+/* the chains' current codes, n x L (DCA_ERR_ARG: out NULL) */
+int dca_plm_bm_chains(dca_ctx* ctx, uint8_t* out);
+/* ends the run (x keeps its refined values); DCA_OK without a run */
+int dca_plm_bm_end(dca_ctx* ctx);
+
 /* ------------------------------------------------------------------ DI on caller-provided arrays
  * The module-level functions of the reference: compute_two_site_model_fields + compute_direct_info
  * (meanfield_dca/msa_numerics.py:378-533: layout 1 = couplings as the n x n matrix, n = L(q-1);
@@ -407,7 +459,8 @@ int dca_spd_inverse(dca_ctx* ctx, const double* A, int n, double* Ainv_out);
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
- * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "sample"). */
+ * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "sample",
+ * "bm_stats"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it
  * instead of two per stage (an event record costs the stream ~5 us: 14 per plmDCA iteration are 5 % of config C's step, 0.4 % of

@@ -35,6 +35,13 @@ class PlmStats(C.Structure):
                 ("seconds", C.c_double)]
 
 
+class BmArgs(C.Structure):
+    """dca_bm_args (include/dca_hip.h)"""
+    _fields_ = [("chains", C.c_int), ("sweeps", C.c_int), ("equilibration_sweeps", C.c_int), ("seed", C.c_uint64),
+                ("eta_h", C.c_double), ("eta_J", C.c_double), ("mu_h", C.c_double), ("mu_J", C.c_double),
+                ("pseudocount", C.c_double), ("initial", C.c_void_p)]
+
+
 COMM_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
 COMM_ALL_REDUCE, COMM_REDUCE_SCATTER, COMM_ALL_GATHER = 0, 1, 2
 REDUCE_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -121,6 +128,11 @@ def lib():
         "dca_plm_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
         "dca_mf_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
         "dca_philox4x32_10": (i, [vp, vp, vp]),
+        "dca_plm_bm_begin": (i, [vp, C.POINTER(BmArgs)]),
+        "dca_plm_bm_iterate": (i, [vp, i, vp]),
+        "dca_plm_bm_freqs": (i, [vp, i, vp, vp]),
+        "dca_plm_bm_chains": (i, [vp, vp]),
+        "dca_plm_bm_end": (i, [vp]),
         "dca_mf_pair_couplings": (i, [vp, vp, i, i, vp]),
         "dca_mf_single_site_freqs": (i, [vp, vp]),
         "dca_mf_pair_site_freqs": (i, [vp, vp]),
@@ -162,6 +174,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_mf_di_scores", "dca_plm_pair_couplings", "dca_mf_fields", "dca_mf_pair_couplings",
            "dca_encode_sequences", "dca_plm_energies", "dca_plm_mutation_scan", "dca_mf_energies", "dca_mf_mutation_scan",
            "dca_plm_sample", "dca_mf_sample", "dca_philox4x32_10",
+           "dca_plm_bm_begin", "dca_plm_bm_iterate", "dca_plm_bm_freqs", "dca_plm_bm_chains", "dca_plm_bm_end",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
            "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
@@ -617,6 +630,41 @@ class Context:
 
     def mf_sample(self, n, sweeps, seed=0, beta=1.0, initial=None, first_chain=0, first_sweep=0):
         return self._sample(self._l.dca_mf_sample, n, sweeps, seed, beta, initial, first_chain, first_sweep)
+
+    # ---- Boltzmann machine learning of x (boltzmann.hip): persistent chains on the device, records (eps_h, eps_J, pearson)
+    def plm_bm_begin(self, chains, sweeps, equilibration_sweeps, seed=0, eta_h=0.0, eta_J=0.0, mu_h=0.0, mu_J=0.0,
+                     pseudocount=0.0, initial=None):
+        init = None
+        if initial is not None:
+            init = np.ascontiguousarray(initial, dtype=np.uint8)
+            if init.shape != (int(chains), self.L):
+                raise ValueError("initial must be uint8[%d, %d]" % (int(chains), self.L))
+        args = BmArgs(int(chains), int(sweeps), int(equilibration_sweeps), int(seed), float(eta_h), float(eta_J), float(mu_h),
+                      float(mu_J), float(pseudocount), None if init is None else init.ctypes.data)
+        check(self._l.dca_plm_bm_begin(self._h, C.byref(args)))
+        self._bm_chains = int(chains)
+
+    def plm_bm_iterate(self, iterations):
+        """-> float64[iterations, 3]: (eps_h, eps_J, pearson) of every iteration"""
+        out = np.zeros((max(int(iterations), 0), 3), dtype=np.float64)
+        check(self._l.dca_plm_bm_iterate(self._h, int(iterations), _ptr(out) if out.size else None))
+        return out
+
+    def plm_bm_freqs(self, which):
+        """which 0: the regularised data frequencies; 1: the chains' frequencies of the last iteration
+        -> (float64[L, q], float64[pairs, q, q])"""
+        fi = np.zeros((self.L, self.q), dtype=np.float64)
+        fij = np.zeros((self.L * (self.L - 1) // 2, self.q, self.q), dtype=np.float64)
+        check(self._l.dca_plm_bm_freqs(self._h, int(which), _ptr(fi), _ptr(fij)))
+        return fi, fij
+
+    def plm_bm_chains(self):
+        out = np.zeros((getattr(self, "_bm_chains", 0), self.L), dtype=np.uint8)
+        check(self._l.dca_plm_bm_chains(self._h, _ptr(out)))
+        return out
+
+    def plm_bm_end(self):
+        check(self._l.dca_plm_bm_end(self._h))
 
     def mf_di_scores(self, apc=False):
         out = np.zeros(self.L * (self.L - 1) // 2, dtype=np.float64)

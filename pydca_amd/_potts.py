@@ -119,3 +119,55 @@ def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata
     path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_mutation_effects_', postfix='.txt')
     dca_utilities.write_mutation_effects(path, dE, [letters[c] for c in w], letters, metadata=metadata, wildtype_file=wildtype_file)
     return path
+
+
+def add_boltzmann_arguments(p):
+    """The options of the plmdca fit_boltzmann sub-command (PlmDCA.fit_boltzmann; --lambda_h / --lambda_J stay the
+    pseudo-likelihood fit's penalties, the L2 weights of the refinement are --bm_lambda_h / --bm_lambda_J)."""
+    p.add_argument('--iterations', type=int, default=500, help='Boltzmann-learning iterations (addition)')
+    p.add_argument('--num_chains', type=int, default=1000, help='persistent Gibbs chains (addition)')
+    p.add_argument('--sweeps_per_iteration', type=int, default=10, help='Gibbs sweeps of every chain per iteration (addition)')
+    p.add_argument('--equilibration_sweeps', type=int, default=100, help='sweeps before the first iteration (addition)')
+    p.add_argument('--learning_rate', type=float, default=0.05, help='gradient step of fields and couplings (addition)')
+    p.add_argument('--bm_lambda_h', type=float, default=1e-4, help='L2 weight of the fields in the refinement (addition)')
+    p.add_argument('--bm_lambda_J', type=float, default=1e-4, help='L2 weight of the couplings in the refinement (addition)')
+    p.add_argument('--pseudocount', type=float, help='pseudocount of the data frequencies (default: 1 / Meff) (addition)')
+    p.add_argument('--seed', type=int, default=0, help='seed of the chains\' counter-based generator (addition)')
+    p.add_argument('--init', choices=('plm', 'zero'), default='plm', help='start from the pseudo-likelihood fit or from zero (addition)')
+    p.add_argument('--num_samples', type=int, help='also draw this many sequences from the refined model (addition)')
+    p.add_argument('--num_sweeps', type=int, default=1000, help='Gibbs sweeps of each of those samples (addition)')
+
+
+BOLTZMANN_OPTIONS = ('iterations', 'num_chains', 'sweeps_per_iteration', 'equilibration_sweeps', 'learning_rate', 'bm_lambda_h',
+                     'bm_lambda_J', 'pseudocount', 'seed', 'init', 'num_samples', 'num_sweeps')
+
+
+def run_boltzmann(instance, prefix, msa_file, output_dir, metadata, biomolecule, opts):
+    """plmdca fit_boltzmann -> the paths written: <output_dir>/<prefix>_boltzmann_<alignment base>.txt (learning curve),
+    <prefix>_boltzmann_params_<alignment base>.npy (the refined x) and, with num_samples, <prefix>_boltzmann_samples_
+    <alignment base>.fa (the sample_sequences format)."""
+    from .dca_utilities import dca_utilities
+    import numpy as np
+    opts = dict(opts or {})
+    dca_utilities.create_directories(output_dir)
+    kw = dict(pseudocount=opts.get('pseudocount'), init=opts.get('init') or 'plm')
+    for key, name in (('iterations', 'iterations'), ('num_chains', 'num_chains'), ('sweeps_per_iteration', 'sweeps_per_iteration'),
+                      ('equilibration_sweeps', 'equilibration_sweeps'), ('learning_rate', 'learning_rate'),
+                      ('bm_lambda_h', 'lambda_h'), ('bm_lambda_J', 'lambda_J'), ('seed', 'seed')):
+        if opts.get(key) is not None:
+            kw[name] = opts[key]
+    fit = instance.fit_boltzmann(**kw)
+    curve = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_boltzmann_', postfix='.txt')
+    dca_utilities.write_boltzmann_history(curve, fit['history'], metadata=metadata)
+    params = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_boltzmann_params_', postfix='.npy')
+    np.save(params, fit['fields_and_couplings'])
+    paths = [curve, params]
+    if opts.get('num_samples'):
+        codes = instance.sample_sequences(int(opts['num_samples']), num_sweeps=opts.get('num_sweeps') or 1000,
+                                          seed=opts.get('seed') or 0, return_codes=True)
+        letters = state_letters(biomolecule)
+        seqs = [''.join(letters[c] for c in row) for row in codes]
+        samples = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_boltzmann_samples_', postfix='.fa')
+        dca_utilities.write_sampled_sequences(samples, seqs, instance.compute_sequence_energies(seqs))
+        paths.append(samples)
+    return tuple(paths)

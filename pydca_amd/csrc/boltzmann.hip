@@ -1,0 +1,342 @@
+// Boltzmann machine learning (bmDCA) of the plm parameter vector x (fields L*q, then the q x q blocks of the pairs i < j in
+// pair order): gradient ascent on the L2-regularised log-likelihood, with the model's one- and two-site frequencies estimated
+// from n persistent Gibbs chains that stay on the device for the whole run (include/dca_hip.h).
+//
+// One iteration: k sweeps of the chains (sample.hip, tag "sample"), then under the tag "bm_stats"
+//   bm_fields_kernel  one workgroup per site: integer counts c_i(a) in LDS, g_i = c_i / n, field update, max |f^_i - g_i|;
+//   bm_pairs_kernel   one workgroup per TB x TB tile of site pairs: each chain's codes of the tile's 2 TB sites are read once
+//                     into registers and counted into an LDS histogram of uint32 (ds_add_u32, exact); the same workgroup then
+//                     reads f^_ij and theta, writes theta', and writes its max |f^_ij - g_ij| and its five Pearson sums to a
+//                     slab of its own;
+//   bm_record_kernel  one workgroup: the slabs and the field maxima reduced in a fixed order, the record of the iteration.
+// No float atomics.  Every sum runs in double in an order fixed by (L, q): thread e of a tile walks the tile's elements
+// e, e + 256, ... in ascending order, the 256 partials meet in a fixed tree; the record kernel does the same over the slabs.
+#include "dca_internal.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr int kBmThreads = 256;
+constexpr int kBmSums = 6;                 // slab: max |d|, sum Cd, sum Cm, sum Cd^2, sum Cm^2, sum Cd Cm
+
+__device__ __forceinline__ size_t pair_index(int L, int i, int j)
+{
+    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
+}
+
+// theta' = theta + eta * ((f - g) - mu * theta), every step in double, rounded once to S
+template <typename S>
+__device__ __forceinline__ void bm_update(S* p, double d, double eta, double mu)
+{
+    const double th = (double)*p;
+    const double r = mu * th;
+    const double s = d - r;
+    *p = (S)(th + eta * s);
+}
+
+// grid L.  g_i(a) = c_i(a) / n; UPDATE: fields updated, epsPart[i] = max_a |f^_i(a) - g_i(a)|
+template <typename S, bool UPDATE>
+__global__ __launch_bounds__(kBmThreads)
+void bm_fields_kernel(const uint8_t* __restrict__ st, int nS, int n, int q, const double* __restrict__ fi, double* __restrict__ gi,
+                      S* __restrict__ x, double eta, double mu, double* __restrict__ epsPart)
+{
+    __shared__ uint32_t hist[32];
+    const int i = blockIdx.x, t = threadIdx.x;
+    if (t < 32) hist[t] = 0u;
+    __syncthreads();
+    const uint8_t* col = st + (size_t)i * nS;
+    for (int c = t; c < n; c += kBmThreads) atomicAdd(&hist[col[c]], 1u);
+    __syncthreads();
+    if (t != 0) return;
+    double m = 0.0;
+    for (int a = 0; a < q; ++a) {
+        const double g = (double)hist[a] / (double)n;
+        gi[(size_t)i * q + a] = g;
+        if (UPDATE) {
+            const double d = fi[(size_t)i * q + a] - g;
+            m = fmax(m, fabs(d));
+            bm_update(x + (size_t)i * q + a, d, eta, mu);
+        }
+    }
+    if (UPDATE) epsPart[i] = m;
+}
+
+// grid (nb, nb), nb = ceil(L / TB); the tiles (I, J) with I <= J hold the pairs i in block I, j in block J, i < j.
+// UPDATE: couplings updated and slab[tile] written (tile = I nb - I (I - 1) / 2 + J - I); otherwise gij = g_ij (pair order).
+template <typename S, int TB, bool UPDATE>
+__global__ __launch_bounds__(kBmThreads)
+void bm_pairs_kernel(const uint8_t* __restrict__ st, int nS, int n, int L, int q, int nb, const double* __restrict__ fi,
+                     const double* __restrict__ fij, const double* __restrict__ gi, S* __restrict__ x, double eta, double mu,
+                     double* __restrict__ slab, double* __restrict__ gij)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char bm_smem[];
+    uint32_t* hist = reinterpret_cast<uint32_t*>(bm_smem);              // [TB * TB][q * q]
+    __shared__ double red[kBmSums][kBmThreads];
+    const int I = blockIdx.y, J = blockIdx.x;
+    if (J < I) return;
+    const int t = threadIdx.x, qq = q * q, i0 = I * TB, j0 = J * TB;
+    const int cells = TB * TB * qq;
+    for (int e = t; e < cells; e += kBmThreads) hist[e] = 0u;
+    __syncthreads();
+    for (int c = t; c < n; c += kBmThreads) {
+        int a[TB], b[TB];
+#pragma unroll
+        for (int u = 0; u < TB; ++u) {
+            a[u] = i0 + u < L ? st[(size_t)(i0 + u) * nS + c] : 0;
+            b[u] = j0 + u < L ? st[(size_t)(j0 + u) * nS + c] : 0;
+        }
+#pragma unroll
+        for (int ii = 0; ii < TB; ++ii)
+#pragma unroll
+            for (int jj = 0; jj < TB; ++jj)
+                if (i0 + ii < j0 + jj && j0 + jj < L) atomicAdd(&hist[(ii * TB + jj) * qq + a[ii] * q + b[jj]], 1u);
+    }
+    __syncthreads();
+    double mx = 0.0, sd = 0.0, sm = 0.0, sdd = 0.0, smm = 0.0, sdm = 0.0;
+    const size_t Lq = (size_t)L * q;
+    for (int e = t; e < cells; e += kBmThreads) {
+        const int p = e / qq, ab = e - p * qq;
+        const int i = i0 + p / TB, j = j0 + p % TB;
+        if (i >= j || j >= L) continue;
+        const double g = (double)hist[e] / (double)n;
+        const size_t off = pair_index(L, i, j) * qq + ab;
+        if (!UPDATE) { gij[off] = g; continue; }
+        const int a = ab / q, b = ab - a * q;
+        const double f = fij[off];
+        const double d = f - g;
+        bm_update(x + Lq + off, d, eta, mu);
+        mx = fmax(mx, fabs(d));
+        const double cd = f - fi[(size_t)i * q + a] * fi[(size_t)j * q + b];
+        const double cm = g - gi[(size_t)i * q + a] * gi[(size_t)j * q + b];
+        sd += cd; sm += cm; sdd += cd * cd; smm += cm * cm; sdm += cd * cm;
+    }
+    if (!UPDATE) return;
+    red[0][t] = mx; red[1][t] = sd; red[2][t] = sm; red[3][t] = sdd; red[4][t] = smm; red[5][t] = sdm;
+    __syncthreads();
+    for (int s = kBmThreads / 2; s > 0; s >>= 1) {
+        if (t < s) {
+            red[0][t] = fmax(red[0][t], red[0][t + s]);
+#pragma unroll
+            for (int k = 1; k < kBmSums; ++k) red[k][t] += red[k][t + s];
+        }
+        __syncthreads();
+    }
+    if (t < kBmSums) slab[((size_t)I * nb - (size_t)I * (I - 1) / 2 + (J - I)) * kBmSums + t] = red[t][0];
+}
+
+// one workgroup: thread t reduces the slabs t, t + 256, ... (and the field maxima likewise) in ascending order, the 256
+// partials meet in a fixed tree; rec = (eps_h, eps_J, pearson) with M = pairs * q^2 values:
+//   cov = Sdm / M - (Sd / M)(Sm / M), vd = Sdd / M - (Sd / M)^2, vm = Smm / M - (Sm / M)^2, pearson = cov / sqrt(vd vm) (0 if vd vm <= 0)
+__global__ __launch_bounds__(kBmThreads)
+void bm_record_kernel(const double* __restrict__ slab, int tiles, const double* __restrict__ epsPart, int L, double M, double* __restrict__ rec)
+{
+    __shared__ double red[kBmSums + 1][kBmThreads];
+    const int t = threadIdx.x;
+    double v[kBmSums + 1] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = t; k < tiles; k += kBmThreads) {
+        v[0] = fmax(v[0], slab[(size_t)k * kBmSums]);
+#pragma unroll
+        for (int s = 1; s < kBmSums; ++s) v[s] += slab[(size_t)k * kBmSums + s];
+    }
+    for (int i = t; i < L; i += kBmThreads) v[kBmSums] = fmax(v[kBmSums], epsPart[i]);
+#pragma unroll
+    for (int s = 0; s <= kBmSums; ++s) red[s][t] = v[s];
+    __syncthreads();
+    for (int s = kBmThreads / 2; s > 0; s >>= 1) {
+        if (t < s) {
+            red[0][t] = fmax(red[0][t], red[0][t + s]);
+#pragma unroll
+            for (int k = 1; k < kBmSums; ++k) red[k][t] += red[k][t + s];
+            red[kBmSums][t] = fmax(red[kBmSums][t], red[kBmSums][t + s]);
+        }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    const double md = red[1][0] / M, mm = red[2][0] / M;
+    const double cov = red[5][0] / M - md * mm;
+    const double vd = red[3][0] / M - md * md, vm = red[4][0] / M - mm * mm;
+    const double vv = vd * vm;
+    rec[0] = red[kBmSums][0];
+    rec[1] = red[0][0];
+    rec[2] = vv > 0.0 ? cov / sqrt(vv) : 0.0;
+}
+
+}  // namespace
+
+struct BmRun {
+    int L = 0, q = 0, dtype = DCA_F32;
+    int k = 1, E = 0;
+    uint64_t seed = 0;
+    double eta_h = 0, eta_J = 0, mu_h = 0, mu_J = 0;
+    long long t = 0;                       // iterations since begin
+    DcaChains ch;
+    double *dFi = nullptr, *dFij = nullptr, *dGi = nullptr, *dEps = nullptr, *dSlab = nullptr, *dRec = nullptr;
+    int tb = 0, nb = 0, tiles = 0, recCap = 0;
+    ~BmRun()
+    {
+        dca_chains_free(&ch);
+        dca_dev_free(dFi); dca_dev_free(dFij); dca_dev_free(dGi); dca_dev_free(dEps); dca_dev_free(dSlab); dca_dev_free(dRec);
+    }
+};
+
+namespace {
+
+// site-pair tile edge: the tile's histogram (TB^2 q^2 uint32) stays within 64 KiB
+int bm_tile(int q) { return q <= 8 ? 16 : q <= 24 ? 4 : 2; }
+
+template <typename S, int TB, bool UPDATE>
+hipError_t launch_pairs_tb(dca_ctx* ctx, BmRun* r, S* x, double* gij)
+{
+    auto kern = bm_pairs_kernel<S, TB, UPDATE>;
+    const size_t lds = (size_t)TB * TB * r->q * r->q * sizeof(uint32_t);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(r->nb, r->nb), dim3(kBmThreads), lds, ctx->stream, r->ch.dState, r->ch.nS, r->ch.n, r->L, r->q, r->nb,
+                       r->dFi, r->dFij, r->dGi, x, r->eta_J, r->mu_J, r->dSlab, gij);
+    return hipGetLastError();
+}
+
+template <typename S, bool UPDATE>
+hipError_t launch_pairs(dca_ctx* ctx, BmRun* r, S* x, double* gij)
+{
+    switch (r->tb) {
+    case 16: return launch_pairs_tb<S, 16, UPDATE>(ctx, r, x, gij);
+    case 4: return launch_pairs_tb<S, 4, UPDATE>(ctx, r, x, gij);
+    default: return launch_pairs_tb<S, 2, UPDATE>(ctx, r, x, gij);
+    }
+}
+
+// the statistics of the current chains; UPDATE: with the update of x and the record written to dRec[slot]
+template <typename S, bool UPDATE>
+hipError_t bm_stats(dca_ctx* ctx, BmRun* r, S* x, int slot, double* gij)
+{
+    ScopedKernelClock kc(ctx, "bm_stats");
+    hipLaunchKernelGGL((bm_fields_kernel<S, UPDATE>), dim3(r->L), dim3(kBmThreads), 0, ctx->stream, r->ch.dState, r->ch.nS, r->ch.n, r->q,
+                       r->dFi, r->dGi, x, r->eta_h, r->mu_h, r->dEps);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = launch_pairs<S, UPDATE>(ctx, r, x, gij);
+    if (e == hipSuccess && UPDATE) {
+        const double M = (double)((size_t)r->L * (r->L - 1) / 2) * (double)(r->q * r->q);
+        hipLaunchKernelGGL(bm_record_kernel, dim3(1), dim3(kBmThreads), 0, ctx->stream, r->dSlab, r->tiles, r->dEps, r->L, M,
+                           r->dRec + (size_t)3 * slot);
+        e = hipGetLastError();
+    }
+    return e;
+}
+
+bool finite_nonneg(double v) { return v >= 0.0 && std::isfinite(v); }
+
+}  // namespace
+
+void dca_bm_free(dca_ctx* ctx)
+{
+    if (!ctx->bm) return;
+    if (ctx->stream) hipStreamSynchronize(ctx->stream);
+    delete ctx->bm;
+    ctx->bm = nullptr;
+}
+
+int dca_bm_begin_impl(dca_ctx* ctx, void* dx, int dtype, const dca_bm_args* a)
+{
+    dca_bm_free(ctx);
+    const int L = ctx->L, q = ctx->q;
+    if (a->chains < 1 || a->sweeps < 1 || a->equilibration_sweeps < 0 || !finite_nonneg(a->eta_h) || !finite_nonneg(a->eta_J) ||
+        !finite_nonneg(a->mu_h) || !finite_nonneg(a->mu_J) || !(a->pseudocount >= 0.0 && a->pseudocount < 1.0)) {
+        dca_set_error("dca_plm_bm_begin: bad arguments (chains %d, sweeps %d, equilibration %d, eta %g / %g, mu %g / %g, pseudocount %g)",
+                      a->chains, a->sweeps, a->equilibration_sweeps, a->eta_h, a->eta_J, a->mu_h, a->mu_J, a->pseudocount);
+        return DCA_ERR_ARG;
+    }
+    if (a->initial)
+        for (size_t k = 0; k < (size_t)a->chains * L; ++k)
+            if (a->initial[k] >= q) {
+                dca_set_error("dca_plm_bm_begin: initial code %d >= q at element %zu", (int)a->initial[k], k);
+                return DCA_ERR_ARG;
+            }
+    BmRun* r = new BmRun();
+    r->L = L; r->q = q; r->dtype = dtype;
+    r->k = a->sweeps; r->E = a->equilibration_sweeps; r->seed = a->seed;
+    r->eta_h = a->eta_h; r->eta_J = a->eta_J; r->mu_h = a->mu_h; r->mu_J = a->mu_J;
+    r->tb = bm_tile(q);
+    r->nb = ceil_div(L, r->tb);
+    r->tiles = r->nb * (r->nb + 1) / 2;
+    const size_t Lq = (size_t)L * q, pairs = (size_t)L * (L - 1) / 2;
+    auto fail = [&](int rc) { delete r; return rc; };
+    if (dca_dev_malloc(reinterpret_cast<void**>(&r->dFi), Lq * sizeof(double), false) != hipSuccess ||
+        dca_dev_malloc(reinterpret_cast<void**>(&r->dFij), pairs * q * q * sizeof(double), false) != hipSuccess ||
+        dca_dev_malloc(reinterpret_cast<void**>(&r->dGi), Lq * sizeof(double)) != hipSuccess ||
+        dca_dev_malloc(reinterpret_cast<void**>(&r->dEps), (size_t)L * sizeof(double)) != hipSuccess ||
+        dca_dev_malloc(reinterpret_cast<void**>(&r->dSlab), (size_t)r->tiles * kBmSums * sizeof(double)) != hipSuccess) {
+        dca_set_error("dca_plm_bm_begin: out of device memory");
+        return fail(DCA_ERR_NOMEM);
+    }
+    // data statistics from the mf engine's weighted counts: a private engine, so the context's own mf state stays as it is
+    {
+        MfEngine* m = dca_make_mf_engine(ctx);
+        const int rc = dca_mf_engine_bm_freqs(m, a->pseudocount, r->dFi, r->dFij);
+        dca_free_mf_engine(m);
+        if (rc != DCA_OK) return fail(rc);
+    }
+    int rc = dca_chains_start(ctx, &r->ch, a->chains, L, q, a->seed, 0, a->initial);
+    if (rc == DCA_OK) rc = dca_chains_sweeps(ctx, r->ch, dx, 0, dtype, nullptr, q, 0, r->E, r->seed, 0, 0, 1.0);
+    if (rc == DCA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { dca_set_error("dca_plm_bm_begin: stream failed"); rc = DCA_ERR_HIP; }
+    if (rc != DCA_OK) return fail(rc);
+    ctx->bm = r;
+    return DCA_OK;
+}
+
+int dca_bm_iterate_impl(dca_ctx* ctx, void* dx, int iterations, dca_bm_record* records_out)
+{
+    BmRun* r = ctx->bm;
+    if (!r) { dca_set_error("dca_plm_bm_begin first"); return DCA_ERR_STATE; }
+    if (iterations < 0) { dca_set_error("dca_plm_bm_iterate: iterations %d < 0", iterations); return DCA_ERR_ARG; }
+    if (iterations == 0) return DCA_OK;
+    if (iterations > r->recCap) {
+        dca_dev_free(r->dRec); r->dRec = nullptr; r->recCap = 0;
+        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&r->dRec), (size_t)iterations * 3 * sizeof(double)));
+        r->recCap = iterations;
+    }
+    for (int it = 0; it < iterations; ++it) {
+        const uint64_t first = (uint64_t)r->E + (uint64_t)r->t * (uint64_t)r->k;
+        DCA_TRY(dca_chains_sweeps(ctx, r->ch, dx, 0, r->dtype, nullptr, r->q, 0, r->k, r->seed, 0, first, 1.0));
+        const hipError_t e = r->dtype == DCA_F32 ? bm_stats<float, true>(ctx, r, static_cast<float*>(dx), it, nullptr)
+                                                 : bm_stats<double, true>(ctx, r, static_cast<double*>(dx), it, nullptr);
+        if (e != hipSuccess) { dca_set_error("dca_plm_bm_iterate: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+        ++r->t;
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (records_out) HIP_TRY(hipMemcpy(records_out, r->dRec, (size_t)iterations * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    return DCA_OK;
+}
+
+int dca_bm_freqs_impl(dca_ctx* ctx, int which, double* fi_out, double* fij_out)
+{
+    BmRun* r = ctx->bm;
+    if (which != 0 && which != 1) { dca_set_error("dca_plm_bm_freqs: which must be 0 or 1"); return DCA_ERR_ARG; }
+    if (!r) { dca_set_error("dca_plm_bm_begin first"); return DCA_ERR_STATE; }
+    const size_t Lq = (size_t)r->L * r->q, nij = (size_t)r->L * (r->L - 1) / 2 * r->q * r->q;
+    if (which == 0) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (fi_out) HIP_TRY(hipMemcpy(fi_out, r->dFi, Lq * sizeof(double), hipMemcpyDeviceToHost));
+        if (fij_out) HIP_TRY(hipMemcpy(fij_out, r->dFij, nij * sizeof(double), hipMemcpyDeviceToHost));
+        return DCA_OK;
+    }
+    if (r->t == 0) { dca_set_error("dca_plm_bm_freqs: no iteration has run yet"); return DCA_ERR_STATE; }
+    // the chains are those of the last iteration's statistics (its sweeps came before them): count them again, x untouched
+    double* dG = nullptr;
+    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dG), std::max<size_t>(nij, 1) * sizeof(double), false));
+    hipError_t e = r->dtype == DCA_F32 ? bm_stats<float, false>(ctx, r, nullptr, 0, dG) : bm_stats<double, false>(ctx, r, nullptr, 0, dG);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e == hipSuccess && fi_out) e = hipMemcpy(fi_out, r->dGi, Lq * sizeof(double), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && fij_out) e = hipMemcpy(fij_out, dG, nij * sizeof(double), hipMemcpyDeviceToHost);
+    dca_dev_free(dG);
+    if (e != hipSuccess) { dca_set_error("dca_plm_bm_freqs: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    return DCA_OK;
+}
+
+int dca_bm_chains_impl(dca_ctx* ctx, uint8_t* out)
+{
+    if (!ctx->bm) { dca_set_error("dca_plm_bm_begin first"); return DCA_ERR_STATE; }
+    if (!out) { dca_set_error("dca_plm_bm_chains: out is NULL"); return DCA_ERR_ARG; }
+    return dca_chains_read(ctx, ctx->bm->ch, out);
+}

@@ -231,6 +231,7 @@ int dca_create(dca_ctx** out, int device, int precision)
 
 static void free_msa(dca_ctx* ctx)
 {
+    dca_bm_free(ctx);
     delete ctx->plm; ctx->plm = nullptr;
     if (ctx->mf) { dca_free_mf_engine(ctx->mf); ctx->mf = nullptr; }
     dca_dev_free(ctx->dX); ctx->dX = nullptr;
@@ -341,6 +342,7 @@ int dca_set_msa(dca_ctx* ctx, const uint8_t* X, int N, int L, int q)
 // is re-weighted must not fall back to unreduced local sums.  The plmDCA engine has to be configured again.
 static void weights_changed(dca_ctx* ctx)
 {
+    dca_bm_free(ctx);          // a Boltzmann-learning run fits the old weights' statistics: it ends
     if (ctx->plm) ctx->plm->weights_changed();
     if (ctx->mf) dca_mf_engine_invalidate(ctx->mf);
 }
@@ -445,6 +447,7 @@ int dca_plm_configure(dca_ctx* ctx, double lambda_h, double lambda_J, int carry_
     CHECK_CTX(ctx);
     DCA_TRY(need_plm(ctx));
     if (carry_mode < 0 || carry_mode > 2) return DCA_ERR_ARG;
+    dca_bm_free(ctx);
     return ctx->plm->configure(lambda_h, lambda_J, carry_mode, chunk, warmup, halo, add_regulariser);
 }
 int dca_plm_configure_strips(dca_ctx* ctx, double lambda_h, double lambda_J, int carry_mode, int chunk, int warmup)
@@ -452,6 +455,7 @@ int dca_plm_configure_strips(dca_ctx* ctx, double lambda_h, double lambda_J, int
     CHECK_CTX(ctx);
     DCA_TRY(need_plm(ctx));
     if (carry_mode < 0 || carry_mode > 2) return DCA_ERR_ARG;
+    dca_bm_free(ctx);
     return ctx->plm->configure_strips(lambda_h, lambda_J, carry_mode, chunk, warmup);
 }
 int dca_plm_release(dca_ctx* ctx)
@@ -460,6 +464,7 @@ int dca_plm_release(dca_ctx* ctx)
     if (!ctx->plm) return DCA_OK;
     // the engine's kernels may still be running on the context's stream
     if (hipStreamSynchronize(ctx->stream) != hipSuccess) { dca_set_error("dca_plm_release: stream synchronisation failed"); return DCA_ERR_HIP; }
+    dca_bm_free(ctx);
     delete ctx->plm; ctx->plm = nullptr;
     return DCA_OK;
 }
@@ -484,7 +489,13 @@ int dca_plm_set_reduce_hook(dca_ctx* ctx, dca_reduce_hook hook, void* user)
     if (hook && ctx->plm->native_mode == 1) ctx->plm->native_mode = 0;      // the hook replaces the native all-reduce
     return DCA_OK;
 }
-int dca_plm_lbfgs_begin(dca_ctx* ctx, int max_iterations, int verbose) { CHECK_CTX(ctx); DCA_TRY(need_plm(ctx)); return ctx->plm->lbfgs_begin(max_iterations, verbose); }
+int dca_plm_lbfgs_begin(dca_ctx* ctx, int max_iterations, int verbose)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    dca_bm_free(ctx);
+    return ctx->plm->lbfgs_begin(max_iterations, verbose);
+}
 int dca_plm_lbfgs_iterate(dca_ctx* ctx, int iterations, dca_plm_stats* st) { CHECK_CTX(ctx); DCA_TRY(need_plm(ctx)); return ctx->plm->lbfgs_iterate(iterations, st); }
 int dca_plm_lbfgs_end(dca_ctx* ctx) { CHECK_CTX(ctx); if (ctx->plm) ctx->plm->lbfgs_end(); return DCA_OK; }
 int dca_plm_scores(dca_ctx* ctx, int apc, double* out) { CHECK_CTX(ctx); DCA_TRY(need_plm(ctx)); return ctx->plm->scores(apc, out); }
@@ -509,6 +520,28 @@ int dca_plm_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t firs
     DCA_TRY(need_plm(ctx));
     return ctx->plm->sample(n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
 }
+// Boltzmann learning (boltzmann.hip) on the plm engine's x
+int dca_plm_bm_begin(dca_ctx* ctx, const dca_bm_args* args)
+{
+    CHECK_CTX(ctx);
+    if (!args) { dca_set_error("dca_plm_bm_begin: args is NULL"); return DCA_ERR_ARG; }
+    DCA_TRY(need_plm(ctx));
+    void* dx = nullptr;
+    DCA_TRY(ctx->plm->bm_source(&dx));
+    return dca_bm_begin_impl(ctx, dx, ctx->precision == DCA_F64 ? DCA_F64 : DCA_F32, args);
+}
+int dca_plm_bm_iterate(dca_ctx* ctx, int iterations, dca_bm_record* records_out)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->bm || !ctx->plm) { dca_set_error("dca_plm_bm_begin first"); return DCA_ERR_STATE; }
+    void* dx = nullptr;
+    DCA_TRY(ctx->plm->bm_source(&dx));
+    return dca_bm_iterate_impl(ctx, dx, iterations, records_out);
+}
+int dca_plm_bm_freqs(dca_ctx* ctx, int which, double* fi_out, double* fij_out) { CHECK_CTX(ctx); return dca_bm_freqs_impl(ctx, which, fi_out, fij_out); }
+int dca_plm_bm_chains(dca_ctx* ctx, uint8_t* out) { CHECK_CTX(ctx); return dca_bm_chains_impl(ctx, out); }
+int dca_plm_bm_end(dca_ctx* ctx) { CHECK_CTX(ctx); dca_bm_free(ctx); return DCA_OK; }
+
 int dca_plm_di_scores(dca_ctx* ctx, const double* reg_fi, int apc, double* out)
 {
     CHECK_CTX(ctx);

@@ -53,6 +53,7 @@ struct KernelClock {
 
 struct PlmEngineBase;
 struct MfEngine;
+struct BmRun;
 
 #define DCA_SIDE_DEPTHS 3
 
@@ -83,6 +84,7 @@ struct dca_ctx {
 
     PlmEngineBase* plm = nullptr;
     MfEngine* mf = nullptr;
+    BmRun* bm = nullptr;          // Boltzmann-learning run in progress (boltzmann.hip)
 
     // native communicator (comm_rccl.cpp): an RCCL communicator whose collectives run on `stream`
     void* comm = nullptr;
@@ -170,6 +172,9 @@ struct PlmEngineBase {
     virtual int mutation_scan(const uint8_t* wildtype, double* out) = 0;
     virtual int sample(int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                        const uint8_t* initial, uint8_t* out) = 0;                  // sample.hip on the current x
+    // the device x a Boltzmann-learning run updates in place; DCA_ERR_STATE (with the reason) unconfigured, during an L-BFGS
+    // run, under column strips, vector sharding, a reduce / comm hook or a native-comm mode
+    virtual int bm_source(void** dx) = 0;
     virtual int set_vector_sharding(int rank, int world, dca_comm_hook hook, void* user) = 0;
     dca_reduce_hook hook = nullptr;
     void* hook_user = nullptr;
@@ -204,6 +209,27 @@ int dca_potts_sample(dca_ctx* ctx, const void* src, int src_kind, int dtype, con
                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                      const uint8_t* initial /* host n*L or NULL */, uint8_t* out /* host n*L */);
 
+// Device-resident chains of the sampler: site-major codes st[s * nS + c], nS = n rounded up to 64 (the chains past n are
+// swept too and never read).  dca_chains_start: tag-1 random starts of chains first_chain + c, or the host rows `initial`
+// (n x L codes < q, checked by the caller).  dca_chains_sweeps: `sweeps` launches numbered first_sweep.., one per sweep, under
+// the tag "sample".  dca_chains_read: the n x L rows to the host (synchronises).
+struct DcaChains { int n = 0, L = 0, nS = 0; uint8_t* dState = nullptr; };
+int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial);
+int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const void* src, int src_kind, int dtype, const double* dMfFields, int q, int ld,
+                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta);
+int dca_chains_read(dca_ctx* ctx, const DcaChains& ch, uint8_t* out);
+void dca_chains_free(DcaChains* ch);
+
+// ---- boltzmann.hip : Boltzmann machine learning of the plm vector (dca_plm_bm_*).  The run lives in ctx->bm; dca_bm_free ends
+// it (alignment, weights, configure, L-BFGS begin, engine release, destroy).  x: the plm engine's device vector (PlmEngineBase::
+// bm_source), looked up again on every call.
+struct BmRun;
+int dca_bm_begin_impl(dca_ctx* ctx, void* dx, int dtype, const dca_bm_args* args);
+int dca_bm_iterate_impl(dca_ctx* ctx, void* dx, int iterations, dca_bm_record* records_out);
+int dca_bm_freqs_impl(dca_ctx* ctx, int which, double* fi_out, double* fij_out);
+int dca_bm_chains_impl(dca_ctx* ctx, uint8_t* out);
+void dca_bm_free(dca_ctx* ctx);
+
 int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, const double* reg_fi, int L, int q,
                             double* fields_out, double* di_out, const double* fields_in = nullptr);
 
@@ -225,6 +251,9 @@ void dca_mf_engine_invalidate(MfEngine*);      // weights changed: counts, frequ
 int dca_mf_engine_pair_couplings(MfEngine*, const int* pairs, int npairs, int shift, double* out);
 int dca_mf_engine_energies(MfEngine*, const uint8_t* X, int n, double* out);
 int dca_mf_engine_mutation_scan(MfEngine*, const uint8_t* wildtype, double* out);
+// data statistics of a Boltzmann-learning run from this engine's weighted counts (dca_plm_bm_begin): device outputs
+// fi (L*q) = (1 - lambda) * f_i + lambda / q and fij (pairs*q*q, pair order, gap included) = (1 - lambda) * f_ij + lambda / q^2
+int dca_mf_engine_bm_freqs(MfEngine*, double lambda, double* dFi, double* dFij);
 int dca_mf_engine_sample(MfEngine*, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                          const uint8_t* initial, uint8_t* out);
 

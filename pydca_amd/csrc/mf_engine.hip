@@ -228,6 +228,27 @@ __global__ void mf_fij_export_kernel(const double* __restrict__ Craw, double* __
     }
 }
 
+// data statistics of a Boltzmann-learning run (dca_plm_bm_begin), every pair block q x q with the gap state:
+// fij[p][a][b] = (1 - lambda) * (Craw[(i,a)][(j,b)] / meff) + lambda / q^2, each operation rounded in double
+__global__ void mf_bm_fij_kernel(const double* __restrict__ Craw, double* __restrict__ fij, int L, int q, int ldc, double meff, double om,
+                                 double lq2)
+{
+    const int i = blockIdx.y, j = blockIdx.x;
+    if (j <= i) return;
+    const size_t p = pair_index(L, i, j);
+    for (int e = threadIdx.x; e < q * q; e += blockDim.x) {
+        const int a = e / q, b = e % q;
+        fij[p * q * q + e] = om * (Craw[(size_t)(i * q + a) * ldc + (size_t)j * q + b] / meff) + lq2;
+    }
+}
+
+// ... and fi[c] = (1 - lambda) * f_i + lambda / q from the single-site frequencies of mf_fi_kernel
+__global__ void mf_bm_fi_kernel(const double* __restrict__ f, double* __restrict__ fi, int Lq, double om, double lq)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < Lq) fi[c] = om * f[c] + lq;
+}
+
 // correlation matrix from raw counts: regularisation (msa_numerics.py:92-125, :231-267)
 // fused with construct_corr_mat (:270-318).
 // Rows/cols >= n (padding up to np) form an identity block.
@@ -423,6 +444,17 @@ int dca_mf_engine_pair_freqs(MfEngine* m, double* fij_out)
     if (e == hipSuccess) e = hipMemcpy(fij_out, dOut, total * sizeof(double), hipMemcpyDeviceToHost);
     dca_dev_free(dOut);
     if (e != hipSuccess) { dca_set_error("pair freqs: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    return DCA_OK;
+}
+
+int dca_mf_engine_bm_freqs(MfEngine* m, double lambda, double* dFi, double* dFij)
+{
+    DCA_TRY(mf_counts(m));
+    const double om = 1.0 - lambda, lq = lambda / (double)m->q, lq2 = lambda / (double)(m->q * m->q);
+    hipLaunchKernelGGL(mf_bm_fi_kernel, dim3(ceil_div(m->Lq, 256)), dim3(256), 0, m->ctx->stream, m->dFi, dFi, m->Lq, om, lq);
+    hipLaunchKernelGGL(mf_bm_fij_kernel, dim3(m->L, m->L), dim3(128), 0, m->ctx->stream, m->dCraw, dFij, m->L, m->q, m->Lq, m->meff, om, lq2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(m->ctx->stream));
     return DCA_OK;
 }
 

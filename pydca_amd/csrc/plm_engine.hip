@@ -2229,6 +2229,18 @@ struct PlmEngine : PlmEngineBase {
         if (rc != DCA_OK) return rc;
         return rc2;
     }
+    int bm_source(void** x) override
+    {
+        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
+        if (o.begun && !o.finished) { dca_set_error("an L-BFGS run is in progress: dca_plm_lbfgs_end first"); return DCA_ERR_STATE; }
+        if (strips || native_mode == 4) { dca_set_error("Boltzmann learning runs on one GPU: configured for column strips"); return DCA_ERR_STATE; }
+        if (comm || hook || native_mode != 0) {
+            dca_set_error("Boltzmann learning runs on one GPU: vector sharding, a reduce / comm hook or a native-comm mode is set");
+            return DCA_ERR_STATE;
+        }
+        *x = dx;
+        return DCA_OK;
+    }
     int set_vector_sharding(int rank, int world, dca_comm_hook h, void* user) override
     {
         if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }

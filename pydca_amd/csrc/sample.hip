@@ -17,7 +17,9 @@
 // LDS in double-buffered chunks of CJ blocks (CJ a multiple of 4), each block stored transposed, T[b][a] = J(a, b) with rows
 // padded to QM values, so that a lane reads J(., s_j) as QM contiguous values; the next chunk's loads are in flight in
 // registers while the current one is summed.  Chain codes live in LDS (64 x L bytes) when L <= kSResidentL, otherwise in
-// the global site-major state buffer.  One launch is one sweep; no atomics, no inter-workgroup communication.
+// the global site-major state buffer.  One launch is one sweep; no atomics, no inter-workgroup communication.  The state
+// buffer lives in a DcaChains (dca_internal.h): dca_potts_sample makes one per call, a Boltzmann-learning run (boltzmann.hip)
+// keeps its own on the device for the whole run.
 #include "dca_internal.h"
 
 #include <cmath>
@@ -277,43 +279,80 @@ hipError_t dispatch_sweep(dca_ctx* ctx, const SampleGeom& sg, const S* src, int 
     }
 }
 
-template <typename S>
-int sample_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q, int ld, int n, int sweeps, uint64_t seed,
-             uint64_t first_chain, uint64_t first_sweep, double beta, const uint8_t* initial, uint8_t* out)
+}  // namespace
+
+// ---- device-resident chains (dca_internal.h): the sampler's state between calls
+int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial)
 {
-    const SampleGeom sg = sample_geometry(L, q, sizeof(S));
-    const int nS = (int)round_up((size_t)n, kSChains);
-    const size_t sites = (size_t)L * nS;
-    uint8_t *dRows = nullptr, *dState = nullptr;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)n * L, false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dState), sites, false);
+    dca_chains_free(ch);
+    ch->n = n; ch->L = L;
+    ch->nS = (int)round_up((size_t)n, kSChains);
+    const size_t sites = (size_t)L * ch->nS;
+    uint8_t* dRows = nullptr;
+    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&ch->dState), sites, false);
     if (e == hipSuccess) {
         if (initial) {
-            e = hipMemcpyAsync(dRows, initial, (size_t)n * L, hipMemcpyHostToDevice, ctx->stream);
+            e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)n * L, false);
+            if (e == hipSuccess) e = hipMemcpyAsync(dRows, initial, (size_t)n * L, hipMemcpyHostToDevice, ctx->stream);
             if (e == hipSuccess)
-                hipLaunchKernelGGL(rows_to_sites_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, dRows, n, L, nS, dState);
+                hipLaunchKernelGGL(rows_to_sites_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, dRows, n, L, ch->nS,
+                                   ch->dState);
         } else {
-            hipLaunchKernelGGL(initial_state_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, n, L, q, nS, seed,
-                               first_chain, dState);
+            hipLaunchKernelGGL(initial_state_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, n, L, q, ch->nS, seed,
+                               first_chain, ch->dState);
         }
         if (e == hipSuccess) e = hipGetLastError();
     }
-    for (int t = 0; t < sweeps && e == hipSuccess; ++t) {       // one launch per sweep
-        ScopedKernelClock kc(ctx, "sample");
-        e = dispatch_sweep<S>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, first_sweep + (uint64_t)t, beta);
+    dca_dev_free(dRows);
+    if (e != hipSuccess) { dca_chains_free(ch); dca_set_error("sample: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    return DCA_OK;
+}
+
+int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const void* src, int src_kind, int dtype, const double* dMfFields, int q, int ld,
+                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta)
+{
+    const int L = ch.L;
+    hipError_t e = hipSuccess;
+    if (dtype == DCA_F32) {
+        const SampleGeom sg = sample_geometry(L, q, sizeof(float));
+        for (int t = 0; t < sweeps && e == hipSuccess; ++t) {       // one launch per sweep
+            ScopedKernelClock kc(ctx, "sample");
+            e = dispatch_sweep<float>(ctx, sg, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, ch.dState, ch.nS, seed,
+                                      first_chain, first_sweep + (uint64_t)t, beta);
+        }
+    } else {
+        const SampleGeom sg = sample_geometry(L, q, sizeof(double));
+        for (int t = 0; t < sweeps && e == hipSuccess; ++t) {
+            ScopedKernelClock kc(ctx, "sample");
+            e = dispatch_sweep<double>(ctx, sg, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, ch.dState, ch.nS, seed,
+                                       first_chain, first_sweep + (uint64_t)t, beta);
+        }
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(sites_to_rows_kernel, dim3((unsigned)(((size_t)n * L + 255) / 256)), dim3(256), 0, ctx->stream, dState, n, L, nS, dRows);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dRows, (size_t)n * L, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dca_dev_free(dRows); dca_dev_free(dState);
     if (e != hipSuccess) { dca_set_error("sample: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
     return DCA_OK;
 }
 
-}  // namespace
+int dca_chains_read(dca_ctx* ctx, const DcaChains& ch, uint8_t* out)
+{
+    const size_t total = (size_t)ch.n * ch.L;
+    uint8_t* dRows = nullptr;
+    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), total, false);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(sites_to_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ch.dState, ch.n, ch.L, ch.nS, dRows);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, dRows, total, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    dca_dev_free(dRows);
+    if (e != hipSuccess) { dca_set_error("sample: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    return DCA_OK;
+}
+
+void dca_chains_free(DcaChains* ch)
+{
+    dca_dev_free(ch->dState);
+    *ch = DcaChains();
+}
 
 int dca_potts_sample(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld, int n,
                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta, const uint8_t* initial,
@@ -327,11 +366,12 @@ int dca_potts_sample(dca_ctx* ctx, const void* src, int src_kind, int dtype, con
     if (initial)
         for (size_t k = 0; k < (size_t)n * L; ++k)
             if (initial[k] >= q) { dca_set_error("sample: initial code %d >= q at element %zu", (int)initial[k], k); return DCA_ERR_ARG; }
-    if (dtype == DCA_F32)
-        return sample_t(ctx, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, n, sweeps, seed, first_chain, first_sweep, beta,
-                        initial, out);
-    return sample_t(ctx, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, n, sweeps, seed, first_chain, first_sweep, beta,
-                    initial, out);
+    DcaChains ch;
+    int rc = dca_chains_start(ctx, &ch, n, L, q, seed, first_chain, initial);
+    if (rc == DCA_OK) rc = dca_chains_sweeps(ctx, ch, src, src_kind, dtype, dMfFields, q, ld, sweeps, seed, first_chain, first_sweep, beta);
+    if (rc == DCA_OK) rc = dca_chains_read(ctx, ch, out);
+    dca_chains_free(&ch);
+    return rc;
 }
 
 int dca_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])

@@ -114,6 +114,16 @@ def write_sampled_sequences(file_name, sequences, energies):
     _stream(file_name, [], rows, 'sampled sequences')
 
 
+def write_boltzmann_history(file_name, history, metadata=None):
+    """Learning curve of PlmDCA.fit_boltzmann: one row per iteration t (0-based) with eps_h, eps_J and pearson, each
+    written with %.17g (no reference counterpart)."""
+    header = [_RULE] + list(metadata or []) + [
+        '# Columns: iteration t (0-based), eps_h = max |f_i - g_i|, eps_J = max |f_ij - g_ij| and the Pearson correlation',
+        '# of the connected correlations of the data (f) and of the model chains (g), measured before the update of t', _RULE]
+    rows = ('{} {} {} {}'.format(t, *('%.17g' % float(v) for v in rec)) for t, rec in enumerate(history))
+    _stream(file_name, header, rows, 'Boltzmann learning curve')
+
+
 def _csv(prefix_values, values):
     # '{}'.format(v), not str(v): numpy scalars of the two print differently (a float32 is widened by format)
     return ','.join('{}'.format(v) for v in list(prefix_values) + list(values))

@@ -25,6 +25,33 @@ def _ranked(scores, L, ctx=None):
     return _ranking.ranked(scores, L, ctx.scores_order() if ctx is not None else None)
 
 
+def _boltzmann_options(iterations, num_chains, sweeps_per_iteration, equilibration_sweeps, learning_rate, lambda_h, lambda_J,
+                       pseudocount, init):
+    """Checks the arguments of PlmDCA.fit_boltzmann (host only) -> dict of the checked values."""
+    def count(name, v, low):
+        if isinstance(v, bool) or int(v) != v or int(v) < low:
+            raise PlmDCAException('{} must be an integer >= {}, not {!r}'.format(name, low, v))
+        return int(v)
+
+    def rate(name, v):
+        v = float(v)
+        if not (0.0 <= v < float('inf')):
+            raise PlmDCAException('{} must be finite and >= 0, not {!r}'.format(name, v))
+        return v
+    opts = dict(iterations=count('iterations', iterations, 1), num_chains=count('num_chains', num_chains, 1),
+                sweeps_per_iteration=count('sweeps_per_iteration', sweeps_per_iteration, 1),
+                equilibration_sweeps=count('equilibration_sweeps', equilibration_sweeps, 0),
+                learning_rate=rate('learning_rate', learning_rate), lambda_h=rate('lambda_h', lambda_h),
+                lambda_J=rate('lambda_J', lambda_J), pseudocount=None, init=init)
+    if pseudocount is not None:
+        opts['pseudocount'] = float(pseudocount)
+        if not (0.0 <= opts['pseudocount'] < 1.0):
+            raise PlmDCAException('pseudocount must lie in [0, 1), not {!r}'.format(pseudocount))
+    if init not in ('plm', 'zero'):
+        raise PlmDCAException("init must be 'plm' or 'zero', not {!r}".format(init))
+    return opts
+
+
 class PlmDCA:
     """plmdca.py:25-104.  Extra keyword arguments (not in the reference): device,
     precision (32: float storage as the reference; 64: float64 checking mode) and
@@ -328,6 +355,55 @@ class PlmDCA:
             return codes
         letters = _potts.state_letters(self.__biomolecule_int)
         return [''.join(letters[c] for c in row) for row in codes]
+
+    def _unfitted_context(self):
+        """Alignment, weights and configuration as _run_backend sets them up, without the L-BFGS run."""
+        X, _raw = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)
+        ctx = _lib.Context(self.__device, self.__precision)
+        ctx.set_msa(X, self.__num_site_states)
+        ctx.compute_weights(self.__seqid, self.__precision)
+        ctx.plm_configure(self.__lambda_h, self.__lambda_J, self.__carry)
+        return ctx
+
+    def fit_boltzmann(self, iterations=500, num_chains=1000, sweeps_per_iteration=10, equilibration_sweeps=100,
+                      learning_rate=0.05, lambda_h=1e-4, lambda_J=1e-4, pseudocount=None, seed=0, init='plm'):
+        """Refines the model by Boltzmann machine learning (bmDCA): gradient ascent on the
+        L2-regularised log-likelihood, the model's one- and two-site frequencies estimated from num_chains persistent
+        Gibbs chains on the GPU (sweeps_per_iteration sweeps per iteration after equilibration_sweeps at the start).
+        learning_rate is the step of fields and couplings, lambda_h / lambda_J their L2 weights; pseudocount
+        regularises the data frequencies (None: 1 / Meff).  init='plm' starts from the model this instance holds (its
+        pseudo-likelihood fit, fitted here if there is none; after an earlier fit_boltzmann, that refined model), 'zero'
+        from all-zero parameters.  Afterwards compute_sequence_energies,
+        compute_single_mutant_effects and sample_sequences use the refined model; compute_sorted_FN* / DI* and
+        compute_params fit the pseudo-likelihood model again, as they always do.
+        -> {'history': float64[iterations, 3] of (eps_h, eps_J, pearson), 'fields_and_couplings': x}"""
+        if self.__devices and len(self.__devices) > 1:
+            logger.error('\n\tBoltzmann learning runs on one GPU; devices={}'.format(self.__devices))
+            raise PlmDCAException('fit_boltzmann runs on one GPU, not on devices {}'.format(self.__devices))
+        opts = _boltzmann_options(iterations, num_chains, sweeps_per_iteration, equilibration_sweeps, learning_rate, lambda_h,
+                                  lambda_J, pseudocount, init)
+        if opts['init'] == 'plm':
+            ctx = self._fitted_context()
+        else:
+            ctx = self.__ctx if self.__ctx is not None else self._unfitted_context()
+        self.__ctx = ctx
+        ctx.plm_lbfgs_end()                      # a pseudo-likelihood run stopped at its iteration cap stays open until now
+        dt = np.float64 if self.__precision == _lib.DCA_F64 else np.float32
+        if opts['init'] == 'zero':
+            ctx.plm_set_x(np.zeros(ctx.num_params(), dtype=dt))
+        lam = 1.0 / ctx.meff() if opts['pseudocount'] is None else opts['pseudocount']
+        logger.info('\n\tBoltzmann learning: {} iterations, {} chains, {} sweeps per iteration, {} equilibration sweeps'.format(
+            opts['iterations'], opts['num_chains'], opts['sweeps_per_iteration'], opts['equilibration_sweeps']))
+        ctx.plm_bm_begin(opts['num_chains'], opts['sweeps_per_iteration'], opts['equilibration_sweeps'], seed=int(seed),
+                         eta_h=opts['learning_rate'], eta_J=opts['learning_rate'], mu_h=opts['lambda_h'], mu_J=opts['lambda_J'],
+                         pseudocount=lam)
+        try:
+            history = ctx.plm_bm_iterate(opts['iterations'])
+        finally:
+            ctx.plm_bm_end()
+        if history.shape[0]:
+            logger.info('\n\tLast iteration: eps_h {:.3g}, eps_J {:.3g}, pearson {:.4f}'.format(*history[-1]))
+        return {'history': history, 'fields_and_couplings': ctx.plm_get_x(dt)}
 
     def compute_seqs_weight(self):
         """plmdca.py:565-591: weights of the PYTHON reader's alignment (float64 comparison,

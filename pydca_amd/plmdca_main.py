@@ -12,6 +12,7 @@ from .sequence_backmapper.sequence_backmapper import SequenceBackmapper
 
 logger = logging.getLogger(__name__)
 DCA_COMPUTATION_SUBCOMMANDS = ('compute_fn', 'compute_di', 'compute_params')
+BOLTZMANN_SUBCOMMAND = 'fit_boltzmann'
 
 
 def configure_logging():
@@ -21,7 +22,8 @@ def configure_logging():
 def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_file=None, seqid=None, lambda_h=None,
                               lambda_J=None, max_iterations=None, apc=False, verbose=False, output_dir=None,
                               num_threads=None, ranked_by=None, linear_dist=None, num_site_pairs=None, device=0,
-                              exact_gradient=False, precision=32, devices=None, query_file=None, wildtype_file=None, sampling=None):
+                              exact_gradient=False, precision=32, devices=None, query_file=None, wildtype_file=None, sampling=None,
+                              boltzmann=None):
     if verbose:
         configure_logging()
     plmdca_instance = plmdca.PlmDCA(msa_file, biomolecule, seqid=seqid, lambda_h=lambda_h, lambda_J=lambda_J,
@@ -34,6 +36,12 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
                                      dca_utilities.plmdca_param_metadata(plmdca_instance),
                                      _lib.DCA_BIOMOLECULE_PROTEIN if plmdca_instance.biomolecule == 'PROTEIN' else _lib.DCA_BIOMOLECULE_RNA, 0,
                                      plmdca.PlmDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling)
+    if the_command == BOLTZMANN_SUBCOMMAND:
+        if not output_dir:
+            output_dir = 'PLMDCA_output_' + os.path.splitext(os.path.basename(msa_file))[0]
+        return _potts.run_boltzmann(plmdca_instance, 'PLMDCA', msa_file, output_dir, dca_utilities.plmdca_param_metadata(plmdca_instance),
+                                    _lib.DCA_BIOMOLECULE_PROTEIN if plmdca_instance.biomolecule == 'PROTEIN' else _lib.DCA_BIOMOLECULE_RNA,
+                                    boltzmann)
     if the_command in DCA_COMPUTATION_SUBCOMMANDS:
         param_metadata = dca_utilities.plmdca_param_metadata(plmdca_instance)
         if not output_dir:
@@ -89,7 +97,7 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
 def run_plm_dca(argv=None):
     parser = ArgumentParser(prog='plmdca')
     subparsers = parser.add_subparsers(dest='subcommand_name')
-    for name in DCA_COMPUTATION_SUBCOMMANDS + _potts.POTTS_SUBCOMMANDS:
+    for name in DCA_COMPUTATION_SUBCOMMANDS + _potts.POTTS_SUBCOMMANDS + (BOLTZMANN_SUBCOMMAND,):
         p = subparsers.add_parser(name)
         p.add_argument('biomolecule', help='protein or rna (case insensitive)')
         p.add_argument('msa_file', help='FASTA formatted multiple sequence alignment, one sequence per line')
@@ -108,6 +116,8 @@ def run_plm_dca(argv=None):
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence (addition)')
         if name == 'sample_sequences':
             _potts.add_sampling_arguments(p)
+        if name == BOLTZMANN_SUBCOMMAND:
+            _potts.add_boltzmann_arguments(p)
         p.add_argument('--output_dir')
         p.add_argument('--device', type=int, default=0, help='GPU index (addition)')
         p.add_argument('--devices', help='comma-separated GPU indices, e.g. 0,1,2,3,4,5,6,7: one rank per GPU, sequences (or sites) '
@@ -130,7 +140,8 @@ def run_plm_dca(argv=None):
         ranked_by=args.get('ranked_by'), linear_dist=args.get('linear_dist'), num_site_pairs=args.get('num_site_pairs'),
         device=args.get('device'), exact_gradient=args.get('exact_gradient'), precision=args.get('precision'),
         devices=args.get('devices'), query_file=args.get('query_file'), wildtype_file=args.get('wildtype_file'),
-        sampling={k: args.get(k) for k in ('num_sequences', 'num_sweeps', 'seed', 'temperature', 'initial_file')})
+        sampling={k: args.get(k) for k in ('num_sequences', 'num_sweeps', 'seed', 'temperature', 'initial_file')},
+        boltzmann={k: args.get(k) for k in _potts.BOLTZMANN_OPTIONS})
 
 
 if __name__ == '__main__':
