@@ -387,6 +387,44 @@ int dca_plm_bm_chains(dca_ctx* ctx, uint8_t* out);
 /* ends the run (x keeps its refined values); DCA_OK without a run */
 int dca_plm_bm_end(dca_ctx* ctx);
 
+/* ------------------------------------------------------------------ log Z by annealed importance sampling (AIS; Neal 2001)
+ * Estimates Z = sum_s exp(E(s)) of the current x (E exactly as dca_plm_energies defines it, gap state included).
+ * h0: base fields, L*q finite host doubles, or NULL: the model's own fields h.  E0(s) = sum_i h0_i(s_i), in double over
+ * ascending i; dE = E - E0; the path is E_beta = E0 + beta * dE with 0 = beta_0 < beta_1 < ... < beta_K = 1 (K >= 1; betas NULL:
+ * beta_k = k / K in double).
+ * Start: chain c (= first_chain + c) draws x_0 exactly from p0(s) ~ exp(E0(s)): at site i, p_a = exp(h0_i(a) - max_b h0_i(b)) and
+ *   the samplers' draw rule with the Philox counter (chain, 0, i, 2) (tag 2; tags 0 and 1 keep their meaning).
+ * Transitions: for k = 1 .. K-1, s Gibbs sweeps under E_{beta_k}, numbered and drawn exactly as dca_plm_sample (tag 0, global sweep
+ *   numbers (k-1)s .. ks-1, ascending sites) except that the conditional is c_i(a) = h0_i(a) + beta_k * (u_i(a) - h0_i(a)), u_i(a)
+ *   the sampler's double sum (same order), and p_a = exp(c_i(a) - max_b c_i(b)).  No sweep runs at beta_K = 1.
+ * Weights: log w = 0.0; for k = 1 .. K: log w <- log w + (beta_k - beta_{k-1}) * (E(x_{k-1}) - E0(x_{k-1})), every operation rounded in
+ *   double in the order written (no fused multiply-add); E(x) here is bit for bit what dca_plm_energies returns for those codes.
+ * Outputs: log_weights_out (n), log_z0_out = log sum_s exp(E0(s)) as dca_ais_estimate wants it (may be NULL), chains_out: the n x L
+ *   codes x_{K-1} after the last transition (may be NULL).  Chain c's codes and log w depend only on the model, h0, the schedule, s,
+ *   the seed and first_chain + c: the same bits in any batch or split.
+ * DCA_ERR_ARG: args or log_weights_out NULL, n < 1 or n > 2^24, K < 1, s < 0, betas not finite, not strictly increasing or not from
+ *   0 to 1, a base field not finite.  DCA_ERR_STATE before dca_plm_configure, under column strips, vector sharding, a reduce / comm
+ *   hook or a native-comm mode (one GPU only); an L-BFGS run in progress is allowed, as for dca_plm_sample.
+ * The call touches neither the alignment, the weights, x, g, the optimiser nor a bmDCA run in progress (its chains and its next
+ * iteration keep their bits).  Nothing leaves the device between temperatures.  Profiling tags: the sweeps "sample", the start draw
+ * and the weight updates "ais".  No reference counterpart. */
+typedef struct dca_ais_args {
+    int chains;                   /* n >= 1 */
+    int temperatures;             /* K >= 1 */
+    const double* betas;          /* K + 1 values as above, or NULL: k / K */
+    int sweeps_per_temperature;   /* s >= 0 */
+    uint64_t seed, first_chain;
+    const double* base_fields;    /* L*q host doubles, or NULL: the model's own fields */
+} dca_ais_args;
+int dca_plm_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out /* n */, double* log_z0_out,
+                uint8_t* chains_out /* n x L, or NULL */);
+/* The estimate from n log weights, on the host in a fixed order (needs no device):
+ *   log Z0 = sum_i (m_i + log sum_a exp(h0_i(a) - m_i)), m_i = max_a h0_i(a) (what the AIS entries return);
+ *   m = max_c log w_c, S1 = sum_c exp(log w_c - m), S2 = sum_c exp(2 (log w_c - m)), both over ascending c;
+ *   log Z = ((log Z0 + m) + log S1) - log n;  ESS = S1 S1 / S2;  stderr(log Z) = sqrt(max(0, S2 / (S1 S1) - 1 / n)), the
+ *   delta-method error of log-mean-w.  Outputs may be NULL.  DCA_ERR_ARG: log_weights NULL, n < 1, a value not finite. */
+int dca_ais_estimate(const double* log_weights, int n, double log_z0, double* log_z, double* ess, double* stderr_log_z);
+
 /* ------------------------------------------------------------------ DI on caller-provided arrays
  * The module-level functions of the reference: compute_two_site_model_fields + compute_direct_info
  * (meanfield_dca/msa_numerics.py:378-533: layout 1 = couplings as the n x n matrix, n = L(q-1);
@@ -435,6 +473,9 @@ int dca_mf_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out /
  * determinism and argument checks; DCA_ERR_STATE before dca_mf_couplings. */
 int dca_mf_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                   const uint8_t* initial, uint8_t* out);
+/* dca_plm_ais under the mean-field model (E, h as in dca_mf_energies; base_fields NULL: those fields, 0 on the gap state).  Same
+ * rules, RNG layout, determinism and argument checks; DCA_ERR_STATE before dca_mf_couplings. */
+int dca_mf_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out);
 /* The counter-based generator of the samplers, on the host: Philox4x32-10 (Salmon et al., SC 2011; 10 rounds, multipliers
  * 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 / 0xBB67AE85).  Needs no device. */
 int dca_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
@@ -460,7 +501,7 @@ int dca_spd_inverse(dca_ctx* ctx, const double* A, int n, double* Ainv_out);
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
  * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "sample",
- * "bm_stats"). */
+ * "bm_stats", "ais"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it
  * instead of two per stage (an event record costs the stream ~5 us: 14 per plmDCA iteration are 5 % of config C's step, 0.4 % of

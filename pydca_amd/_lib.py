@@ -42,6 +42,12 @@ class BmArgs(C.Structure):
                 ("pseudocount", C.c_double), ("initial", C.c_void_p)]
 
 
+class AisArgs(C.Structure):
+    """dca_ais_args (include/dca_hip.h)"""
+    _fields_ = [("chains", C.c_int), ("temperatures", C.c_int), ("betas", C.c_void_p), ("sweeps_per_temperature", C.c_int),
+                ("seed", C.c_uint64), ("first_chain", C.c_uint64), ("base_fields", C.c_void_p)]
+
+
 COMM_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
 COMM_ALL_REDUCE, COMM_REDUCE_SCATTER, COMM_ALL_GATHER = 0, 1, 2
 REDUCE_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -133,6 +139,9 @@ def lib():
         "dca_plm_bm_freqs": (i, [vp, i, vp, vp]),
         "dca_plm_bm_chains": (i, [vp, vp]),
         "dca_plm_bm_end": (i, [vp]),
+        "dca_plm_ais": (i, [vp, C.POINTER(AisArgs), vp, C.POINTER(d), vp]),
+        "dca_mf_ais": (i, [vp, C.POINTER(AisArgs), vp, C.POINTER(d), vp]),
+        "dca_ais_estimate": (i, [vp, i, d, C.POINTER(d), C.POINTER(d), C.POINTER(d)]),
         "dca_mf_pair_couplings": (i, [vp, vp, i, i, vp]),
         "dca_mf_single_site_freqs": (i, [vp, vp]),
         "dca_mf_pair_site_freqs": (i, [vp, vp]),
@@ -175,10 +184,48 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_encode_sequences", "dca_plm_energies", "dca_plm_mutation_scan", "dca_mf_energies", "dca_mf_mutation_scan",
            "dca_plm_sample", "dca_mf_sample", "dca_philox4x32_10",
            "dca_plm_bm_begin", "dca_plm_bm_iterate", "dca_plm_bm_freqs", "dca_plm_bm_chains", "dca_plm_bm_end",
+           "dca_plm_ais", "dca_mf_ais", "dca_ais_estimate",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
            "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
            "dca_reset_kernel_times", "dca_plm_run", "plmdcaBackend", "freeFieldsAndCouplings"]
+
+
+def ais_schedule(temperatures, betas=None):
+    """The annealing schedule of the AIS entries: betas None -> None (the library forms k / K), else float64[K + 1], checked as
+    dca_plm_ais checks it (finite, strictly increasing from 0 to 1); ValueError otherwise."""
+    K = int(temperatures)
+    if K < 1:
+        raise ValueError("the number of temperatures must be >= 1, not %r" % (temperatures,))
+    if betas is None:
+        return None
+    b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+    if b.size != K + 1:
+        raise ValueError("betas must hold K + 1 = %d values, not %d" % (K + 1, b.size))
+    if not np.all(np.isfinite(b)) or b[0] != 0.0 or b[-1] != 1.0 or not np.all(np.diff(b) > 0):
+        raise ValueError("betas must be finite and strictly increasing from 0 to 1")
+    return b
+
+
+def ais_base_fields(base_fields, L, q):
+    """None -> None (the model's own fields), else float64[L, q] of finite values; ValueError otherwise."""
+    if base_fields is None:
+        return None
+    h = np.ascontiguousarray(base_fields, dtype=np.float64)
+    if h.size != L * q:
+        raise ValueError("the base fields must be an L x q = %d x %d array, not of shape %s" % (L, q, h.shape))
+    h = h.reshape(L, q)
+    if not np.all(np.isfinite(h)):
+        raise ValueError("the base fields must be finite")
+    return h
+
+
+def ais_estimate(log_weights, log_z0):
+    """dca_ais_estimate -> (log_z, ess, stderr_log_z)"""
+    w = np.ascontiguousarray(log_weights, dtype=np.float64).reshape(-1)
+    lz, ess, se = C.c_double(0), C.c_double(0), C.c_double(0)
+    check(lib().dca_ais_estimate(_ptr(w) if w.size else None, int(w.size), float(log_z0), C.byref(lz), C.byref(ess), C.byref(se)))
+    return lz.value, ess.value, se.value
 
 
 class PlmArgs(C.Structure):
@@ -665,6 +712,29 @@ class Context:
 
     def plm_bm_end(self):
         check(self._l.dca_plm_bm_end(self._h))
+
+    # ---- log Z by annealed importance sampling (ais.hip) -> (float64[n] log weights, log Z0, uint8[n, L] final chains or None)
+    def _ais(self, fn, chains, temperatures, sweeps_per_temperature, seed, first_chain, betas, base_fields, return_chains):
+        n = int(chains)
+        b = ais_schedule(temperatures, betas)
+        h0 = ais_base_fields(base_fields, self.L, self.q)
+        args = AisArgs(n, int(temperatures), None if b is None else b.ctypes.data, int(sweeps_per_temperature), int(seed),
+                       int(first_chain), None if h0 is None else h0.ctypes.data)
+        logw = np.zeros(max(n, 0), dtype=np.float64)
+        lz0 = C.c_double(0)
+        out = np.zeros((max(n, 0), self.L), dtype=np.uint8) if return_chains else None
+        check(fn(self._h, C.byref(args), _ptr(logw) if logw.size else None, C.byref(lz0), None if out is None else _ptr(out)))
+        return logw, lz0.value, out
+
+    def plm_ais(self, chains, temperatures, sweeps_per_temperature=1, seed=0, first_chain=0, betas=None, base_fields=None,
+                return_chains=False):
+        return self._ais(self._l.dca_plm_ais, chains, temperatures, sweeps_per_temperature, seed, first_chain, betas, base_fields,
+                         return_chains)
+
+    def mf_ais(self, chains, temperatures, sweeps_per_temperature=1, seed=0, first_chain=0, betas=None, base_fields=None,
+               return_chains=False):
+        return self._ais(self._l.dca_mf_ais, chains, temperatures, sweeps_per_temperature, seed, first_chain, betas, base_fields,
+                         return_chains)
 
     def mf_di_scores(self, apc=False):
         out = np.zeros(self.L * (self.L - 1) // 2, dtype=np.float64)

@@ -70,7 +70,67 @@ def state_letters(biomolecule):
 
 
 
-POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences')
+def ais_options(num_chains, num_temperatures, sweeps_per_temperature, seed, pseudocount, exc_type):
+    """Checks the AIS arguments of compute_log_partition_function (host only) -> dict of the checked values."""
+    def count(name, v, low):
+        if isinstance(v, bool) or int(v) != v or int(v) < low:
+            raise exc_type('{} must be an integer >= {}, not {!r}'.format(name, low, v))
+        return int(v)
+    opts = dict(num_chains=count('num_chains', num_chains, 1), num_temperatures=count('num_temperatures', num_temperatures, 1),
+                sweeps_per_temperature=count('sweeps_per_temperature', sweeps_per_temperature, 0), seed=count('seed', seed, 0),
+                pseudocount=None)
+    if opts['num_chains'] > 1 << 24:
+        raise exc_type('num_chains must be <= 2^24, not {}'.format(num_chains))
+    if pseudocount is not None:
+        opts['pseudocount'] = float(pseudocount)
+        if not (0.0 < opts['pseudocount'] <= 1.0):
+            raise exc_type('pseudocount must lie in (0, 1], not {!r}'.format(pseudocount))
+    return opts
+
+
+def profile_fields(X, weights, q, pseudocount=None):
+    """h0 = log((1 - lambda) f + lambda / q) of the weighted single-site frequencies f of the alignment X (codes, N x L) with
+    weights w: f_i(a) = sum_n w_n [X_ni = a] / Meff, Meff = sum_n w_n; lambda = pseudocount, or 1 / Meff -> float64[L, q]."""
+    X = np.asarray(X)
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    meff = float(w.sum())
+    lam = 1.0 / meff if pseudocount is None else float(pseudocount)
+    f = np.stack([(w[:, None] * (X == a)).sum(axis=0) for a in range(q)], axis=1) / meff
+    return np.log((1.0 - lam) * f + lam / q)
+
+
+def ais_base(base, X, weights, L, q, pseudocount, exc_type):
+    """base of compute_log_partition_function: 'profile' (the training profile, profile_fields), 'fields' (None: the model's own
+    fields) or an L x q array of finite values -> float64[L, q] or None."""
+    if isinstance(base, str):
+        if base == 'profile':
+            h0 = profile_fields(X, weights, q, pseudocount)
+        elif base == 'fields':
+            return None
+        else:
+            raise exc_type("base must be 'profile', 'fields' or an L x q array, not {!r}".format(base))
+    else:
+        h0 = base
+    try:
+        return _lib.ais_base_fields(h0, L, q)
+    except ValueError as exc:
+        raise exc_type(str(exc))
+
+
+def log_partition_function(run_ais, opts, base_fields):
+    """run_ais(n, K, s, seed, h0) -> (log weights, log Z0, _) of the context's AIS entry; -> the dict of
+    compute_log_partition_function."""
+    logw, log_z0, _ = run_ais(opts['num_chains'], opts['num_temperatures'], opts['sweeps_per_temperature'], opts['seed'], base_fields)
+    log_z, ess, stderr = _lib.ais_estimate(logw, log_z0)
+    return {'log_z': log_z, 'log_z_stderr': stderr, 'ess': ess, 'log_z_base': log_z0, 'log_weights': logw}
+
+
+def log_likelihood(energies, weights, meff, log_z):
+    """(sum_n w_n E(s_n)) / Meff - log Z"""
+    return float(np.dot(np.asarray(weights, dtype=np.float64), np.asarray(energies, dtype=np.float64))) / float(meff) - float(log_z)
+
+
+POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences', 'compute_log_likelihood')
 
 
 def add_sampling_arguments(p):
@@ -82,13 +142,47 @@ def add_sampling_arguments(p):
     p.add_argument('--initial_file', help='FASTA file with 1 or num_sequences aligned starting sequences (default: random) (addition)')
 
 
+def add_ais_arguments(p):
+    """The options of the compute_log_likelihood sub-command (plmdca and mfdca command lines)."""
+    p.add_argument('--num_chains', type=int, default=1000, help='AIS chains (addition)')
+    p.add_argument('--num_temperatures', type=int, default=1000, help='K, annealing steps beta_k = k / K (addition)')
+    p.add_argument('--sweeps_per_temperature', type=int, default=1, help='Gibbs sweeps per intermediate temperature (addition)')
+    p.add_argument('--seed', type=int, default=0, help='seed of the counter-based generator (addition)')
+    p.add_argument('--base', choices=('profile', 'fields'), default='profile',
+                   help='base model: the training profile or the model\'s own fields (addition)')
+    p.add_argument('--base_pseudocount', type=float, help='pseudocount of the profile base (default: 1 / Meff) (addition)')
+
+
+AIS_OPTIONS = ('num_chains', 'num_temperatures', 'sweeps_per_temperature', 'seed', 'base', 'base_pseudocount')
+
+
+def run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, opts):
+    """compute_log_likelihood of the plmdca and mfdca command lines -> the path of <output_dir>/<prefix>_log_likelihood_
+    <alignment base>.txt: a header with log Z, its stderr, the ESS, log Z0 and the schedule, the average log-likelihood of the
+    training alignment, then one log P(s) = E(s) - log Z per training record (file order)."""
+    from .dca_utilities import dca_utilities
+    opts = {k: v for k, v in dict(opts or {}).items() if v is not None}
+    kw = dict(num_chains=opts.get('num_chains', 1000), num_temperatures=opts.get('num_temperatures', 1000),
+              sweeps_per_temperature=opts.get('sweeps_per_temperature', 1), seed=opts.get('seed', 0), base=opts.get('base', 'profile'),
+              pseudocount=opts.get('base_pseudocount'))
+    dca_utilities.create_directories(output_dir)
+    res = instance.compute_log_partition_function(**kw)
+    ll = instance.compute_log_likelihood(log_z=res['log_z'])
+    logp = instance.compute_sequence_log_probabilities(log_z=res['log_z'])
+    path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_log_likelihood_', postfix='.txt')
+    dca_utilities.write_log_likelihood(path, res, ll, logp, kw, metadata=metadata)
+    return path
+
+
 def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata, biomolecule, table, exc_type,
-                   query_file=None, wildtype_file=None, sampling=None):
+                   query_file=None, wildtype_file=None, sampling=None, ais=None):
     """compute_energies / compute_mutation_effects / sample_sequences of the plmdca and mfdca command lines -> the path of
     the file written: <output_dir>/<prefix>_energies_<alignment base>.txt, <prefix>_mutation_effects_<alignment base>.txt
     or <prefix>_samples_<alignment base>.fa.  sampling: the sample_sequences options (num_sequences, num_sweeps, seed,
     temperature, initial_file)."""
     from .dca_utilities import dca_utilities
+    if the_command == 'compute_log_likelihood':
+        return run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, ais)
     dca_utilities.create_directories(output_dir)
     if the_command == 'sample_sequences':
         opts = dict(sampling or {})

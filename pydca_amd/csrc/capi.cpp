@@ -520,6 +520,14 @@ int dca_plm_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t firs
     DCA_TRY(need_plm(ctx));
     return ctx->plm->sample(n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
 }
+// annealed importance sampling (ais.hip) of the plm engine's x
+int dca_plm_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    if (!args || !log_weights_out) { dca_set_error("dca_plm_ais: args or log_weights_out is NULL"); return DCA_ERR_ARG; }
+    return ctx->plm->ais(args, log_weights_out, log_z0_out, chains_out);
+}
 // Boltzmann learning (boltzmann.hip) on the plm engine's x
 int dca_plm_bm_begin(dca_ctx* ctx, const dca_bm_args* args)
 {
@@ -689,6 +697,13 @@ int dca_mf_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first
     CHECK_CTX(ctx);
     DCA_TRY(need_mf(ctx));
     return dca_mf_engine_sample(ctx->mf, n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
+}
+int dca_mf_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_mf(ctx));
+    if (!args || !log_weights_out) { dca_set_error("dca_mf_ais: args or log_weights_out is NULL"); return DCA_ERR_ARG; }
+    return dca_mf_engine_ais(ctx->mf, args, log_weights_out, log_z0_out, chains_out);
 }
 int dca_mf_pair_couplings(dca_ctx* ctx, const int* pairs, int npairs, int shift, double* out)
 {

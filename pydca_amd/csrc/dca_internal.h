@@ -175,6 +175,9 @@ struct PlmEngineBase {
     // the device x a Boltzmann-learning run updates in place; DCA_ERR_STATE (with the reason) unconfigured, during an L-BFGS
     // run, under column strips, vector sharding, a reduce / comm hook or a native-comm mode
     virtual int bm_source(void** dx) = 0;
+    // annealed importance sampling of the current x (ais.hip); DCA_ERR_STATE unconfigured, under column strips, vector sharding,
+    // a reduce / comm hook or a native-comm mode
+    virtual int ais(const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out) = 0;
     virtual int set_vector_sharding(int rank, int world, dca_comm_hook hook, void* user) = 0;
     dca_reduce_hook hook = nullptr;
     void* hook_user = nullptr;
@@ -204,21 +207,59 @@ int dca_potts_energies(dca_ctx* ctx, const void* src, int src_kind, int dtype, c
 int dca_potts_mutation_scan(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
                             const uint8_t* wildtype, double* out /* L*q */);
 
+// The pair stage of dca_potts_energies on device codes QT[s * NqS + k] (k < nq, NqS a multiple of 128): slab g of query k at
+// dSlabs[g * NqS + k], g < dca_energy_slab_count(L, q, dtype).  E(k) = sum_i h_i (ascending i) + sum_g slab (ascending g) is then
+// bit for bit what dca_potts_energies returns for those codes.
+int dca_energy_slab_count(int L, int q, int dtype);
+hipError_t dca_energy_pairs_device(dca_ctx* ctx, const void* src, int src_kind, int dtype, int L, int q, int ld, const uint8_t* dQT, int nq,
+                                   int NqS, double* dSlabs);
+
 // ---- sample.hip : Gibbs sampling of n chains (one launch per sweep) under the same sources.  initial / out: host, n x L.
 int dca_potts_sample(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld, int n,
                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                      const uint8_t* initial /* host n*L or NULL */, uint8_t* out /* host n*L */);
 
+// Philox4x32-10 of the samplers (sample.hip, ais.hip): key = (seed lo, seed hi), counter = (chain, sweep, site, tag), each
+// word the value mod 2^32; U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  Tags: 0 Gibbs draw, 1 random start, 2 AIS start.
+static __host__ __device__ __forceinline__ void philox4x32_10(const uint32_t in[4], const uint32_t k[2], uint32_t out[4])
+{
+    uint32_t c0 = in[0], c1 = in[1], c2 = in[2], c3 = in[3], k0 = k[0], k1 = k[1];
+    for (int r = 0; r < 10; ++r) {
+        if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+static __device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t chain, uint64_t sweep, int site, uint32_t tag)
+{
+    const uint32_t ctr[4] = {(uint32_t)chain, (uint32_t)sweep, (uint32_t)site, tag};
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    uint32_t w[4];
+    philox4x32_10(ctr, key, w);
+    return (double)((uint64_t)(w[0] >> 5) * 67108864ull + (w[1] >> 6)) * 0x1.0p-53;
+}
+
 // Device-resident chains of the sampler: site-major codes st[s * nS + c], nS = n rounded up to 64 (the chains past n are
 // swept too and never read).  dca_chains_start: tag-1 random starts of chains first_chain + c, or the host rows `initial`
 // (n x L codes < q, checked by the caller).  dca_chains_sweeps: `sweeps` launches numbered first_sweep.., one per sweep, under
-// the tag "sample".  dca_chains_read: the n x L rows to the host (synchronises).
+// the tag "sample"; with dBase (L x q device doubles) the sweeps draw from the AIS interpolation h0 + bk * (u - h0) instead
+// (beta unused).  dca_chains_read: the n x L rows to the host (synchronises).  Any nS that is a multiple of 64 works (ais.hip
+// uses multiples of 128, the energy kernels' stride).
 struct DcaChains { int n = 0, L = 0, nS = 0; uint8_t* dState = nullptr; };
 int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial);
 int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const void* src, int src_kind, int dtype, const double* dMfFields, int q, int ld,
-                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta);
+                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                      const double* dBase = nullptr, double bk = 0.0);
 int dca_chains_read(dca_ctx* ctx, const DcaChains& ch, uint8_t* out);
 void dca_chains_free(DcaChains* ch);
+
+// ---- ais.hip : annealed importance sampling of log Z under the same sources (dca_plm_ais / dca_mf_ais; arguments checked here)
+int dca_potts_ais(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
+                  const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out);
+double dca_ais_log_z0(const double* h0, int L, int q);    // host, L x q base fields
 
 // ---- boltzmann.hip : Boltzmann machine learning of the plm vector (dca_plm_bm_*).  The run lives in ctx->bm; dca_bm_free ends
 // it (alignment, weights, configure, L-BFGS begin, engine release, destroy).  x: the plm engine's device vector (PlmEngineBase::
@@ -256,6 +297,7 @@ int dca_mf_engine_mutation_scan(MfEngine*, const uint8_t* wildtype, double* out)
 int dca_mf_engine_bm_freqs(MfEngine*, double lambda, double* dFi, double* dFij);
 int dca_mf_engine_sample(MfEngine*, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                          const uint8_t* initial, uint8_t* out);
+int dca_mf_engine_ais(MfEngine*, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out);
 
 // ---- cholinv.hip : scale * inverse of an SPD matrix on the device (f64 MFMA)
 // dA: n x n row-major (ld = n), n multiple of 64; destroyed (holds the triangular factor's inverse afterwards).

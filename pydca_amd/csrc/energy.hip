@@ -278,3 +278,20 @@ int dca_potts_mutation_scan(dca_ctx* ctx, const void* src, int src_kind, int dty
     if (dtype == DCA_F32) return mutation_scan_t(ctx, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, wt, out);
     return mutation_scan_t(ctx, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, wt, out);
 }
+
+// ---- the pair stage on device-resident site-major codes (ais.hip): the same kernels, geometry and order as above
+int dca_energy_slab_count(int L, int q, int dtype)
+{
+    return energy_geometry(L, q, dtype == DCA_F32 ? sizeof(float) : sizeof(double)).G;
+}
+
+hipError_t dca_energy_pairs_device(dca_ctx* ctx, const void* src, int src_kind, int dtype, int L, int q, int ld, const uint8_t* dQT, int nq,
+                                   int NqS, double* dSlabs)
+{
+    if (dtype == DCA_F32) {
+        const EnergyGeom eg = energy_geometry(L, q, sizeof(float));
+        return dispatch_pairs<float>(ctx, eg, static_cast<const float*>(src), src_kind, L, q, ld, dQT, nq, NqS, dSlabs);
+    }
+    const EnergyGeom eg = energy_geometry(L, q, sizeof(double));
+    return dispatch_pairs<double>(ctx, eg, static_cast<const double*>(src), src_kind, L, q, ld, dQT, nq, NqS, dSlabs);
+}

@@ -669,6 +669,16 @@ int dca_mf_engine_sample(MfEngine* m, int n, int sweeps, uint64_t seed, uint64_t
     return rc;
 }
 
+int dca_mf_engine_ais(MfEngine* m, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
+{
+    double* dH = nullptr;
+    DCA_TRY(mf_fields_device(m, &dH));
+    const int rc = dca_potts_ais(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, args, log_weights_out, log_z0_out, chains_out);
+    hipStreamSynchronize(m->ctx->stream);
+    dca_dev_free(dH);
+    return rc;
+}
+
 int dca_mf_engine_pair_couplings(MfEngine* m, const int* pairs, int npairs, int shift, double* out)
 {
     if (!m->have_J) { dca_set_error("dca_mf_couplings first"); return DCA_ERR_STATE; }

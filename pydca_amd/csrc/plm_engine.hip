@@ -2241,6 +2241,17 @@ struct PlmEngine : PlmEngineBase {
         *x = dx;
         return DCA_OK;
     }
+    // annealed importance sampling of the current x; one GPU only, an L-BFGS run in progress is allowed (as for sample())
+    int ais(const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out) override
+    {
+        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
+        if (strips || native_mode == 4) { dca_set_error("AIS runs on one GPU: configured for column strips"); return DCA_ERR_STATE; }
+        if (comm || hook || native_mode != 0) {
+            dca_set_error("AIS runs on one GPU: vector sharding, a reduce / comm hook or a native-comm mode is set");
+            return DCA_ERR_STATE;
+        }
+        return dca_potts_ais(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, args, log_weights_out, log_z0_out, chains_out);
+    }
     int set_vector_sharding(int rank, int world, dca_comm_hook h, void* user) override
     {
         if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }

@@ -10,7 +10,9 @@
 // Draw rule (restated by the tests): T = sum_a p_a ascending; r = U * T; s_i = the smallest a with p_0 + ... + p_a > r
 // (ascending sums), or the largest a with p_a > 0 if rounding leaves none.  U = Philox4x32-10 of
 //   key = (seed lo, seed hi), counter = (chain, sweep, site, tag) (each word the value mod 2^32), tag 0: Gibbs draw,
-//   tag 1: initial state (sweep word 0, s_i = floor(U * q)); U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.
+//   tag 1: initial state (sweep word 0, s_i = floor(U * q)); U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  (Tag 2 is the AIS
+//   start draw, ais.hip.)  The INTERP instantiations draw from the AIS interpolation c(a) = h0_i(a) + bk (u(a) - h0_i(a)) instead
+//   of beta * u(a); the others compile to the plain sweep.
 //
 // Geometry: one workgroup of 4 waves holds 64 chains (lane = chain) in lockstep over the sites.  Wave w sums the j = w
 // (mod 4) terms; the partials meet in LDS in ascending w and wave 0 draws.  Row i of J (L blocks of q x q) streams through
@@ -30,27 +32,6 @@ constexpr int kSThreads = 256;                    // 4 waves, 64 chains
 constexpr int kSChains = 64;
 constexpr int kSResidentL = 512;                  // chain codes in LDS up to 32 KiB
 constexpr size_t kSChunkBudget = 40 * 1024;       // LDS per J chunk buffer (two of them)
-
-__host__ __device__ __forceinline__ void philox4x32_10(const uint32_t in[4], const uint32_t k[2], uint32_t out[4])
-{
-    uint32_t c0 = in[0], c1 = in[1], c2 = in[2], c3 = in[3], k0 = k[0], k1 = k[1];
-    for (int r = 0; r < 10; ++r) {
-        if (r > 0) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-__device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t chain, uint64_t sweep, int site, uint32_t tag)
-{
-    const uint32_t ctr[4] = {(uint32_t)chain, (uint32_t)sweep, (uint32_t)site, tag};
-    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
-    uint32_t w[4];
-    philox4x32_10(ctr, key, w);
-    return (double)((uint64_t)(w[0] >> 5) * 67108864ull + (w[1] >> 6)) * 0x1.0p-53;
-}
 
 __device__ __forceinline__ size_t pair_index(int L, int i, int j)
 {
@@ -105,10 +86,13 @@ __global__ void initial_state_kernel(int n, int L, int q, int nS, uint64_t seed,
 
 // One sweep.  grid: nS / 64 workgroups.  LDS: two chunk buffers (CJ blocks of q x QM values of S each), the partial
 // buffer (QM x 64 doubles), and with RES the chain codes (L x 64 bytes, site-major).  R: chunk elements per thread.
-template <typename S, int QM, bool RES, int R>
+// INTERP (annealed importance sampling, ais.hip): wave 0 draws from c(a) = h0_i(a) + bk * (u(a) - h0_i(a)),
+// p_a = exp(c(a) - max_b c(b)), with h0 the L x q base fields (device); beta is not used.  Without it h0 and bk are not read.
+template <typename S, int QM, bool RES, int R, bool INTERP>
 __global__ __launch_bounds__(kSThreads)
 void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __restrict__ mfh, int L, int q, int ld, int CJ,
-                        uint8_t* __restrict__ state, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta)
+                        uint8_t* __restrict__ state, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta,
+                        const double* __restrict__ h0, double bk)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char sample_smem[];
     const int blk = q * QM;                                   // values of one staged block
@@ -201,13 +185,22 @@ void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __res
                 __syncthreads();
             }
             if (wave == 0) {
+                if constexpr (INTERP) {
+#pragma unroll
+                    for (int a = 0; a < QM; ++a)
+                        if (a < q) {
+                            const double b0 = h0[(size_t)i * q + a];
+                            u[a] = b0 + bk * (u[a] - b0);
+                        }
+                }
                 double m = u[0];
 #pragma unroll
                 for (int a = 1; a < QM; ++a) if (a < q) m = fmax(m, u[a]);
                 double T = 0.0;
 #pragma unroll
                 for (int a = 0; a < QM; ++a) {
-                    u[a] = a < q ? exp(beta * (u[a] - m)) : 0.0;
+                    if constexpr (INTERP) u[a] = a < q ? exp(u[a] - m) : 0.0;
+                    else u[a] = a < q ? exp(beta * (u[a] - m)) : 0.0;
                     T += u[a];
                 }
                 const double r = philox_uniform(seed, chain, sweep, i, 0) * T;
@@ -247,36 +240,45 @@ SampleGeom sample_geometry(int L, int q, size_t elem)
     return g;
 }
 
-template <typename S, int QM, bool RES>
+template <typename S, int QM, bool RES, bool INTERP>
 hipError_t launch_sweep(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
-                        uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta)
+                        uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta, const double* h0, double bk)
 {
     constexpr int R = sizeof(S) == 4 ? 32 : 16;
-    auto kern = gibbs_sweep_kernel<S, QM, RES, R>;
+    auto kern = gibbs_sweep_kernel<S, QM, RES, R, INTERP>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(nS / kSChains), dim3(kSThreads), sg.lds, ctx->stream, src, kind, mfh, L, q, ld, sg.CJ, dState, nS,
-                       seed, first_chain, sweep, beta);
+                       seed, first_chain, sweep, beta, h0, bk);
     return hipGetLastError();
 }
 
-template <typename S, int QM>
+template <typename S, int QM, bool INTERP>
 hipError_t dispatch_res(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
-                        uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta)
+                        uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta, const double* h0, double bk)
 {
-    if (sg.res) return launch_sweep<S, QM, true>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
-    return launch_sweep<S, QM, false>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
+    if (sg.res) return launch_sweep<S, QM, true, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
+    return launch_sweep<S, QM, false, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
 }
 
-template <typename S>
-hipError_t dispatch_sweep(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
-                          uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta)
+template <typename S, bool INTERP>
+hipError_t dispatch_qm(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
+                       uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta, const double* h0, double bk)
 {
     switch (sg.QM) {
-    case 8: return dispatch_res<S, 8>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
-    case 24: return dispatch_res<S, 24>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
-    default: return dispatch_res<S, 32>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta);
+    case 8: return dispatch_res<S, 8, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
+    case 24: return dispatch_res<S, 24, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
+    default: return dispatch_res<S, 32, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
     }
+}
+
+// h0 NULL: the plain sweep under beta; otherwise the interpolated one (INTERP above)
+template <typename S>
+hipError_t dispatch_sweep(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
+                          uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta, const double* h0, double bk)
+{
+    if (h0) return dispatch_qm<S, true>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
+    return dispatch_qm<S, false>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
 }
 
 }  // namespace
@@ -309,7 +311,7 @@ int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t 
 }
 
 int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const void* src, int src_kind, int dtype, const double* dMfFields, int q, int ld,
-                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta)
+                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta, const double* dBase, double bk)
 {
     const int L = ch.L;
     hipError_t e = hipSuccess;
@@ -318,14 +320,14 @@ int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const void* src, int sr
         for (int t = 0; t < sweeps && e == hipSuccess; ++t) {       // one launch per sweep
             ScopedKernelClock kc(ctx, "sample");
             e = dispatch_sweep<float>(ctx, sg, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, ch.dState, ch.nS, seed,
-                                      first_chain, first_sweep + (uint64_t)t, beta);
+                                      first_chain, first_sweep + (uint64_t)t, beta, dBase, bk);
         }
     } else {
         const SampleGeom sg = sample_geometry(L, q, sizeof(double));
         for (int t = 0; t < sweeps && e == hipSuccess; ++t) {
             ScopedKernelClock kc(ctx, "sample");
             e = dispatch_sweep<double>(ctx, sg, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, ch.dState, ch.nS, seed,
-                                       first_chain, first_sweep + (uint64_t)t, beta);
+                                       first_chain, first_sweep + (uint64_t)t, beta, dBase, bk);
         }
     }
     if (e != hipSuccess) { dca_set_error("sample: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }

@@ -124,6 +124,26 @@ def write_boltzmann_history(file_name, history, metadata=None):
     _stream(file_name, header, rows, 'Boltzmann learning curve')
 
 
+def write_log_likelihood(file_name, result, log_likelihood, log_probabilities, options, metadata=None):
+    """log Z by annealed importance sampling and the log-likelihood of the training alignment (compute_log_likelihood
+    sub-command): a header with log Z, its stderr, the ESS, log Z0 and the schedule, the line 'average_log_likelihood <value>',
+    then one log P(s) = E(s) - log Z per training record in file order, every value written with %.17g (no reference
+    counterpart)."""
+    g = lambda v: '%.17g' % float(v)
+    header = [_RULE] + list(metadata or []) + [
+        '#\tlog Z (annealed importance sampling): {}'.format(g(result['log_z'])),
+        '#\tstderr of log Z: {}'.format(g(result['log_z_stderr'])),
+        '#\teffective sample size: {}'.format(g(result['ess'])),
+        '#\tlog Z of the base model: {}'.format(g(result['log_z_base'])),
+        '#\tschedule: {} chains, K = {} temperatures beta_k = k / K, {} sweeps per temperature, seed {}, base {}'.format(
+            options['num_chains'], options['num_temperatures'], options['sweeps_per_temperature'], options['seed'],
+            options['base'] if isinstance(options['base'], str) else 'array'),
+        '# Below: the average log-likelihood (sum_n w_n E(s_n)) / Meff - log Z of the training alignment, then one',
+        '# log-probability E(s) - log Z per training record (file order)', _RULE]
+    rows = ['average_log_likelihood {}'.format(g(log_likelihood))] + [g(v) for v in log_probabilities]
+    _stream(file_name, header, rows, 'log-likelihood')
+
+
 def _csv(prefix_values, values):
     # '{}'.format(v), not str(v): numpy scalars of the two print differently (a float32 is widened by format)
     return ','.join('{}'.format(v) for v in list(prefix_values) + list(values))

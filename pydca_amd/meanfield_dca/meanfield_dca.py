@@ -54,6 +54,7 @@ class MeanFieldDCA:
         self.__biomolecule = biomolecule
         t1 = time.perf_counter()
         devices = multi_gpu.parse_devices(devices)          # ValueError on a malformed list, as for the other arguments
+        self.__devices = devices
         if devices and len(devices) > 1:
             # one rank per GPU for the two stages that scale with the number of sequences: the weights (N^2 L comparisons divided
             # over the ranks) and the pair counts (a window of the sequences each, ONE all-reduce); what follows runs here
@@ -305,6 +306,47 @@ class MeanFieldDCA:
             return codes
         letters = _potts.state_letters(bio)
         return [''.join(letters[c] for c in row) for row in codes]
+
+    # ---- normalised probabilities: log Z by annealed importance sampling (no reference counterpart)
+    def _one_gpu(self, what):
+        if self.__devices and len(self.__devices) > 1:
+            logger.error('\n\t{} runs on one GPU; devices={}'.format(what, self.__devices))
+            raise MeanFieldDCAException('{} runs on one GPU, not on devices {}'.format(what, self.__devices))
+
+    def compute_log_partition_function(self, num_chains=1000, num_temperatures=1000, sweeps_per_temperature=1, seed=0, base='profile',
+                                       pseudocount=None):
+        """log Z = log sum_s exp(E(s)) of the mean-field model (E as in compute_sequence_energies) by annealed importance
+        sampling on the GPU: num_chains chains start from the independent-site base model and anneal through beta_k = k / K
+        (K = num_temperatures) with sweeps_per_temperature Gibbs sweeps per intermediate temperature.  base: 'profile' (log of
+        the alignment's weighted single-site frequencies, regularised by (1 - lambda) f + lambda / q, lambda = pseudocount or
+        1 / Meff), 'fields' (the model's own fields, 0 on the gap state) or an L x q array.
+        -> {'log_z', 'log_z_stderr', 'ess', 'log_z_base', 'log_weights'}"""
+        self._one_gpu('compute_log_partition_function')
+        opts = _potts.ais_options(num_chains, num_temperatures, sweeps_per_temperature, seed, pseudocount, MeanFieldDCAException)
+        h0 = _potts.ais_base(base, self.__X0, self.__sequences_weight, self.__sequences_len, self.__num_site_states,
+                             opts['pseudocount'], MeanFieldDCAException)
+        logger.info('\n\tlog Z by annealed importance sampling: {} chains, {} temperatures, {} sweeps per temperature'.format(
+            opts['num_chains'], opts['num_temperatures'], opts['sweeps_per_temperature']))
+        return _potts.log_partition_function(
+            lambda n, K, s, sd, h: self._with_couplings(lambda: self.__ctx.mf_ais(n, K, sweeps_per_temperature=s, seed=sd, base_fields=h)),
+            opts, h0)
+
+    def compute_sequence_log_probabilities(self, sequences=None, log_z=None, **ais_kwargs):
+        """log P(s) = E(s) - log Z -> float64[n] (sequences as in compute_sequence_energies).  log_z None: estimated first by
+        compute_log_partition_function(**ais_kwargs)."""
+        self._one_gpu('compute_sequence_log_probabilities')
+        if log_z is None:
+            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
+        return self.compute_sequence_energies(sequences) - float(log_z)
+
+    def compute_log_likelihood(self, log_z=None, **ais_kwargs):
+        """(sum_n w_n E(s_n)) / Meff - log Z over the alignment and weights of this instance -> float.  log_z None: estimated
+        first by compute_log_partition_function(**ais_kwargs)."""
+        self._one_gpu('compute_log_likelihood')
+        if log_z is None:
+            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
+        E = self._with_couplings(lambda: self.__ctx.mf_energies(self.__X0))
+        return _potts.log_likelihood(E, self.__sequences_weight, self.__effective_num_sequences, log_z)
 
     def shift_couplings(self, couplings_ij):
         """meanfield_dca.py:636-658 (zero-sum gauge of one block)."""

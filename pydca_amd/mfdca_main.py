@@ -20,7 +20,8 @@ def configure_logging():
 
 def execute_from_command_line(msa_file=None, biomolecule=None, seqid=None, pseudocount=None, the_command=None,
                               refseq_file=None, verbose=False, output_dir=None, apc=False, ranked_by=None,
-                              linear_dist=None, num_site_pairs=None, device=0, devices=None, query_file=None, wildtype_file=None, sampling=None):
+                              linear_dist=None, num_site_pairs=None, device=0, devices=None, query_file=None, wildtype_file=None, sampling=None,
+                              ais=None):
     if verbose:
         configure_logging()
     mfdca_instance = meanfield_dca.MeanFieldDCA(msa_file, biomolecule, pseudocount=pseudocount, seqid=seqid, device=device, devices=devices)
@@ -36,7 +37,8 @@ def execute_from_command_line(msa_file=None, biomolecule=None, seqid=None, pseud
     if the_command.strip() in _potts.POTTS_SUBCOMMANDS:
         bio = _lib.DCA_BIOMOLECULE_PROTEIN if mfdca_instance.num_site_states == 21 else _lib.DCA_BIOMOLECULE_RNA
         return _potts.run_subcommand(mfdca_instance, the_command.strip(), 'MFDCA', msa_file, output_dir, param_metadata, bio, 1,
-                                     meanfield_dca.MeanFieldDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling)
+                                     meanfield_dca.MeanFieldDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling,
+                                     ais=ais)
     if the_command.strip() == 'compute_params':
         fields, couplings = mfdca_instance.compute_params(seqbackmapper=seqbackmapper, ranked_by=ranked_by, linear_dist=linear_dist,
                                                           num_site_pairs=num_site_pairs)
@@ -112,6 +114,8 @@ def run_meanfield_dca(argv=None):
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence (addition)')
         if name == 'sample_sequences':
             _potts.add_sampling_arguments(p)
+        if name == 'compute_log_likelihood':
+            _potts.add_ais_arguments(p)
         p.add_argument('--device', type=int, default=0, help='GPU index (addition)')
         p.add_argument('--devices', help='comma-separated GPU indices: one rank per GPU for the sequence weights and the pair counts '
                        '(ONE all-reduce of the counts over RCCL); the inverse and the scores run on the first (addition)')
@@ -128,7 +132,8 @@ def run_meanfield_dca(argv=None):
         ranked_by=args.get('ranked_by'), linear_dist=args.get('linear_dist'), num_site_pairs=args.get('num_site_pairs'),
         device=args.get('device'), devices=args.get('devices'), query_file=args.get('query_file'),
         wildtype_file=args.get('wildtype_file'),
-        sampling={k: args.get(k) for k in ('num_sequences', 'num_sweeps', 'seed', 'temperature', 'initial_file')})
+        sampling={k: args.get(k) for k in ('num_sequences', 'num_sweeps', 'seed', 'temperature', 'initial_file')},
+        ais={k: args.get(k) for k in _potts.AIS_OPTIONS})
 
 
 if __name__ == '__main__':

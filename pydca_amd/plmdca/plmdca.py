@@ -405,6 +405,49 @@ class PlmDCA:
             logger.info('\n\tLast iteration: eps_h {:.3g}, eps_J {:.3g}, pearson {:.4f}'.format(*history[-1]))
         return {'history': history, 'fields_and_couplings': ctx.plm_get_x(dt)}
 
+    # ---- normalised probabilities: log Z by annealed importance sampling (no reference counterpart)
+    def _one_gpu(self, what):
+        if self.__devices and len(self.__devices) > 1:
+            logger.error('\n\t{} runs on one GPU; devices={}'.format(what, self.__devices))
+            raise PlmDCAException('{} runs on one GPU, not on devices {}'.format(what, self.__devices))
+
+    def compute_log_partition_function(self, num_chains=1000, num_temperatures=1000, sweeps_per_temperature=1, seed=0, base='profile',
+                                       pseudocount=None):
+        """log Z = log sum_s exp(E(s)) of the fitted model (E as in compute_sequence_energies; after fit_boltzmann the refined
+        model) by annealed importance sampling on the GPU: num_chains chains start from the independent-site base model and
+        anneal through beta_k = k / K (K = num_temperatures) with sweeps_per_temperature Gibbs sweeps per intermediate
+        temperature.  base: 'profile' (log of the training alignment's weighted single-site frequencies, regularised by
+        (1 - lambda) f + lambda / q, lambda = pseudocount or 1 / Meff), 'fields' (the model's own fields) or an L x q array.
+        -> {'log_z', 'log_z_stderr', 'ess', 'log_z_base', 'log_weights'}"""
+        self._one_gpu('compute_log_partition_function')
+        opts = _potts.ais_options(num_chains, num_temperatures, sweeps_per_temperature, seed, pseudocount, PlmDCAException)
+        ctx = self._fitted_context()
+        X = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)[0] if isinstance(base, str) and base == 'profile' else None
+        h0 = _potts.ais_base(base, X, ctx.weights() if X is not None else None, self.__seqs_len, self.__num_site_states,
+                             opts['pseudocount'], PlmDCAException)
+        logger.info('\n\tlog Z by annealed importance sampling: {} chains, {} temperatures, {} sweeps per temperature'.format(
+            opts['num_chains'], opts['num_temperatures'], opts['sweeps_per_temperature']))
+        return _potts.log_partition_function(
+            lambda n, K, s, sd, h: ctx.plm_ais(n, K, sweeps_per_temperature=s, seed=sd, base_fields=h), opts, h0)
+
+    def compute_sequence_log_probabilities(self, sequences=None, log_z=None, **ais_kwargs):
+        """log P(s) = E(s) - log Z -> float64[n] (sequences as in compute_sequence_energies).  log_z None: estimated first by
+        compute_log_partition_function(**ais_kwargs)."""
+        self._one_gpu('compute_sequence_log_probabilities')
+        if log_z is None:
+            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
+        return self.compute_sequence_energies(sequences) - float(log_z)
+
+    def compute_log_likelihood(self, log_z=None, **ais_kwargs):
+        """(sum_n w_n E(s_n)) / Meff - log Z over the alignment and weights of the fit -> float.  log_z None: estimated first
+        by compute_log_partition_function(**ais_kwargs)."""
+        self._one_gpu('compute_log_likelihood')
+        if log_z is None:
+            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
+        ctx = self._fitted_context()
+        X = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)[0]
+        return _potts.log_likelihood(ctx.plm_energies(X), ctx.weights(), ctx.meff(), log_z)
+
     def compute_seqs_weight(self):
         """plmdca.py:565-591: weights of the PYTHON reader's alignment (float64 comparison,
         plmdca/msa_numerics.py:13-49), computed on the device; remembered with their sum like the

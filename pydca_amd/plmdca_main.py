@@ -23,7 +23,7 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
                               lambda_J=None, max_iterations=None, apc=False, verbose=False, output_dir=None,
                               num_threads=None, ranked_by=None, linear_dist=None, num_site_pairs=None, device=0,
                               exact_gradient=False, precision=32, devices=None, query_file=None, wildtype_file=None, sampling=None,
-                              boltzmann=None):
+                              boltzmann=None, ais=None):
     if verbose:
         configure_logging()
     plmdca_instance = plmdca.PlmDCA(msa_file, biomolecule, seqid=seqid, lambda_h=lambda_h, lambda_J=lambda_J,
@@ -35,7 +35,8 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
         return _potts.run_subcommand(plmdca_instance, the_command, 'PLMDCA', msa_file, output_dir,
                                      dca_utilities.plmdca_param_metadata(plmdca_instance),
                                      _lib.DCA_BIOMOLECULE_PROTEIN if plmdca_instance.biomolecule == 'PROTEIN' else _lib.DCA_BIOMOLECULE_RNA, 0,
-                                     plmdca.PlmDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling)
+                                     plmdca.PlmDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling,
+                                     ais=ais)
     if the_command == BOLTZMANN_SUBCOMMAND:
         if not output_dir:
             output_dir = 'PLMDCA_output_' + os.path.splitext(os.path.basename(msa_file))[0]
@@ -116,6 +117,8 @@ def run_plm_dca(argv=None):
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence (addition)')
         if name == 'sample_sequences':
             _potts.add_sampling_arguments(p)
+        if name == 'compute_log_likelihood':
+            _potts.add_ais_arguments(p)
         if name == BOLTZMANN_SUBCOMMAND:
             _potts.add_boltzmann_arguments(p)
         p.add_argument('--output_dir')
@@ -141,7 +144,8 @@ def run_plm_dca(argv=None):
         device=args.get('device'), exact_gradient=args.get('exact_gradient'), precision=args.get('precision'),
         devices=args.get('devices'), query_file=args.get('query_file'), wildtype_file=args.get('wildtype_file'),
         sampling={k: args.get(k) for k in ('num_sequences', 'num_sweeps', 'seed', 'temperature', 'initial_file')},
-        boltzmann={k: args.get(k) for k in _potts.BOLTZMANN_OPTIONS})
+        boltzmann={k: args.get(k) for k in _potts.BOLTZMANN_OPTIONS},
+        ais={k: args.get(k) for k in _potts.AIS_OPTIONS})
 
 
 if __name__ == '__main__':
