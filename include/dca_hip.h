@@ -319,6 +319,21 @@ int dca_plm_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out
  *   = h_i(a) - h_i(w_i) + sum_{j != i} [J_ij(a, w_j) - J_ij(w_i, w_j)]
  * for every site i and every state a (gap included), summed in double over ascending j; dE[i*q + w_i] = 0.0 exactly. */
 int dca_plm_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out /* L*q */);
+/* Site conditionals and pseudo-log-likelihoods of n query sequences X (n x L codes < q, gap = q-1; host) under the current x
+ * (h and J exactly as dca_plm_energies defines them, gap state included):
+ *   u_i(a) = h_i(a) + sum_{j != i} J_ij(a, s_j)      (J_ij for i > j is J_ji transposed)
+ *   m_i = max_b u_i(b),  Z_i = sum_b exp(u_i(b) - m_i) (ascending b),  cond[i][a] = (u_i(a) - m_i) - log Z_i = log P(s_i = a | s_-i)
+ *   site[i] = cond[i][s_i],  PLL(s) = sum_i site[i] (ascending i).
+ * Every term is widened to double and summed in double without contraction: h_i(a) first, then j ascending; the order depends
+ * on (L, q, precision) alone.  A sequence's outputs have the same bits whatever n, its position among the queries, the passes
+ * the call splits the queries into, or the call.  Outputs (host): pll_out[n]; site_out[n*L] (row n, site i at n*L + i) and
+ * cond_out[n*L*q] (at (n*L + i)*q + a) when not NULL.  The alignment, the weights, x, g and the optimiser state are not
+ * touched; an L-BFGS or Boltzmann-learning run in progress is allowed.  n == 0 is DCA_OK; a code >= q is DCA_ERR_ARG;
+ * DCA_ERR_STATE before dca_plm_configure.  Column strips: collective, like dca_plm_energies.  This is the true PLL: with
+ * carry_mode CARRY_EXACT and no regulariser, the fx of dca_plm_gradient is -sum_n w_n PLL(s_n) over the context's alignment;
+ * the other carry modes differ from it by design.  Profiling tag "pll".  No reference counterpart. */
+int dca_plm_pseudo_likelihood(dca_ctx* ctx, const uint8_t* X, int n, double* pll_out /* n */, double* site_out /* n*L or NULL */,
+                              double* cond_out /* n*L*q or NULL */);
 /* Systematic-scan Gibbs sampling of n independent chains from P(s) ~ exp(beta * E(s)) under the current x (E as in
  * dca_plm_energies).  One sweep visits sites i = 0 .. L-1 in order; at site i a chain forms u_i(a) = h_i(a) + sum_{j != i} J(a, s_j)
  * for every state a < q (gap included; every term in double, in an order fixed by (L, q, precision)), sets
@@ -469,6 +484,10 @@ int dca_mf_fields(dca_ctx* ctx, double* fields_out);
  * dca_mf_couplings. */
 int dca_mf_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out);
 int dca_mf_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out /* L*q */);
+/* dca_plm_pseudo_likelihood under the mean-field model (J, h as in dca_mf_energies; zero on the gap state).  Same formulas,
+ * order, determinism and argument checks; DCA_ERR_STATE before dca_mf_couplings. */
+int dca_mf_pseudo_likelihood(dca_ctx* ctx, const uint8_t* X, int n, double* pll_out /* n */, double* site_out /* n*L or NULL */,
+                             double* cond_out /* n*L*q or NULL */);
 /* dca_plm_sample under the mean-field model (J, h as in dca_mf_energies; zero on the gap state).  Same rule, RNG layout,
  * determinism and argument checks; DCA_ERR_STATE before dca_mf_couplings. */
 int dca_mf_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
@@ -500,7 +519,7 @@ int dca_spd_inverse(dca_ctx* ctx, const double* A, int n, double* Ainv_out);
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
- * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "sample",
+ * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample",
  * "bm_stats", "ais"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it

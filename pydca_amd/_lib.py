@@ -131,6 +131,8 @@ def lib():
         "dca_plm_mutation_scan": (i, [vp, vp, vp]),
         "dca_mf_energies": (i, [vp, vp, i, vp]),
         "dca_mf_mutation_scan": (i, [vp, vp, vp]),
+        "dca_plm_pseudo_likelihood": (i, [vp, vp, i, vp, vp, vp]),
+        "dca_mf_pseudo_likelihood": (i, [vp, vp, i, vp, vp, vp]),
         "dca_plm_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
         "dca_mf_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
         "dca_philox4x32_10": (i, [vp, vp, vp]),
@@ -182,6 +184,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_plm_lbfgs_begin", "dca_plm_lbfgs_iterate", "dca_plm_lbfgs_end", "dca_plm_scores", "dca_plm_di_scores",
            "dca_mf_di_scores", "dca_plm_pair_couplings", "dca_mf_fields", "dca_mf_pair_couplings",
            "dca_encode_sequences", "dca_plm_energies", "dca_plm_mutation_scan", "dca_mf_energies", "dca_mf_mutation_scan",
+           "dca_plm_pseudo_likelihood", "dca_mf_pseudo_likelihood",
            "dca_plm_sample", "dca_mf_sample", "dca_philox4x32_10",
            "dca_plm_bm_begin", "dca_plm_bm_iterate", "dca_plm_bm_freqs", "dca_plm_bm_chains", "dca_plm_bm_end",
            "dca_plm_ais", "dca_mf_ais", "dca_ais_estimate",
@@ -658,6 +661,26 @@ class Context:
 
     def mf_mutation_scan(self, wildtype):
         return self._mutation_scan(self._l.dca_mf_mutation_scan, wildtype)
+
+    # ---- site conditionals and pseudo-log-likelihoods (pll.hip): X uint8[n, L] codes < q -> pll float64[n], or a tuple with
+    # site float64[n, L] and / or cond float64[n, L, q] (log P(s_i = a | s_-i))
+    def _pseudo_likelihood(self, fn, X, per_site, conditionals):
+        X = np.ascontiguousarray(X, dtype=np.uint8).reshape(-1, self.L)
+        n = X.shape[0]
+        pll = np.zeros(n, dtype=np.float64)
+        site = np.zeros((n, self.L), dtype=np.float64) if per_site else None
+        cond = np.zeros((n, self.L, self.q), dtype=np.float64) if conditionals else None
+        check(fn(self._h, _ptr(X), int(n), _ptr(pll), None if site is None or not n else _ptr(site),
+                 None if cond is None or not n else _ptr(cond)))
+        if not per_site and not conditionals:
+            return pll
+        return (pll,) + tuple(v for v in (site, cond) if v is not None)
+
+    def plm_pseudo_likelihood(self, X, per_site=False, conditionals=False):
+        return self._pseudo_likelihood(self._l.dca_plm_pseudo_likelihood, X, per_site, conditionals)
+
+    def mf_pseudo_likelihood(self, X, per_site=False, conditionals=False):
+        return self._pseudo_likelihood(self._l.dca_mf_pseudo_likelihood, X, per_site, conditionals)
 
     # ---- Gibbs sampling (sample.hip): n chains, `sweeps` systematic sweeps -> uint8[n, L] codes
     def _sample(self, fn, n, sweeps, seed, beta, initial, first_chain, first_sweep):

@@ -130,7 +130,28 @@ def log_likelihood(energies, weights, meff, log_z):
     return float(np.dot(np.asarray(weights, dtype=np.float64), np.asarray(energies, dtype=np.float64))) / float(meff) - float(log_z)
 
 
-POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences', 'compute_log_likelihood')
+POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences', 'compute_log_likelihood',
+                     'compute_pseudo_log_likelihood')
+
+
+def pll_flag(per_site, exc_type):
+    """per_site of compute_sequence_pseudo_log_likelihoods: a bool (host check, before any device work)."""
+    if not isinstance(per_site, (bool, np.bool_)):
+        raise exc_type('per_site must be True or False, not {!r}'.format(per_site))
+    return bool(per_site)
+
+
+def single_query(sequences, exc_type):
+    """sequences of compute_conditional_log_probabilities -> True for one aligned string (the result drops its first axis),
+    False for a FASTA path or a list of aligned strings."""
+    if sequences is None:
+        raise exc_type('compute_conditional_log_probabilities needs sequences: an aligned string, a list of them or a FASTA file')
+    return isinstance(sequences, str) and not os.path.isfile(sequences)
+
+
+def pseudo_log_likelihood(plls, weights, meff):
+    """(sum_n w_n PLL(s_n)) / Meff"""
+    return float(np.dot(np.asarray(weights, dtype=np.float64), np.asarray(plls, dtype=np.float64))) / float(meff)
 
 
 def add_sampling_arguments(p):
@@ -176,9 +197,10 @@ def run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, opts):
 
 def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata, biomolecule, table, exc_type,
                    query_file=None, wildtype_file=None, sampling=None, ais=None):
-    """compute_energies / compute_mutation_effects / sample_sequences of the plmdca and mfdca command lines -> the path of
-    the file written: <output_dir>/<prefix>_energies_<alignment base>.txt, <prefix>_mutation_effects_<alignment base>.txt
-    or <prefix>_samples_<alignment base>.fa.  sampling: the sample_sequences options (num_sequences, num_sweeps, seed,
+    """compute_energies / compute_mutation_effects / sample_sequences / compute_pseudo_log_likelihood of the plmdca and mfdca
+    command lines -> the path of the file written: <output_dir>/<prefix>_energies_<alignment base>.txt,
+    <prefix>_mutation_effects_<alignment base>.txt, <prefix>_samples_<alignment base>.fa or
+    <prefix>_pseudo_log_likelihoods_<alignment base>.txt.  sampling: the sample_sequences options (num_sequences, num_sweeps, seed,
     temperature, initial_file)."""
     from .dca_utilities import dca_utilities
     if the_command == 'compute_log_likelihood':
@@ -198,6 +220,12 @@ def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata
         energies = instance.compute_sequence_energies(seqs) if seqs else []
         path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_samples_', postfix='.fa')
         dca_utilities.write_sampled_sequences(path, seqs, energies)
+        return path
+    if the_command == 'compute_pseudo_log_likelihood':
+        plls = instance.compute_sequence_pseudo_log_likelihoods(query_file)
+        weighted = None if query_file else instance.compute_pseudo_log_likelihood()
+        path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_pseudo_log_likelihoods_', postfix='.txt')
+        dca_utilities.write_pseudo_log_likelihoods(path, plls, metadata=metadata, query_file=query_file or msa_file, weighted=weighted)
         return path
     if the_command == 'compute_energies':
         energies = instance.compute_sequence_energies(query_file)

@@ -513,6 +513,13 @@ int dca_plm_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out)
     if (!wildtype || !dE_out) return DCA_ERR_ARG;
     return ctx->plm->mutation_scan(wildtype, dE_out);
 }
+int dca_plm_pseudo_likelihood(dca_ctx* ctx, const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    if (n < 0 || (n > 0 && (!X || !pll_out))) return DCA_ERR_ARG;
+    return ctx->plm->pseudo_likelihood(X, n, pll_out, site_out, cond_out);
+}
 int dca_plm_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                    const uint8_t* initial, uint8_t* out)
 {
@@ -690,6 +697,13 @@ int dca_mf_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out)
     DCA_TRY(need_mf(ctx));
     if (!wildtype || !dE_out) return DCA_ERR_ARG;
     return dca_mf_engine_mutation_scan(ctx->mf, wildtype, dE_out);
+}
+int dca_mf_pseudo_likelihood(dca_ctx* ctx, const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_mf(ctx));
+    if (n < 0 || (n > 0 && (!X || !pll_out))) return DCA_ERR_ARG;
+    return dca_mf_engine_pseudo_likelihood(ctx->mf, X, n, pll_out, site_out, cond_out);
 }
 int dca_mf_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                   const uint8_t* initial, uint8_t* out)

@@ -170,6 +170,7 @@ struct PlmEngineBase {
     virtual int pair_couplings(const int* pairs, int npairs, int shift, double* out) = 0;
     virtual int energies(const uint8_t* X, int n, double* out) = 0;            // energy.hip on the current x
     virtual int mutation_scan(const uint8_t* wildtype, double* out) = 0;
+    virtual int pseudo_likelihood(const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out) = 0;   // pll.hip
     virtual int sample(int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                        const uint8_t* initial, uint8_t* out) = 0;                  // sample.hip on the current x
     // the device x a Boltzmann-learning run updates in place; DCA_ERR_STATE (with the reason) unconfigured, during an L-BFGS
@@ -206,6 +207,11 @@ int dca_potts_energies(dca_ctx* ctx, const void* src, int src_kind, int dtype, c
                        const uint8_t* X, int n, double* out);
 int dca_potts_mutation_scan(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
                             const uint8_t* wildtype, double* out /* L*q */);
+
+// ---- pll.hip : site conditionals and pseudo-log-likelihoods of host query rows under the same sources (dca_plm_pseudo_likelihood
+// semantics).  site_out (n*L) and cond_out (n*L*q) may be NULL; all outputs on the host.
+int dca_potts_pseudo_likelihood(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
+                                const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out);
 
 // The pair stage of dca_potts_energies on device codes QT[s * NqS + k] (k < nq, NqS a multiple of 128): slab g of query k at
 // dSlabs[g * NqS + k], g < dca_energy_slab_count(L, q, dtype).  E(k) = sum_i h_i (ascending i) + sum_g slab (ascending g) is then
@@ -292,6 +298,7 @@ void dca_mf_engine_invalidate(MfEngine*);      // weights changed: counts, frequ
 int dca_mf_engine_pair_couplings(MfEngine*, const int* pairs, int npairs, int shift, double* out);
 int dca_mf_engine_energies(MfEngine*, const uint8_t* X, int n, double* out);
 int dca_mf_engine_mutation_scan(MfEngine*, const uint8_t* wildtype, double* out);
+int dca_mf_engine_pseudo_likelihood(MfEngine*, const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out);
 // data statistics of a Boltzmann-learning run from this engine's weighted counts (dca_plm_bm_begin): device outputs
 // fi (L*q) = (1 - lambda) * f_i + lambda / q and fij (pairs*q*q, pair order, gap included) = (1 - lambda) * f_ij + lambda / q^2
 int dca_mf_engine_bm_freqs(MfEngine*, double lambda, double* dFi, double* dFij);

@@ -657,6 +657,16 @@ int dca_mf_engine_mutation_scan(MfEngine* m, const uint8_t* wildtype, double* ou
     return rc;
 }
 
+int dca_mf_engine_pseudo_likelihood(MfEngine* m, const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out)
+{
+    double* dH = nullptr;
+    DCA_TRY(mf_fields_device(m, &dH));
+    const int rc = dca_potts_pseudo_likelihood(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, X, n, pll_out, site_out, cond_out);
+    hipStreamSynchronize(m->ctx->stream);
+    dca_dev_free(dH);
+    return rc;
+}
+
 int dca_mf_engine_sample(MfEngine* m, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                          const uint8_t* initial, uint8_t* out)
 {

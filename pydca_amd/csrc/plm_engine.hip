@@ -2563,6 +2563,13 @@ struct PlmEngine : PlmEngineBase {
         if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
         return dca_potts_mutation_scan(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, wildtype, out);
     }
+    // site conditionals and pseudo-log-likelihoods of the current x (pll.hip); column strips gather x first, as energies() does
+    int pseudo_likelihood(const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out) override
+    {
+        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
+        if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
+        return dca_potts_pseudo_likelihood(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, X, n, pll_out, site_out, cond_out);
+    }
     // Gibbs samples of the current x (sample.hip); column strips gather x first, as energies() does
     int sample(int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta, const uint8_t* initial,
                uint8_t* out) override

@@ -94,6 +94,20 @@ def write_sequence_energies(file_name, energies, metadata=None, query_file=None)
     _stream(file_name, header, rows, 'sequence energies')
 
 
+def write_pseudo_log_likelihoods(file_name, plls, metadata=None, query_file=None, weighted=None):
+    """One row per query record: its number (1-based, input order) and its pseudo-log-likelihood PLL(s) = sum_i log P(s_i | s_-i);
+    weighted (the training records' sum_n w_n PLL(s_n) / Meff) adds a header line (no reference counterpart)."""
+    header = [_RULE] + list(metadata or [])
+    if query_file:
+        header.append('#\tQuery sequences: {}'.format(query_file))
+    if weighted is not None:
+        header.append('#\tWeighted pseudo-log-likelihood per effective sequence: {}'.format('%.17g' % float(weighted)))
+    header += ['# The First column is the record number (1-based) of the query sequence and the',
+               '# Second its pseudo-log-likelihood PLL(s) = sum_i log P(s_i | s_-i) under the model', _RULE]
+    rows = ('{0:<7} {1}'.format(k + 1, '%.17g' % float(v)) for k, v in enumerate(plls))
+    _stream(file_name, header, rows, 'pseudo-log-likelihoods')
+
+
 def write_mutation_effects(file_name, dE, wildtype_letters, state_letters, metadata=None, wildtype_file=None):
     """One row per (site, state), site-major: site (1-based), wild-type letter, mutant letter and
     dE = E(mutant) - E(wild type) (no reference counterpart)."""

@@ -348,6 +348,40 @@ class MeanFieldDCA:
         E = self._with_couplings(lambda: self.__ctx.mf_energies(self.__X0))
         return _potts.log_likelihood(E, self.__sequences_weight, self.__effective_num_sequences, log_z)
 
+    # ---- pseudo-log-likelihoods (no reference counterpart)
+    def _query(self, sequences):
+        src = self.__msa if sequences is None else sequences
+        bio = _lib.DCA_BIOMOLECULE_PROTEIN if self.__num_site_states == 21 else _lib.DCA_BIOMOLECULE_RNA
+        return _potts.query_codes(src, bio, self.__sequences_len, 1, MeanFieldDCAException)
+
+    def compute_sequence_pseudo_log_likelihoods(self, sequences=None, per_site=False):
+        """PLL(s) = sum_i log P(s_i | s_-i) of the mean-field model (J the couplings, h the fields of compute_fields, both
+        zero on the gap state), log P(s_i = a | s_-i) = u_i(a) - log sum_b exp u_i(b), u_i(a) = h_i(a) + sum_{j != i}
+        J_ij(a, s_j) -> float64[n], or (float64[n], float64[n, L] of log P(s_i | s_-i)) with per_site.  sequences: as in
+        compute_sequence_energies.  This is the true pseudo-log-likelihood of the model."""
+        per_site = _potts.pll_flag(per_site, MeanFieldDCAException)
+        self._one_gpu('compute_sequence_pseudo_log_likelihoods')
+        X = self._query(sequences)
+        logger.info('\n\tPseudo-log-likelihoods of {} sequences'.format(X.shape[0]))
+        return self._with_couplings(lambda: self.__ctx.mf_pseudo_likelihood(X, per_site=per_site))
+
+    def compute_conditional_log_probabilities(self, sequences):
+        """log P(s_i = a | s_-i) for every site i and state a (gap last) of each sequence (as in
+        compute_sequence_pseudo_log_likelihoods) -> float64[n, L, q], or float64[L, q] for a single aligned string.
+        sequences: an aligned string, a list of aligned strings or a FASTA path."""
+        single = _potts.single_query(sequences, MeanFieldDCAException)
+        self._one_gpu('compute_conditional_log_probabilities')
+        X = self._query([sequences] if single else sequences)
+        _pll, cond = self._with_couplings(lambda: self.__ctx.mf_pseudo_likelihood(X, conditionals=True))
+        return cond[0] if single else cond
+
+    def compute_pseudo_log_likelihood(self):
+        """(sum_n w_n PLL(s_n)) / Meff over the alignment and weights of this instance -> float: the pseudo-log-likelihood
+        per effective sequence (compute_sequence_pseudo_log_likelihoods), comparable with compute_log_likelihood."""
+        self._one_gpu('compute_pseudo_log_likelihood')
+        plls = self._with_couplings(lambda: self.__ctx.mf_pseudo_likelihood(self.__X0))
+        return _potts.pseudo_log_likelihood(plls, self.__sequences_weight, self.__effective_num_sequences)
+
     def shift_couplings(self, couplings_ij):
         """meanfield_dca.py:636-658 (zero-sum gauge of one block)."""
         qm1 = self.__num_site_states - 1

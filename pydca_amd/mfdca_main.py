@@ -108,7 +108,7 @@ def run_meanfield_dca(argv=None):
         p.add_argument('--verbose', action='store_true')
         if name not in _potts.POTTS_SUBCOMMANDS:
             p.add_argument('--apc', action='store_true')
-        if name == 'compute_energies':
+        if name in ('compute_energies', 'compute_pseudo_log_likelihood'):
             p.add_argument('--query_file', help='FASTA file of aligned query sequences (default: the records of msa_file) (addition)')
         if name == 'compute_mutation_effects':
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence (addition)')

@@ -448,6 +448,42 @@ class PlmDCA:
         X = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)[0]
         return _potts.log_likelihood(ctx.plm_energies(X), ctx.weights(), ctx.meff(), log_z)
 
+    # ---- pseudo-log-likelihoods (no reference counterpart)
+    def _query(self, sequences):
+        src = self.__msa_file if sequences is None else sequences
+        return _potts.query_codes(src, self.__biomolecule_int, self.__seqs_len, 0, PlmDCAException)
+
+    def compute_sequence_pseudo_log_likelihoods(self, sequences=None, per_site=False):
+        """PLL(s) = sum_i log P(s_i | s_-i) of the fitted parameters (after fit_boltzmann the refined model), with
+        log P(s_i = a | s_-i) = u_i(a) - log sum_b exp u_i(b), u_i(a) = h_i(a) + sum_{j != i} J_ij(a, s_j) (gap state included)
+        -> float64[n], or (float64[n], float64[n, L] of log P(s_i | s_-i)) with per_site.  sequences: as in
+        compute_sequence_energies.  This is the true pseudo-log-likelihood, not the fx the fit reports: under the reference's
+        carry-over of the gradient the fit's objective differs from it by design."""
+        per_site = _potts.pll_flag(per_site, PlmDCAException)
+        self._one_gpu('compute_sequence_pseudo_log_likelihoods')
+        X = self._query(sequences)
+        logger.info('\n\tPseudo-log-likelihoods of {} sequences'.format(X.shape[0]))
+        return self._fitted_context().plm_pseudo_likelihood(X, per_site=per_site)
+
+    def compute_conditional_log_probabilities(self, sequences):
+        """log P(s_i = a | s_-i) for every site i and state a (gap last) of each sequence (as in
+        compute_sequence_pseudo_log_likelihoods) -> float64[n, L, q], or float64[L, q] for a single aligned string.
+        sequences: an aligned string, a list of aligned strings or a FASTA path."""
+        single = _potts.single_query(sequences, PlmDCAException)
+        self._one_gpu('compute_conditional_log_probabilities')
+        X = self._query([sequences] if single else sequences)
+        _pll, cond = self._fitted_context().plm_pseudo_likelihood(X, conditionals=True)
+        return cond[0] if single else cond
+
+    def compute_pseudo_log_likelihood(self):
+        """(sum_n w_n PLL(s_n)) / Meff over the alignment and weights of the fit -> float: the unregularised
+        pseudo-log-likelihood per effective sequence (compute_sequence_pseudo_log_likelihoods), comparable with
+        compute_log_likelihood.  Not the fit's reported fx."""
+        self._one_gpu('compute_pseudo_log_likelihood')
+        ctx = self._fitted_context()
+        X = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)[0]
+        return _potts.pseudo_log_likelihood(ctx.plm_pseudo_likelihood(X), ctx.weights(), ctx.meff())
+
     def compute_seqs_weight(self):
         """plmdca.py:565-591: weights of the PYTHON reader's alignment (float64 comparison,
         plmdca/msa_numerics.py:13-49), computed on the device; remembered with their sum like the
