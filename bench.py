@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the plmDCA / mfDCA hot path on MI355X (contract: see the task prompt).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload D|C|E] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--workload D|C|E] [--dump-outputs DIR] [--full]
 
 A "step" is one L-BFGS iteration of plmDCA (line search included: ~1.0-1.2 objective +
 gradient evaluations) on the synthetic protein alignment L=500, N=50k, q=21 (config D of
 BASELINE.json / SURVEY.md section 8), lambda_h=1, lambda_J=50, seqid 0.8, resident in HBM.
 N>1: sequences are sharded over the ranks, every evaluation ends with one RCCL all-reduce
 of the gradient (strong scaling: total work fixed).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline (metric, value,
+unit, ms_per_step, ...) and what the timed steps measured on the way -- the roofline of the gather stage they bracket with HIP
+events.  --full adds everything that takes runs of its own: the stage clock pass and its per-kernel figures, the mfDCA chain
+and its rooflines, the float64 mode, the end-to-end command-line figures, config E beside D, the CPU baselines and, with
+several GPUs, rank 0 alone on its GPU.  The --no-* options leave one of these out of a --full run.
 
 --dump-outputs DIR writes what the timed path computed in its last timed step, as a caller receives it, to DIR/<name>.npy
 (float32 with --precision 32, float64 otherwise): plm_x and plm_g, the parameters and the gradient at them, and plm_lbfgs =
@@ -352,6 +358,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="D", choices=sorted(WORKLOADS))
     ap.add_argument("--precision", type=int, default=32, choices=(32, 64))
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need (see the module docstring); off by default")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-mfdca", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
@@ -359,12 +367,15 @@ def main():
     ap.add_argument("--no-modes", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0)
     ap.add_argument("--cpu-full", action="store_true",
-                    help="also time ONE full evaluation of the reference C++/OpenMP on all sequences (about a minute at config D) and report it beside the fit")
+                    help="also time ONE full evaluation of the reference C++/OpenMP on all sequences (about a minute at config D) and report it "
+                         "beside the fit; implies --full")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path computed in its last step to DIR/<name>.npy (see the module docstring)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.cpu_full:
+        args.full = True
     if args.dump_outputs and int(os.environ.get("RANK", "0")) == 0:
         for name in DUMP_NAMES:             # a file this run does not write must not be left from an earlier one
             if os.path.exists(dump_path(args.dump_outputs, name)):
@@ -626,8 +637,8 @@ def main():
     iterate(args.warmup)
     # The timed region carries HIP events around ONE stage only -- the roofline's kernel (the gather stage that dominates: scatter
     # at q = 21, logits on the site-pair alphabet of q = 5).  An event record costs the stream ~5 us; two per stage and seven stages
-    # per iteration were 5 % of config C's step and 4 % of E's (0.4 % of D's) -- the instrument, not the path.  The other stages are
-    # clocked over the same number of iterations right after the timed region (`kernel_clock_pass`).
+    # per iteration were 5 % of config C's step and 4 % of E's (0.4 % of D's) -- the instrument, not the path.  With --full the
+    # other stages are clocked over the same number of iterations right after the timed region (`kernel_clock_pass`).
     roof_stage = "plm_scatter" if q == 21 else "plm_logits"
     ctx.reset_kernel_times()
     st, dt, steps_done, evals = iterate(args.steps, lambda: ctx.set_profiling_only(roof_stage))
@@ -652,21 +663,24 @@ def main():
             write_dump(args.dump_outputs, "plm_lbfgs", np.array([st.fx, st.xnorm, st.gnorm, st.step, st.iterations, st.evaluations],
                                                                 dtype=np.float64))
         del x_last, g_last
-    # the same number of iterations again with every stage clocked (not part of `value`); the optimiser simply goes on
-    ctx.reset_kernel_times()
-    _, secs_clocked, steps_clocked, _ = iterate(args.steps, lambda: ctx.set_profiling(True))
-    clock_pass = {"steps": steps_clocked, "ms_per_step": secs_clocked / steps_clocked * 1e3,
-                  "what": "every stage bracketed with HIP events (14 event records per iteration); the timed region brackets only %s" % roof_stage}
-    ktimes = {tag: ctx.kernel_time(tag) for tag in ("plm_expand", "plm_logits", "plm_softmax", "plm_scatter", "plm_fold", "lbfgs_vec")}
-    if roof_time[1] > 0:
-        ktimes[roof_stage] = roof_time
+    clock_pass, steps_clocked = None, 0
+    ktimes = {roof_stage: roof_time}
+    if args.full:
+        # the same number of iterations again with every stage clocked (not part of `value`); the optimiser simply goes on
+        ctx.reset_kernel_times()
+        _, secs_clocked, steps_clocked, _ = iterate(args.steps, lambda: ctx.set_profiling(True))
+        clock_pass = {"steps": steps_clocked, "ms_per_step": secs_clocked / steps_clocked * 1e3,
+                      "what": "every stage bracketed with HIP events (14 event records per iteration); the timed region brackets only %s" % roof_stage}
+        ktimes = {tag: ctx.kernel_time(tag) for tag in ("plm_expand", "plm_logits", "plm_softmax", "plm_scatter", "plm_fold", "lbfgs_vec")}
+        if roof_time[1] > 0:
+            ktimes[roof_stage] = roof_time
     ctx.set_profiling(False)
 
     # The N = 1 point of the same run: rank 0 times the same K iterations on its GPU alone, in this
     # process group, while the other ranks wait -- the scaling curve's first point can be checked against BENCH without a
-    # second launch.  After the timed region; not part of `value`.
+    # second launch.  After the timed region, with --full; not part of `value`.
     single_gpu_same_run = None
-    if world > 1 and os.environ.get("DCA_BENCH_NO_SINGLE") != "1":
+    if world > 1 and args.full and os.environ.get("DCA_BENCH_NO_SINGLE") != "1":
         if rank == 0:
             c1 = _lib.Context(local_rank, _lib.DCA_F64 if args.precision == 64 else _lib.DCA_F32)
             c1.set_msa(X, q)
@@ -709,10 +723,11 @@ def main():
     model = gather_issue_model(q, args.precision)
     lds_bytes = {k: units * model[k]["lds_bytes"] for k in ("plm_logits", "plm_scatter")}
     # the roofline's kernel: the stage the timed region clocked (the longer of the two gather stages by construction); should the
-    # clock pass show the other one longer per launch, that one is reported -- from the clock pass, and said so
+    # clock pass (--full) show the other one longer per launch, that one is reported -- from the clock pass, and said so
     per_launch = lambda k: ktimes[k][0] / max(ktimes[k][1], 1)
-    dom = roof_stage if roof_stage in alg_bytes and ktimes[roof_stage][1] > 0 else max(alg_bytes, key=per_launch)
-    longest = max(alg_bytes, key=per_launch)
+    clocked = [k for k in alg_bytes if k in ktimes]
+    dom = roof_stage if roof_stage in alg_bytes and ktimes[roof_stage][1] > 0 else max(clocked, key=per_launch)
+    longest = max(clocked, key=per_launch)
     roof_measured_in = "timed region" if dom == roof_stage else "kernel clock pass"
     if longest != dom and per_launch(longest) > 1.05 * per_launch(dom):
         dom, roof_measured_in = longest, "kernel clock pass (the timed region clocked %s, which turned out shorter per launch)" % roof_stage
@@ -754,9 +769,9 @@ def main():
                 "hbm": hbm_view,
                 "onchip": {"bound": "lds", "achieved": lds_bytes[dom] / avg_s / 1e9, "peak": LDS_PEAK_GBS, "unit": "GB/s",
                            "frac": lds_bytes[dom] / avg_s / 1e9 / LDS_PEAK_GBS}}
-    # both gather kernels, each against the same roof
+    # both gather kernels (--full; a plain run clocked only the roofline's), each against the same roof
     roofline["per_kernel"] = {}
-    for k in alg_bytes:
+    for k in clocked:
         k_s = ktimes[k][0] / max(ktimes[k][1], 1) / 1e3
         if k_s > 0:
             roofline["per_kernel"][k] = {"avg_ms": k_s * 1e3, "valu_frac": sums * model[k]["adds"] / k_s / 1e12 / valu_peak,
@@ -807,8 +822,16 @@ def main():
         except (OSError, ValueError, KeyError):
             pass
 
-    if world == 1 and not args.no_mfdca:
-        # second half of the headline metric: mfDCA residue pairs/s, encoded MSA on host ->
+    if world == 1 and not args.no_mfdca and not args.full and args.dump_outputs:
+        # a plain run times no mfDCA chain, but --dump-outputs still writes its scores: one untimed pass, as a timed one of --full
+        mctx = _lib.Context(local_rank, _lib.DCA_F64)
+        mctx.set_msa(X, q)
+        mctx.compute_weights(0.8, _lib.DCA_F64)
+        write_dump(args.dump_outputs, "mfdca_scores", np.asarray(mctx.mf_run(0.5, True), dtype=np.float64))
+        mctx.close()
+
+    if world == 1 and not args.no_mfdca and args.full:
+        # the mfDCA leg (--full; not part of `value`): residue pairs/s, encoded MSA on host ->
         # FN_APC scores ranked on host (weights + counts + C + inverse + scoring + sort)
         # one untimed pass first (like the warm-up iterations of the plmDCA leg: first-use code
         # loading and allocator growth are not part of the metric), then three timed passes, each on a
@@ -889,7 +912,7 @@ def main():
         out["roofline_more"] = more
         mctx.close()
 
-    if world == 1 and args.precision == 32 and not args.no_modes:
+    if world == 1 and args.full and args.precision == 32 and not args.no_modes:
         # The two precisions of the product side by side, each with its MEASURED parity class.  north_star's tolerance
         # ("FN / DI within 1e-4 of the float64 CPU path, identical top-L") is protocol P3 of SURVEY 8c4; the float32 mode is the
         # reference's own arithmetic (lbfgs.h:50-62) and lands in the P4 regime after 100 iterations of an optimisation
@@ -900,19 +923,19 @@ def main():
         except Exception as exc:   # pragma: no cover
             out["modes"] = {"error": repr(exc)}
 
-    if world == 1 and not args.no_e2e:
+    if world == 1 and args.full and not args.no_e2e:
         try:
             out["e2e"] = end_to_end(X, L, q, lh, lJ, local_rank)
         except Exception as exc:   # pragma: no cover
             out["e2e"] = {"error": repr(exc)}
 
-    if world == 1 and args.workload == "D" and not args.no_rna:
+    if world == 1 and args.full and args.workload == "D" and not args.no_rna:
         try:
             out["workload_E"] = rna_workload_block(local_rank)
         except Exception as exc:   # pragma: no cover
             out["workload_E"] = {"error": repr(exc)}
 
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         sample = args.cpu_sample or max(200, min(N, int(4000 * (500.0 / L) ** 2 * (21.0 / q))))
         sample = min(sample, N)
         try:

@@ -669,7 +669,7 @@ def test_bench_two_process_selftest(mode):
     two = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert two.returncode == 0, two.stderr[-2000:]
     d2 = json.loads(two.stdout.strip().splitlines()[-1])
-    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--workload", "C",
+    one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--workload", "C", "--full",
                           "--no-cpu-baseline", "--no-mfdca", "--no-e2e"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert one.returncode == 0, one.stderr[-2000:]
     d1 = json.loads(one.stdout.strip().splitlines()[-1])
@@ -695,8 +695,8 @@ def test_bench_native_path_two_processes(scheme):
         env.pop(k, None)
     if scheme != "timed":
         env["DCA_BENCH_SCHEME"] = scheme
-    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--workload", "C"],
-                         env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    two = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--workload", "C",
+                          "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert two.returncode == 0, two.stderr[-3000:]
     d2 = json.loads(two.stdout.strip().splitlines()[-1])
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--workload", "C",
@@ -766,6 +766,22 @@ def test_bench_dump_outputs_are_what_the_timed_path_computed(tmp_path):
     m.compute_weights(0.8, _lib.DCA_F64)
     assert np.array_equal(D["mfdca_scores"], m.mf_run(0.5, True))
     m.close()
+
+
+def test_bench_plain_run_is_the_headline():
+    """A plain bench.py run times the steps and reports the headline with the roofline of the stage its timed region clocked;
+    what takes runs of its own (clock pass, mfDCA chain, float64 mode, end-to-end, CPU baseline) waits for --full."""
+    import json
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "C"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d = json.loads(p.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["roofline"]["kernel"] == "plm_scatter" and d["roofline"]["measured_over"] == "timed region"
+    assert d["roofline"]["launches"] >= 3 and list(d["kernels"]) == ["plm_scatter"] and d["kernel_clock_pass"] is None
+    assert not {"mfdca", "roofline_mf", "roofline_more", "modes", "e2e", "workload_E", "cpu_baseline"} & set(d)
 
 
 def test_msa_numerics_direct_information_functions():
