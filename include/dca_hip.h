@@ -515,11 +515,71 @@ int dca_mf_corr_from_freqs(dca_ctx* ctx, const double* reg_fi, const double* reg
 /* test hook / stage API: inverse of a host SPD matrix through the same device path */
 int dca_spd_inverse(dca_ctx* ctx, const double* A, int n, double* Ainv_out);
 
+/* ------------------------------------------------------------------ autoregressive model (arDCA)
+ * Trinquier et al., Nat. Commun. 12, 5800 (2021).  Sites are in model order: the column order of the context's alignment (a
+ * caller that wants another order permutes the columns before dca_set_msa).  x has the plm layout and size
+ * (dca_ar_num_params == dca_plm_num_params): fields h_l(b) at l*q + b, then one q x q block per pair k < l in pair order
+ * (0,1),(0,2)...,(1,2)..., element a*q + b = J_kl(a, b) with a the state of the EARLIER site k and b that of the later site l.
+ * All q states are used, the gap q-1 included; everything is float64.
+ *   u_l(b) = h_l(b) + sum_{k<l} J_kl(s_k, b)      (site 0: fields only)
+ *   m_l = max_b u_l(b),  Z_l = sum_b exp(u_l(b) - m_l) (ascending b),  cond_l(b) = (u_l(b) - m_l) - log Z_l = log P(s_l = b | s_<l)
+ *   log P(s) = sum_l cond_l(s_l) (ascending l)    -- exact: every conditional is normalised, no log Z is needed.
+ * u_l is summed in double without contraction: h_l(b) first, then k ascending.  P_nl(b) = exp(cond_l(b)) of sequence n.
+ * Objective of the fit, with W_n = w_n / sum_m w_m (the context's weights, dca_compute_weights / dca_set_weights):
+ *   f(x) = -sum_n W_n log P(s_n) + lambda_h sum h^2 + lambda_J sum J^2                  (no gauge is fixed; the L2 term makes
+ *   df/dh_l(b)    = sum_n W_n (P_nl(b) - [s_nl = b]) + 2 lambda_h h_l(b)                   the minimum unique)
+ *   df/dJ_kl(a,b) = sum_n W_n [s_nk = a] (P_nl(b) - [s_nl = b]) + 2 lambda_J J_kl(a, b)
+ * The sequences go through in passes that bound the device scratch (DCA_AR_PASS, a positive count, caps the pass size); the
+ * sums over n ascend within a pass and the pass results are added in ascending pass order, so fx and g depend on (N, L, q, pass
+ * size) and repeated calls give the same bits.  No float atomics.  Profiling tags "ar_logits", "ar_grad", "ar_sample".
+ *
+ * dca_ar_configure: lambdas finite and >= 0 (else DCA_ERR_ARG); DCA_ERR_STATE without an alignment or weights.  The first call
+ * creates the engine with x = 0; later calls keep x.  A change of the weights unconfigures the engine (x stays): gradient and
+ * fit answer DCA_ERR_STATE until the next dca_ar_configure.  The other entries need only x (DCA_ERR_STATE before the first
+ * configure).  dca_ar_release frees the engine; dca_set_msa and dca_destroy free it too. */
+#define DCA_AR_CONVERGED 0            /* |g| <= epsilon * max(1, |x|) */
+#define DCA_AR_MAX_ITERATIONS 1       /* max_iterations reached */
+#define DCA_AR_LINE_SEARCH_FAILED 2   /* the line search found no Wolfe point; x, fx and g are the last accepted point's */
+typedef struct {
+    int status;        /* DCA_AR_* */
+    int iterations;    /* accepted L-BFGS steps */
+    int evaluations;   /* objective/gradient evaluations, the initial one included */
+    double fx, gnorm;  /* at the returned x */
+    double seconds;
+} dca_ar_stats;
+int dca_ar_configure(dca_ctx* ctx, double lambda_h, double lambda_J);
+size_t dca_ar_num_params(int L, int q);
+int dca_ar_init_x(dca_ctx* ctx);                          /* x <- 0 */
+int dca_ar_set_x(dca_ctx* ctx, const double* x);
+int dca_ar_get_x(dca_ctx* ctx, double* x);
+/* fx (fx_out may be NULL) and g at the current x; dca_ar_get_g reads g of the last evaluation */
+int dca_ar_gradient(dca_ctx* ctx, double* fx_out);
+int dca_ar_get_g(dca_ctx* ctx, double* g);
+/* L-BFGS from the current x: memory m = 5, More-Thuente line search enforcing the strong Wolfe conditions (ftol 1e-4, gtol 0.9,
+ * at most 20 evaluations), first step 1/|g| along -g, then 1.  Stops when |g| <= epsilon * max(1, |x|) (checked before the first
+ * step too), after max_iterations accepted steps (0: evaluate only) or when the line search fails; stats_out (may be NULL) says
+ * which.  Only scalars cross to the host.  DCA_ERR_ARG: max_iterations < 0, epsilon < 0 or not finite. */
+int dca_ar_fit(dca_ctx* ctx, int max_iterations, double epsilon, dca_ar_stats* stats_out);
+/* log P(s) of n query rows X (n x L codes < q, model order; host) under the current x.  Outputs (host): logp[n]; site[n*L]
+ * (row n, site l at n*L + l: cond_l(s_l)) and cond[n*L*q] (at (n*L + l)*q + b) when not NULL.  A sequence's outputs have the
+ * same bits whatever n, its position or the passes; logp is the ascending sum of its site values.  The alignment, weights, x
+ * and g are not touched.  n == 0 is DCA_OK; a code >= q is DCA_ERR_ARG.  Profiling tag "ar_logits". */
+int dca_ar_log_probabilities(dca_ctx* ctx, const uint8_t* X, int n, double* logp, double* site, double* cond);
+/* Ancestral sampling of n exact, independent sequences under the current x.  Chain c = first_chain + k visits sites
+ * l = 0 .. L-1 once: u_l(b) = (((h_l(b) + S_0(b)) + S_1(b)) + S_2(b)) + S_3(b), S_w(b) = sum over k < l, k = w (mod 4), ascending
+ * k, of J_kl(s_k, b) (S_0 added onto h_l term by term); then dca_plm_sample's draw rule at beta = 1: p_b = exp(u_l(b) - m_l),
+ * T = sum_b p_b ascending, r = U * T, s_l = the smallest b whose ascending cumulative sum exceeds r (the largest b with p_b > 0 if
+ * rounding leaves none), U of Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (chain, 0, l, 3).  out: n x L
+ * codes (host, model order).  Chain k's codes depend only on x, seed and first_chain + k.  DCA_ERR_ARG: n < 0, out NULL with
+ * n > 0, L > 10240; n == 0 is DCA_OK.  Profiling tag "ar_sample". */
+int dca_ar_sample(dca_ctx* ctx, int n, uint64_t seed, uint64_t first_chain, uint8_t* out);
+int dca_ar_release(dca_ctx* ctx);
+
 /* ------------------------------------------------------------------ timing
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
- * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample",
+ * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "ar_logits", "ar_grad", "ar_sample",
  * "bm_stats", "ais"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it

@@ -48,6 +48,14 @@ class AisArgs(C.Structure):
                 ("seed", C.c_uint64), ("first_chain", C.c_uint64), ("base_fields", C.c_void_p)]
 
 
+class ArStats(C.Structure):
+    """dca_ar_stats (include/dca_hip.h)"""
+    _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("evaluations", C.c_int), ("fx", C.c_double), ("gnorm", C.c_double),
+                ("seconds", C.c_double)]
+
+
+AR_CONVERGED, AR_MAX_ITERATIONS, AR_LINE_SEARCH_FAILED = 0, 1, 2
+
 COMM_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
 COMM_ALL_REDUCE, COMM_REDUCE_SCATTER, COMM_ALL_GATHER = 0, 1, 2
 REDUCE_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
@@ -136,6 +144,17 @@ def lib():
         "dca_plm_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
         "dca_mf_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
         "dca_philox4x32_10": (i, [vp, vp, vp]),
+        "dca_ar_configure": (i, [vp, d, d]),
+        "dca_ar_num_params": (sz, [i, i]),
+        "dca_ar_init_x": (i, [vp]),
+        "dca_ar_set_x": (i, [vp, vp]),
+        "dca_ar_get_x": (i, [vp, vp]),
+        "dca_ar_gradient": (i, [vp, C.POINTER(d)]),
+        "dca_ar_get_g": (i, [vp, vp]),
+        "dca_ar_fit": (i, [vp, i, d, C.POINTER(ArStats)]),
+        "dca_ar_log_probabilities": (i, [vp, vp, i, vp, vp, vp]),
+        "dca_ar_sample": (i, [vp, i, C.c_uint64, C.c_uint64, vp]),
+        "dca_ar_release": (i, [vp]),
         "dca_plm_bm_begin": (i, [vp, C.POINTER(BmArgs)]),
         "dca_plm_bm_iterate": (i, [vp, i, vp]),
         "dca_plm_bm_freqs": (i, [vp, i, vp, vp]),
@@ -186,6 +205,8 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_encode_sequences", "dca_plm_energies", "dca_plm_mutation_scan", "dca_mf_energies", "dca_mf_mutation_scan",
            "dca_plm_pseudo_likelihood", "dca_mf_pseudo_likelihood",
            "dca_plm_sample", "dca_mf_sample", "dca_philox4x32_10",
+           "dca_ar_configure", "dca_ar_num_params", "dca_ar_init_x", "dca_ar_set_x", "dca_ar_get_x", "dca_ar_gradient", "dca_ar_get_g",
+           "dca_ar_fit", "dca_ar_log_probabilities", "dca_ar_sample", "dca_ar_release",
            "dca_plm_bm_begin", "dca_plm_bm_iterate", "dca_plm_bm_freqs", "dca_plm_bm_chains", "dca_plm_bm_end",
            "dca_plm_ais", "dca_mf_ais", "dca_ais_estimate",
            "dca_mf_single_site_freqs",
@@ -700,6 +721,59 @@ class Context:
 
     def mf_sample(self, n, sweeps, seed=0, beta=1.0, initial=None, first_chain=0, first_sweep=0):
         return self._sample(self._l.dca_mf_sample, n, sweeps, seed, beta, initial, first_chain, first_sweep)
+
+    # ---- autoregressive model (ardca.hip): float64 x in the plm layout, sites in the alignment's column order
+    def ar_configure(self, lambda_h, lambda_J):
+        check(self._l.dca_ar_configure(self._h, float(lambda_h), float(lambda_J)))
+
+    def ar_num_params(self):
+        return int(self._l.dca_ar_num_params(self.L, self.q))
+
+    def ar_init_x(self):
+        check(self._l.dca_ar_init_x(self._h))
+
+    def ar_set_x(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        if x.size != self.ar_num_params():
+            raise ValueError("x must hold %d values, not %d" % (self.ar_num_params(), x.size))
+        check(self._l.dca_ar_set_x(self._h, _ptr(x)))
+
+    def ar_get_x(self):
+        x = np.zeros(self.ar_num_params(), dtype=np.float64)
+        check(self._l.dca_ar_get_x(self._h, _ptr(x)))
+        return x
+
+    def ar_gradient(self):
+        fx = C.c_double(0)
+        check(self._l.dca_ar_gradient(self._h, C.byref(fx)))
+        return fx.value
+
+    def ar_get_g(self):
+        g = np.zeros(self.ar_num_params(), dtype=np.float64)
+        check(self._l.dca_ar_get_g(self._h, _ptr(g)))
+        return g
+
+    def ar_fit(self, max_iterations=1000, epsilon=1e-5):
+        """L-BFGS from the current x -> dict(status, iterations, evaluations, fx, gnorm, seconds); status AR_CONVERGED,
+        AR_MAX_ITERATIONS or AR_LINE_SEARCH_FAILED."""
+        st = ArStats()
+        check(self._l.dca_ar_fit(self._h, int(max_iterations), float(epsilon), C.byref(st)))
+        return {k: getattr(st, k) for k, _t in ArStats._fields_}
+
+    def ar_log_probabilities(self, X, per_site=False, conditionals=False):
+        """log P(s) of codes X (n x L, model order) -> float64[n], or a tuple with float64[n, L] site values (per_site) and
+        float64[n, L, q] conditionals (conditionals)."""
+        return self._pseudo_likelihood(self._l.dca_ar_log_probabilities, X, per_site, conditionals)
+
+    def ar_sample(self, n, seed=0, first_chain=0):
+        """n ancestral samples -> uint8[n, L] codes (model order)"""
+        n = int(n)
+        out = np.zeros((max(n, 0), self.L), dtype=np.uint8)
+        check(self._l.dca_ar_sample(self._h, n, int(seed), int(first_chain), _ptr(out)))
+        return out
+
+    def ar_release(self):
+        check(self._l.dca_ar_release(self._h))
 
     # ---- Boltzmann machine learning of x (boltzmann.hip): persistent chains on the device, records (eps_h, eps_J, pearson)
     def plm_bm_begin(self, chains, sweeps, equilibration_sweeps, seed=0, eta_h=0.0, eta_J=0.0, mu_h=0.0, mu_J=0.0,

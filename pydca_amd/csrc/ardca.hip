@@ -1,0 +1,1035 @@
+// Autoregressive Potts model (arDCA): fit, exact log-probabilities and ancestral sampling, all in float64.
+//   P(s) = prod_l P(s_l | s_<l),  P(s_l = b | s_<l) = exp u_l(b) / sum_c exp u_l(c),  u_l(b) = h_l(b) + sum_{k<l} J_kl(s_k, b)
+// with x in the plm layout (dca_plm_num_params): fields L*q first, then the q x q blocks of the pairs (k < l) in pair order,
+// element a*q + b = J_kl(a at the earlier site k, b at the later site l).  Sites are in model order (the alignment's columns).
+//
+// Objective (include/dca_hip.h): f(x) = -sum_n W_n sum_l log P(s_nl | s_n,<l) + lambda_h sum h^2 + lambda_J sum J^2, W_n = w_n / sum w.
+// One evaluation runs the sequences through in passes (bounded device scratch); per pass:
+//   ar_sites_kernel   site-major copy of the pass's codes, QT[l * NpS + n]
+//   ar_logits_kernel  ("ar_logits") u_l, log-softmax, the site values log P(s_nl | .) and the residual R_nl(b) = W_n (P_nl(b) - [s_nl = b])
+//   ar_finish_kernel  log P(s_n) = sum_l site (ascending l); ar_wsum_kernel: F_pass = sum_n W_n log P(s_n) (fixed tree)
+//   ar_field_kernel / ar_grad_kernel ("ar_grad")  G_h[l][b] = sum_n R_nl(b), G_kl[a][b] = sum_n [s_nk = a] R_nl(b), ascending n
+// and the pass results are added in ascending pass order; then g += 2 lambda x and fx = -(sum of F_pass) + lambda_h |h|^2 + lambda_J |J|^2.
+// No atomics anywhere: every element is summed in an order fixed by (N, L, q, pass size), so repeated calls give the same bits.
+//
+// Optimiser: L-BFGS (m = 5) on device vectors with the More-Thuente line search (strong Wolfe conditions, as plm_engine.hip's,
+// whose interval update is restated here); only scalars cross to the host.
+//
+// Sampler ("ar_sample"): chain c visits sites 0 .. L-1 once and draws s_l with sample.hip's rule at beta = 1 from
+// U = Philox(seed; chain, 0, site, 3).  DESIGN.md section 16 has the geometry and the measured numbers.
+#include "dca_internal.h"
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdlib>
+
+namespace {
+
+constexpr int kAThreads = 256;                     // logits: 4 waves
+constexpr int kAPerLane = 2;                       // queries per lane
+constexpr int kASeqBlock = kAThreads * kAPerLane;  // queries per logits workgroup
+constexpr int kAMaxCJ = 16;                        // blocks per chunk at most
+constexpr size_t kAChunkBudget = 16 * 1024;        // LDS per J chunk buffer (two of them)
+constexpr size_t kAPassBudget = 1ull << 30;        // device scratch of one pass
+constexpr int kGTile = 64;                         // sequences per staged tile of the coupling gradient
+constexpr size_t kGBlockBudget = 56 * 1024;        // LDS of the gradient blocks of one workgroup
+constexpr int kGMaxThreads = 512;
+constexpr int kSSlices = 4;                        // sampler: lanes per chain (k = w mod 4)
+constexpr int kSChainsPerWave = 64 / kSSlices;
+constexpr int kDotBlocks = 256;
+
+__device__ __forceinline__ size_t pair_index(int L, int i, int j)
+{
+    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
+}
+
+// site-major copy of n rows (row stride ld): QT[s * NpS + k], zero past n
+__global__ void ar_sites_kernel(const uint8_t* __restrict__ rows, size_t ld, int n, int L, int NpS, uint8_t* __restrict__ QT)
+{
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t >= (size_t)L * NpS) return;
+    const int s = (int)(t / NpS), k = (int)(t % NpS);
+    QT[t] = k < n ? rows[(size_t)k * ld + s] : 0;
+}
+
+template <int QM>
+constexpr int chunk_blocks() { return (int)(kAChunkBudget / (QM * QM * sizeof(double))) < kAMaxCJ ? (int)(kAChunkBudget / (QM * QM * sizeof(double))) : kAMaxCJ; }
+
+// grid (ceil(nq / 512), L): blockIdx.y = L - 1 - l, so the sites with the most terms are dispatched first.  LDS: two J chunk
+// buffers (CJ blocks of q x QM doubles: the block of the pair (k, l) as stored, rows padded to QM), then two code buffers
+// (CJ x 512 bytes).  QT: site-major codes, NpS a multiple of 512 and >= gridDim.x * 512.  site: L x NpS.  With W (the pass's
+// normalised weights) R (L x NpS x q) receives W_n (P_nl(b) - [s_nl = b]); with cond (nq x L x q, host layout) the conditionals.
+template <int QM>
+__global__ __launch_bounds__(kAThreads)
+void ar_logits_kernel(const double* __restrict__ x, int L, int q, const uint8_t* __restrict__ QT, int nq, int NpS,
+                      const double* __restrict__ W, double* __restrict__ site, double* __restrict__ R, double* __restrict__ cond)
+{
+    constexpr int CJ = chunk_blocks<QM>();
+    constexpr int KPB = (QM * QM + kAThreads - 1) / kAThreads;
+    constexpr int codeBytes = CJ * kASeqBlock;
+    constexpr int CPT = (codeBytes / 16 + kAThreads - 1) / kAThreads;   // 16-byte code pieces per thread
+    static_assert(CPT <= 2, "at most two code pieces per thread");
+    extern __shared__ __attribute__((aligned(16))) unsigned char ar_smem[];
+    const int blk = q * QM;
+    const int bufVals = CJ * blk;
+    double* bufJ = reinterpret_cast<double*>(ar_smem);
+    uint8_t* bufC = ar_smem + (size_t)2 * bufVals * sizeof(double);
+    const int tid = threadIdx.x;
+    const int l = L - 1 - (int)blockIdx.y;
+    const int seq0 = blockIdx.x * kASeqBlock;
+    const int qq = q * q;
+    const int steps = (l + CJ - 1) / CJ;
+
+    // this thread's block elements e = tid + kk * 256 < q * q: (a, b) = (e / q, e % q), contiguous in the source
+    int kA[KPB], kB[KPB];
+#pragma unroll
+    for (int kk = 0; kk < KPB; ++kk) {
+        const int e = tid + kk * kAThreads;
+        kA[kk] = e < qq ? e / q : -1;
+        kB[kk] = e < qq ? e - (e / q) * q : 0;
+    }
+    for (int e = tid; e < 2 * bufVals; e += kAThreads) bufJ[e] = 0.0;      // the row padding stays zero
+
+    double val[CJ][KPB];
+    uint4 cv0 = {}, cv1 = {};
+    auto load = [&](int t) {
+        const int k0 = t * CJ;
+#pragma unroll
+        for (int jj = 0; jj < CJ; ++jj) {
+            const int k = k0 + jj;
+            if (k >= l) continue;
+            const double* blkSrc = x + (size_t)L * q + pair_index(L, k, l) * (size_t)qq;
+#pragma unroll
+            for (int kk = 0; kk < KPB; ++kk)
+                if (kA[kk] >= 0) val[jj][kk] = blkSrc[kA[kk] * q + kB[kk]];
+        }
+        if (tid / 32 < CJ && k0 + tid / 32 < l) cv0 = *reinterpret_cast<const uint4*>(QT + (size_t)(k0 + tid / 32) * NpS + seq0 + (tid & 31) * 16);
+        if constexpr (CPT > 1) {
+            const int e = tid + kAThreads;
+            if (e / 32 < CJ && k0 + e / 32 < l) cv1 = *reinterpret_cast<const uint4*>(QT + (size_t)(k0 + e / 32) * NpS + seq0 + (e & 31) * 16);
+        }
+    };
+    auto store = [&](int t) {
+        const int k0 = t * CJ;
+        double* bj = bufJ + (t & 1) * bufVals;
+        uint8_t* bc = bufC + (t & 1) * codeBytes;
+#pragma unroll
+        for (int jj = 0; jj < CJ; ++jj) {
+            if (k0 + jj >= l) continue;
+#pragma unroll
+            for (int kk = 0; kk < KPB; ++kk)
+                if (kA[kk] >= 0) bj[jj * blk + kA[kk] * QM + kB[kk]] = val[jj][kk];
+        }
+        if (tid / 32 < CJ && k0 + tid / 32 < l) *reinterpret_cast<uint4*>(bc + (tid / 32) * kASeqBlock + (tid & 31) * 16) = cv0;
+        if constexpr (CPT > 1) {
+            const int e = tid + kAThreads;
+            if (e / 32 < CJ && k0 + e / 32 < l) *reinterpret_cast<uint4*>(bc + (e / 32) * kASeqBlock + (e & 31) * 16) = cv1;
+        }
+    };
+
+    double u[kAPerLane][QM];
+#pragma unroll
+    for (int b = 0; b < QM; ++b) {
+        const double h = b < q ? x[(size_t)l * q + b] : 0.0;
+#pragma unroll
+        for (int p = 0; p < kAPerLane; ++p) u[p][b] = h;
+    }
+
+    __syncthreads();
+    if (steps > 0) {
+        load(0);
+        store(0);
+    }
+    __syncthreads();
+
+    for (int t = 0; t < steps; ++t) {
+        const int k0 = t * CJ;
+        if (t + 1 < steps) load(t + 1);
+        const double* cur = bufJ + (t & 1) * bufVals;
+        const uint8_t* cc = bufC + (t & 1) * codeBytes;
+#pragma unroll 1
+        for (int jj = 0; jj < CJ; ++jj) {
+            if (k0 + jj >= l) break;
+#pragma unroll
+            for (int p = 0; p < kAPerLane; ++p) {
+                const double* row = cur + jj * blk + (int)cc[jj * kASeqBlock + p * kAThreads + tid] * QM;
+#pragma unroll
+                for (int b = 0; b < QM; b += 2) {
+                    const double2 v = *reinterpret_cast<const double2*>(row + b);
+                    u[p][b] += v.x; u[p][b + 1] += v.y;
+                }
+            }
+        }
+        if (t + 1 < steps) store(t + 1);
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int p = 0; p < kAPerLane; ++p) {
+        const int n = seq0 + p * kAThreads + tid;
+        if (n >= nq) continue;
+        const int sl = QT[(size_t)l * NpS + n];
+        double m = u[p][0];
+#pragma unroll
+        for (int b = 1; b < QM; ++b) if (b < q) m = fmax(m, u[p][b]);
+        double Z = 0.0, us = u[p][0];
+#pragma unroll
+        for (int b = 0; b < QM; ++b) {
+            if (b < q) Z += exp(u[p][b] - m);
+            if (b == sl) us = u[p][b];
+        }
+        const double lz = log(Z);
+        site[(size_t)l * NpS + n] = (us - m) - lz;
+        if (R) {
+            const double w = W[n];
+            double* r = R + ((size_t)l * NpS + n) * q;
+#pragma unroll
+            for (int b = 0; b < QM; ++b)
+                if (b < q) r[b] = w * (exp((u[p][b] - m) - lz) - (b == sl ? 1.0 : 0.0));
+        }
+        if (cond) {
+            double* out = cond + ((size_t)n * L + l) * q;
+#pragma unroll
+            for (int b = 0; b < QM; ++b) if (b < q) out[b] = (u[p][b] - m) - lz;
+        }
+    }
+}
+
+// logp[n] = sum_l site[l][n] (ascending l); rows (nq x L) or NULL: the site values in the host layout
+__global__ __launch_bounds__(256)
+void ar_finish_kernel(const double* __restrict__ site, int L, int nq, int NpS, double* __restrict__ logp, double* __restrict__ rows)
+{
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= nq) return;
+    double s = 0.0;
+    for (int l = 0; l < L; ++l) {
+        const double v = site[(size_t)l * NpS + n];
+        s += v;
+        if (rows) rows[(size_t)n * L + l] = v;
+    }
+    logp[n] = s;
+}
+
+// out[0] = sum_n W_n logp_n: thread t sums n = t, t + 256, ... ascending, then a fixed tree over the 256 partials
+__global__ __launch_bounds__(256)
+void ar_wsum_kernel(const double* __restrict__ logp, const double* __restrict__ W, int nq, double* __restrict__ out)
+{
+    __shared__ double part[256];
+    double s = 0.0;
+    for (int n = threadIdx.x; n < nq; n += 256) s += W[n] * logp[n];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = part[0];
+}
+
+// field gradient of one pass: g[l * q + b] (+)= sum_n R_nl(b), ascending n
+__global__ __launch_bounds__(256)
+void ar_field_kernel(const double* __restrict__ R, int L, int q, int nq, int NpS, double* __restrict__ g, int accumulate)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= L * q) return;
+    const int l = t / q, b = t - l * q;
+    const double* r = R + (size_t)l * NpS * q + b;
+    double s = 0.0;
+    for (int n = 0; n < nq; ++n) s += r[(size_t)n * q];
+    g[t] = accumulate ? g[t] + s : s;
+}
+
+// coupling gradient of one pass.  grid (ceil((L - 1) / KC), L - 1): blockIdx.y = L - 1 - l (heavy sites first), blockIdx.x the
+// chunk of KC earlier sites k.  Thread e < kc * q owns the column b = e % q of the block of k = k0 + e / q: G[kk][a][b] in LDS,
+// which it alone updates, for every a.  Tiles of 64 sequences (their residual rows R_nl(.) and the chunk's codes s_nk) are
+// staged in LDS; within a tile n ascends, so every element is summed over n in ascending order.  LDS: KC q^2 + 64 q doubles,
+// then KC x 64 code bytes.
+__global__ __launch_bounds__(kGMaxThreads)
+void ar_grad_kernel(const uint8_t* __restrict__ QT, const double* __restrict__ R, int L, int q, int nq, int NpS, int KC,
+                    double* __restrict__ g, int accumulate)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ar_gsmem[];
+    const int l = L - 1 - (int)blockIdx.y;
+    const int k0 = blockIdx.x * KC;
+    if (k0 >= l) return;
+    const int kc = min(KC, l - k0);
+    const int qq = q * q;
+    double* G = reinterpret_cast<double*>(ar_gsmem);
+    double* Rt = G + (size_t)KC * qq;
+    uint8_t* Ct = reinterpret_cast<uint8_t*>(Rt + kGTile * q);
+    const int tid = threadIdx.x;
+    const bool own = tid < kc * q;
+    const int kk = own ? tid / q : 0, b = own ? tid - (tid / q) * q : 0;
+    double* Gc = G + (size_t)kk * qq + b;
+    if (own)
+        for (int a = 0; a < q; ++a) Gc[a * q] = 0.0;
+    const double* Rl = R + (size_t)l * NpS * q;
+    for (int n0 = 0; n0 < nq; n0 += kGTile) {
+        const int tn = min(kGTile, nq - n0);
+        __syncthreads();
+        for (int e = tid; e < tn * q; e += blockDim.x) Rt[e] = Rl[(size_t)n0 * q + e];
+        for (int e = tid; e < kc * kGTile; e += blockDim.x) Ct[e] = QT[(size_t)(k0 + e / kGTile) * NpS + n0 + (e % kGTile)];
+        __syncthreads();
+        if (own) {
+            const uint8_t* cs = Ct + kk * kGTile;
+            for (int j = 0; j < tn; ++j) Gc[(int)cs[j] * q] += Rt[j * q + b];
+        }
+    }
+    if (!own) return;
+    double* dst = g + (size_t)L * q + pair_index(L, k0 + kk, l) * (size_t)qq + b;
+    for (int a = 0; a < q; ++a) dst[(size_t)a * q] = accumulate ? dst[(size_t)a * q] + Gc[a * q] : Gc[a * q];
+}
+
+// g[i] += 2 lambda x[i]  (lambda_h on the L q fields, lambda_J on the couplings)
+__global__ void ar_reg_kernel(double* __restrict__ g, const double* __restrict__ x, size_t P, size_t Lq, double lh2, double lJ2)
+{
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    g[i] = g[i] + (i < Lq ? lh2 : lJ2) * x[i];
+}
+
+// part[block] = sum of a[i] * b[i] over i = gid, gid + stride, ... (ascending), then a fixed tree in the block
+__global__ __launch_bounds__(256)
+void ar_dot_kernel(const double* __restrict__ a, const double* __restrict__ b, size_t n, double* __restrict__ part)
+{
+    __shared__ double sh[256];
+    double s = 0.0;
+    for (size_t i = blockIdx.x * (size_t)256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) s += a[i] * b[i];
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
+}
+
+// out[0] = the kDotBlocks partials summed by a fixed tree
+__global__ __launch_bounds__(kDotBlocks)
+void ar_dot_final_kernel(const double* __restrict__ part, double* __restrict__ out)
+{
+    __shared__ double sh[kDotBlocks];
+    sh[threadIdx.x] = part[threadIdx.x];
+    __syncthreads();
+    for (int w = kDotBlocks / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = sh[0];
+}
+
+__global__ void ar_axpy_kernel(double* __restrict__ y, double a, const double* __restrict__ x, size_t n)
+{
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) y[i] = y[i] + a * x[i];
+}
+
+__global__ void ar_scale_kernel(double* __restrict__ y, double a, size_t n)
+{
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) y[i] = a * y[i];
+}
+
+// y = a - b
+__global__ void ar_diff_kernel(double* __restrict__ y, const double* __restrict__ a, const double* __restrict__ b, size_t n)
+{
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) y[i] = a[i] - b[i];
+}
+
+// x = xp + t d
+__global__ void ar_step_kernel(double* __restrict__ x, const double* __restrict__ xp, double t, const double* __restrict__ d, size_t n)
+{
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) x[i] = xp[i] + t * d[i];
+}
+
+__global__ void ar_neg_kernel(double* __restrict__ d, const double* __restrict__ g, size_t n)
+{
+    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i < n) d[i] = -g[i];
+}
+
+// Ancestral sampling.  A wave holds 16 chains x 4 lanes; lane w of a chain sums the terms k = w (mod 4), k < l, ascending k
+// (lane 0 starting from h_l), the partials join in lane 0 in ascending w and lane 0 draws; the pick is broadcast and stored in
+// LDS by the lane that will read it (codes[(k / 4) * 64 + lane] holds s_k of that lane's chain for its k = w mod 4).
+// grid: ceil(n / 16) one-wave workgroups.  out: n x L codes (rows).
+template <int QM>
+__global__ __launch_bounds__(64)
+void ar_sample_kernel(const double* __restrict__ x, int L, int q, int n, uint64_t seed, uint64_t first_chain, uint8_t* __restrict__ out)
+{
+    extern __shared__ uint8_t ar_codes[];
+    const int lane = threadIdx.x, w = lane & (kSSlices - 1), base = lane & ~(kSSlices - 1);
+    const int c = blockIdx.x * kSChainsPerWave + lane / kSSlices;
+    const uint64_t chain = first_chain + (uint64_t)c;
+    const int qq = q * q;
+    const double* J = x + (size_t)L * q;
+    for (int l = 0; l < L; ++l) {
+        double u[QM];
+#pragma unroll
+        for (int b = 0; b < QM; ++b) u[b] = (w == 0 && b < q) ? x[(size_t)l * q + b] : 0.0;
+        for (int k = w; k < l; k += kSSlices) {
+            const int a = ar_codes[(k / kSSlices) * 64 + lane];
+            const double* row = J + pair_index(L, k, l) * (size_t)qq + (size_t)a * q;
+#pragma unroll
+            for (int b = 0; b < QM; ++b) if (b < q) u[b] += row[b];
+        }
+#pragma unroll
+        for (int s = 1; s < kSSlices; ++s) {
+#pragma unroll
+            for (int b = 0; b < QM; ++b) {
+                const double v = __shfl(u[b], base + s);
+                if (w == 0) u[b] += v;
+            }
+        }
+        int pick = 0;
+        if (w == 0) {
+            double m = u[0];
+#pragma unroll
+            for (int b = 1; b < QM; ++b) if (b < q) m = fmax(m, u[b]);
+            double T = 0.0;
+#pragma unroll
+            for (int b = 0; b < QM; ++b) {
+                u[b] = b < q ? exp(u[b] - m) : 0.0;          // sample.hip's exp(beta * (u - m)) at beta = 1
+                T += u[b];
+            }
+            const double r = philox_uniform(seed, chain, 0, l, 3) * T;
+            int last = 0;
+            double cum = 0.0;
+            pick = -1;
+#pragma unroll
+            for (int b = 0; b < QM; ++b) {
+                if (b < q) {
+                    cum += u[b];
+                    if (pick < 0 && cum > r) pick = b;
+                    if (u[b] > 0.0) last = b;
+                }
+            }
+            if (pick < 0) pick = last;
+        }
+        pick = __shfl(pick, base);
+        if ((l & (kSSlices - 1)) == w) ar_codes[(l / kSSlices) * 64 + lane] = (uint8_t)pick;
+        if (w == 0 && c < n) out[(size_t)c * L + l] = (uint8_t)pick;
+    }
+}
+
+inline int qm_of(int q) { return q <= 8 ? 8 : q <= 24 ? 24 : 32; }
+
+template <int QM>
+size_t logits_lds(int q)
+{
+    constexpr int CJ = chunk_blocks<QM>();
+    return 2 * (size_t)CJ * q * QM * sizeof(double) + 2 * (size_t)CJ * kASeqBlock;
+}
+
+template <int QM>
+hipError_t launch_logits_qm(dca_ctx* ctx, const double* x, int L, int q, const uint8_t* QT, int nq, int NpS, const double* W,
+                            double* site, double* R, double* cond)
+{
+    auto kern = ar_logits_kernel<QM>;
+    const size_t lds = logits_lds<QM>(q);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(ceil_div(nq, kASeqBlock), L), dim3(kAThreads), lds, ctx->stream, x, L, q, QT, nq, NpS, W, site, R, cond);
+    return hipGetLastError();
+}
+
+hipError_t launch_logits(dca_ctx* ctx, const double* x, int L, int q, const uint8_t* QT, int nq, int NpS, const double* W,
+                         double* site, double* R, double* cond)
+{
+    ScopedKernelClock kc(ctx, "ar_logits");
+    switch (qm_of(q)) {
+    case 8: return launch_logits_qm<8>(ctx, x, L, q, QT, nq, NpS, W, site, R, cond);
+    case 24: return launch_logits_qm<24>(ctx, x, L, q, QT, nq, NpS, W, site, R, cond);
+    default: return launch_logits_qm<32>(ctx, x, L, q, QT, nq, NpS, W, site, R, cond);
+    }
+}
+
+int grad_chunk(int q)
+{
+    return std::max(1, std::min({64, (int)(kGBlockBudget / ((size_t)q * q * sizeof(double))), kGMaxThreads / q}));
+}
+
+// sequences per pass: device scratch within kAPassBudget; DCA_AR_PASS (a positive count) caps it
+int ar_pass_size(int n, size_t perSeq)
+{
+    size_t cap = std::max((size_t)kASeqBlock, kAPassBudget / perSeq / kASeqBlock * kASeqBlock);
+    const char* env = getenv("DCA_AR_PASS");
+    if (env && atol(env) > 0) cap = std::min(cap, (size_t)atol(env));
+    return (int)std::min(cap, (size_t)std::max(n, 1));
+}
+
+inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
+
+// ---- More-Thuente interval update (More & Thuente 1994), restated from plm_engine.hip
+struct LsPoint { double st, f, d; };
+
+double cubic_min(double u, double fu, double du, double v, double fv, double dv)
+{
+    const double d = v - u;
+    const double theta = (fu - fv) * 3 / d + du + dv;
+    const double s = std::max(std::fabs(theta), std::max(std::fabs(du), std::fabs(dv)));
+    const double a = theta / s;
+    double gamma = s * std::sqrt(a * a - (du / s) * (dv / s));
+    if (v < u) gamma = -gamma;
+    const double p = gamma - du + theta, qd = gamma - du + gamma + dv;
+    return u + (p / qd) * d;
+}
+double cubic_min_clamped(double u, double fu, double du, double v, double fv, double dv, double lo, double hi)
+{
+    const double d = v - u;
+    const double theta = (fu - fv) * 3 / d + du + dv;
+    const double s = std::max(std::fabs(theta), std::max(std::fabs(du), std::fabs(dv)));
+    const double a = theta / s;
+    double gamma = s * std::sqrt(std::max(0.0, a * a - (du / s) * (dv / s)));
+    if (u < v) gamma = -gamma;
+    const double p = gamma - dv + theta, qd = gamma - dv + gamma + du;
+    const double r = p / qd;
+    if (r < 0. && gamma != 0.) return v - r * d;
+    return a < 0 ? hi : lo;
+}
+double quad_min_f(double u, double fu, double du, double v, double fv)
+{
+    const double a = v - u;
+    return u + du / ((fu - fv) / a + du) / 2 * a;
+}
+double quad_min_d(double u, double du, double v, double dv)
+{
+    const double a = u - v;
+    return v + dv / (dv - du) * a;
+}
+
+// 0, or < 0 when the trial point leaves the interval / the direction is no descent
+int mt_update(LsPoint& best, LsPoint& other, double& t, double ft, double dt, double tmin, double tmax, bool& brackt)
+{
+    const bool opposite = (dt * (best.d / std::fabs(best.d)) < 0.);
+    bool bound;
+    double newt;
+    if (brackt) {
+        if (t <= std::min(best.st, other.st) || std::max(best.st, other.st) <= t) return -1;
+        if (0. <= best.d * (t - best.st)) return -2;
+        if (tmax < tmin) return -3;
+    }
+    if (best.f < ft) {
+        brackt = true; bound = true;
+        const double mc = cubic_min(best.st, best.f, best.d, t, ft, dt);
+        const double mq = quad_min_f(best.st, best.f, best.d, t, ft);
+        newt = (std::fabs(mc - best.st) < std::fabs(mq - best.st)) ? mc : mc + 0.5 * (mq - mc);
+    } else if (opposite) {
+        brackt = true; bound = false;
+        const double mc = cubic_min(best.st, best.f, best.d, t, ft, dt);
+        const double mq = quad_min_d(best.st, best.d, t, dt);
+        newt = (std::fabs(mc - t) > std::fabs(mq - t)) ? mc : mq;
+    } else if (std::fabs(dt) < std::fabs(best.d)) {
+        bound = true;
+        const double mc = cubic_min_clamped(best.st, best.f, best.d, t, ft, dt, tmin, tmax);
+        const double mq = quad_min_d(best.st, best.d, t, dt);
+        if (brackt) newt = (std::fabs(t - mc) < std::fabs(t - mq)) ? mc : mq;
+        else newt = (std::fabs(t - mc) > std::fabs(t - mq)) ? mc : mq;
+    } else {
+        bound = false;
+        if (brackt) newt = cubic_min(t, ft, dt, other.st, other.f, other.d);
+        else newt = (best.st < t) ? tmax : tmin;
+    }
+    if (best.f < ft) {
+        other = LsPoint{t, ft, dt};
+    } else {
+        if (opposite) other = best;
+        best = LsPoint{t, ft, dt};
+    }
+    newt = std::min(newt, tmax);
+    newt = std::max(newt, tmin);
+    if (brackt && bound) {
+        const double mq = best.st + 0.66 * (other.st - best.st);
+        if (best.st < other.st) newt = std::min(newt, mq);
+        else newt = std::max(newt, mq);
+    }
+    t = newt;
+    return 0;
+}
+
+}  // namespace
+
+struct ArEngine {
+    dca_ctx* ctx;
+    int N = 0, L = 0, q = 0;
+    size_t P = 0;
+    bool configured = false;
+    double lh = 0.0, lJ = 0.0;
+    double *dx = nullptr, *dg = nullptr, *dW = nullptr;
+    // passes of the fit
+    int pass = 0, NpS = 0, npass = 0;
+    uint8_t* dQT = nullptr;
+    double *dSite = nullptr, *dR = nullptr, *dLogp = nullptr, *dPassF = nullptr;
+    // scalars: dot partials, results
+    double *dPart = nullptr, *dOut = nullptr;
+    // optimiser
+    double *dxp = nullptr, *dgp = nullptr, *dd = nullptr, *dS[5] = {}, *dY[5] = {};
+    int evals = 0;
+
+    explicit ArEngine(dca_ctx* c) : ctx(c) {}
+    ~ArEngine()
+    {
+        free_pass();
+        for (double* p : {dx, dg, dW, dPart, dOut, dxp, dgp, dd}) dca_dev_free(p);
+        for (int i = 0; i < 5; ++i) { dca_dev_free(dS[i]); dca_dev_free(dY[i]); }
+    }
+    void free_pass()
+    {
+        dca_dev_free(dQT); dca_dev_free(dSite); dca_dev_free(dR); dca_dev_free(dLogp); dca_dev_free(dPassF);
+        dQT = nullptr; dSite = dR = dLogp = dPassF = nullptr;
+    }
+
+    int fail(hipError_t e, const char* what)
+    {
+        dca_set_error("arDCA %s: %s", what, hipGetErrorString(e));
+        return DCA_ERR_HIP;
+    }
+
+    // x exists (zeros) for the context's (L, q)
+    int ensure_x()
+    {
+        if (dx && L == ctx->L && q == ctx->q) return DCA_OK;
+        dca_dev_free(dx); dca_dev_free(dg); dx = dg = nullptr;
+        L = ctx->L; q = ctx->q;
+        P = dca_plm_num_params(L, q);
+        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dx), P * sizeof(double)));
+        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dg), P * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(dx, 0, P * sizeof(double), ctx->stream));
+        HIP_TRY(hipMemsetAsync(dg, 0, P * sizeof(double), ctx->stream));
+        if (!dPart) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dPart), kDotBlocks * sizeof(double)));
+        if (!dOut) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dOut), 16 * sizeof(double)));
+        return DCA_OK;
+    }
+
+    int configure(double lambda_h, double lambda_J)
+    {
+        configured = false;
+        DCA_TRY(ensure_x());
+        N = ctx->N;
+        lh = lambda_h; lJ = lambda_J;
+        // W_n = w_n / sum w (the context's Meff: the ascending sum of the weights)
+        std::vector<double> w(N);
+        HIP_TRY(hipMemcpy(w.data(), ctx->dWd, (size_t)N * sizeof(double), hipMemcpyDeviceToHost));
+        const double meff = ctx->meff;
+        if (!(meff > 0.0)) { dca_set_error("arDCA: the weights sum to %g", meff); return DCA_ERR_ARG; }
+        for (double& v : w) v = v / meff;
+        dca_dev_free(dW); dW = nullptr;
+        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dW), (size_t)N * sizeof(double)));
+        HIP_TRY(hipMemcpy(dW, w.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
+        free_pass();
+        pass = ar_pass_size(N, (size_t)L * (1 + sizeof(double) + (size_t)q * sizeof(double)) + sizeof(double));
+        NpS = (int)round_up((size_t)pass, kASeqBlock);
+        npass = ceil_div(N, pass);
+        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dQT), (size_t)L * NpS, false));
+        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dSite), (size_t)L * NpS * sizeof(double), false));
+        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dR), (size_t)L * NpS * q * sizeof(double), false));
+        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dLogp), (size_t)NpS * sizeof(double), false));
+        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dPassF), (size_t)npass * sizeof(double), false));
+        configured = true;
+        return DCA_OK;
+    }
+
+    // dot products a_i . b_i into dOut[slot_i], then one copy of nout values to the host
+    hipError_t dot_async(const double* a, const double* b, size_t n, int slot)
+    {
+        hipLaunchKernelGGL(ar_dot_kernel, dim3(kDotBlocks), dim3(256), 0, ctx->stream, a, b, n, dPart);
+        hipLaunchKernelGGL(ar_dot_final_kernel, dim3(1), dim3(kDotBlocks), 0, ctx->stream, dPart, dOut + slot);
+        return hipGetLastError();
+    }
+    int read_out(int count, double* host)
+    {
+        HIP_TRY(hipMemcpyAsync(host, dOut, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return DCA_OK;
+    }
+    double dot(const double* a, const double* b, int* rc)
+    {
+        double v = 0.0;
+        hipError_t e = dot_async(a, b, P, 0);
+        if (e != hipSuccess) { *rc = fail(e, "dot"); return 0.0; }
+        *rc = read_out(1, &v);
+        return v;
+    }
+
+    // fx and g at dx.  With d: also g.d; always |g|^2 and |x|^2.  One round trip.
+    int evaluate(double* fx, const double* d, double* gd, double* gg, double* xx)
+    {
+        const size_t Lq = (size_t)L * q;
+        hipError_t e = hipSuccess;
+        const int KC = grad_chunk(q);
+        const int gthreads = (int)round_up((size_t)KC * q, 64);
+        const size_t glds = ((size_t)KC * q * q + (size_t)kGTile * q) * sizeof(double) + (size_t)KC * kGTile;
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ar_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds);
+        for (int p = 0; p < npass && e == hipSuccess; ++p) {
+            const int first = p * pass, nq = std::min(pass, N - first);
+            hipLaunchKernelGGL(ar_sites_kernel, dim3(blocks_of((size_t)L * NpS)), dim3(256), 0, ctx->stream, ctx->dX + (size_t)first * ctx->Ls,
+                               (size_t)ctx->Ls, nq, L, NpS, dQT);
+            e = launch_logits(ctx, dx, L, q, dQT, nq, NpS, dW + first, dSite, dR, nullptr);
+            if (e != hipSuccess) break;
+            hipLaunchKernelGGL(ar_finish_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, dSite, L, nq, NpS, dLogp, nullptr);
+            hipLaunchKernelGGL(ar_wsum_kernel, dim3(1), dim3(256), 0, ctx->stream, dLogp, dW + first, nq, dPassF + p);
+            {
+                ScopedKernelClock kc(ctx, "ar_grad");
+                hipLaunchKernelGGL(ar_field_kernel, dim3(blocks_of(Lq)), dim3(256), 0, ctx->stream, dR, L, q, nq, NpS, dg, p > 0 ? 1 : 0);
+                hipLaunchKernelGGL(ar_grad_kernel, dim3(ceil_div(L - 1, KC), L - 1), dim3(gthreads), glds, ctx->stream, dQT, dR, L, q, nq,
+                                   NpS, KC, dg, p > 0 ? 1 : 0);
+            }
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ar_reg_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dg, dx, P, Lq, 2.0 * lh, 2.0 * lJ);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = dot_async(dx, dx, Lq, 0);
+        if (e == hipSuccess) e = dot_async(dx + Lq, dx + Lq, P - Lq, 1);
+        if (e == hipSuccess) e = dot_async(dg, dg, P, 2);
+        if (e == hipSuccess && d) e = dot_async(dg, d, P, 3);
+        if (e != hipSuccess) return fail(e, "evaluation");
+        std::vector<double> pf(npass);
+        HIP_TRY(hipMemcpyAsync(pf.data(), dPassF, (size_t)npass * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        double s[4] = {0, 0, 0, 0};
+        DCA_TRY(read_out(d ? 4 : 3, s));
+        double F = 0.0;
+        for (int p = 0; p < npass; ++p) F += pf[p];
+        *fx = -F + (lh * s[0] + lJ * s[1]);
+        if (xx) *xx = s[0] + s[1];
+        if (gg) *gg = s[2];
+        if (gd) *gd = d ? s[3] : 0.0;
+        ++evals;
+        return DCA_OK;
+    }
+
+    int gradient(double* fx_out)
+    {
+        double fx = 0.0;
+        DCA_TRY(evaluate(&fx, nullptr, nullptr, nullptr, nullptr));
+        if (fx_out) *fx_out = fx;
+        return DCA_OK;
+    }
+
+    void vstep(double* x, const double* xp, double t, const double* d)
+    {
+        hipLaunchKernelGGL(ar_step_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, x, xp, t, d, P);
+    }
+    void vaxpy(double* y, double a, const double* x)
+    {
+        hipLaunchKernelGGL(ar_axpy_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, y, a, x, P);
+    }
+
+    // More-Thuente line search from xp along dd (x = xp + stp d): > 0 evaluations on success, < 0 failure; *rc runtime errors
+    int line_search(double* stp, double* f, double dginit, double* gg, double* xx, int* rc)
+    {
+        const double ftol = 1e-4, gtol = 0.9, xtol = 1e-16, min_step = 1e-20, max_step = 1e20;
+        const int max_ls = 20;
+        int count = 0, uinfo = 0;
+        bool brackt = false, stage1 = true;
+        *rc = DCA_OK;
+        if (*stp <= 0.) return -1;
+        if (0 <= dginit) return -2;
+        const double finit = *f;
+        const double dgtest = ftol * dginit;
+        double width = max_step - min_step, prev_width = 2.0 * width;
+        LsPoint bx{0., finit, dginit}, by{0., finit, dginit};
+        for (;;) {
+            double stmin, stmax;
+            if (brackt) { stmin = std::min(bx.st, by.st); stmax = std::max(bx.st, by.st); }
+            else { stmin = bx.st; stmax = *stp + 4.0 * (*stp - bx.st); }
+            if (*stp < min_step) *stp = min_step;
+            if (max_step < *stp) *stp = max_step;
+            if ((brackt && ((*stp <= stmin || stmax <= *stp) || max_ls <= count + 1 || uinfo != 0)) ||
+                (brackt && (stmax - stmin <= xtol * stmax)))
+                *stp = bx.st;
+            vstep(dx, dxp, *stp, dd);
+            double dg_ = 0.0;
+            if ((*rc = evaluate(f, dd, &dg_, gg, xx))) return -100;
+            const double ftest1 = finit + *stp * dgtest;
+            ++count;
+            if (brackt && ((*stp <= stmin || stmax <= *stp) || uinfo != 0)) return -3;
+            if (*stp == max_step && *f <= ftest1 && dg_ <= dgtest) return -4;
+            if (*stp == min_step && (ftest1 < *f || dgtest <= dg_)) return -5;
+            if (brackt && (stmax - stmin) <= xtol * stmax) return -6;
+            if (max_ls <= count) return -7;
+            if (*f <= ftest1 && std::fabs(dg_) <= gtol * (-dginit)) return count;      // strong Wolfe conditions
+            if (stage1 && *f <= ftest1 && std::min(ftol, gtol) * dginit <= dg_) stage1 = false;
+            if (stage1 && ftest1 < *f && *f <= bx.f) {
+                LsPoint mx{bx.st, bx.f - bx.st * dgtest, bx.d - dgtest};
+                LsPoint my{by.st, by.f - by.st * dgtest, by.d - dgtest};
+                uinfo = mt_update(mx, my, *stp, *f - *stp * dgtest, dg_ - dgtest, stmin, stmax, brackt);
+                bx = LsPoint{mx.st, mx.f + mx.st * dgtest, mx.d + dgtest};
+                by = LsPoint{my.st, my.f + my.st * dgtest, my.d + dgtest};
+            } else {
+                uinfo = mt_update(bx, by, *stp, *f, dg_, stmin, stmax, brackt);
+            }
+            if (brackt) {
+                if (0.66 * prev_width <= std::fabs(by.st - bx.st)) *stp = bx.st + 0.5 * (by.st - bx.st);
+                prev_width = width;
+                width = std::fabs(by.st - bx.st);
+            }
+        }
+    }
+
+    int fit(int max_iterations, double epsilon, dca_ar_stats* st)
+    {
+        constexpr int M = 5;
+        const auto t0 = std::chrono::steady_clock::now();
+        if (!dxp) {
+            for (double** p : {&dxp, &dgp, &dd}) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(p), P * sizeof(double)));
+            for (int i = 0; i < M; ++i) {
+                HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dS[i]), P * sizeof(double)));
+                HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dY[i]), P * sizeof(double)));
+            }
+        }
+        evals = 0;
+        double fx = 0.0, gg = 0.0, xx = 0.0;
+        DCA_TRY(evaluate(&fx, nullptr, nullptr, &gg, &xx));
+        int status = DCA_AR_MAX_ITERATIONS, k = 0, stored = 0, newest = -1;
+        double ys[M] = {}, alpha[M] = {};
+        hipLaunchKernelGGL(ar_neg_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dd, dg, P);
+        double dginit = -gg;
+        double step = gg > 0.0 ? 1.0 / std::sqrt(gg) : 1.0;
+        int rc = DCA_OK;
+        for (;;) {
+            if (std::sqrt(gg) <= epsilon * std::max(1.0, std::sqrt(xx))) { status = DCA_AR_CONVERGED; break; }
+            if (k >= max_iterations) { status = DCA_AR_MAX_ITERATIONS; break; }
+            std::swap(dx, dxp);
+            std::swap(dg, dgp);
+            const double fprev = fx, ggprev = gg, xxprev = xx;
+            const int ls = line_search(&step, &fx, dginit, &gg, &xx, &rc);
+            if (rc) return rc;
+            if (ls < 0) {                                     // back to the last accepted point
+                std::swap(dx, dxp);
+                std::swap(dg, dgp);
+                fx = fprev; gg = ggprev; xx = xxprev;
+                status = DCA_AR_LINE_SEARCH_FAILED;
+                break;
+            }
+            ++k;
+            if (std::sqrt(gg) <= epsilon * std::max(1.0, std::sqrt(xx))) { status = DCA_AR_CONVERGED; break; }
+            if (k >= max_iterations) { status = DCA_AR_MAX_ITERATIONS; break; }
+            // the new pair s = x - xp, y = g - gp
+            const int slot = (newest + 1) % M;
+            hipLaunchKernelGGL(ar_diff_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dS[slot], dx, dxp, P);
+            hipLaunchKernelGGL(ar_diff_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dY[slot], dg, dgp, P);
+            HIP_TRY(dot_async(dY[slot], dS[slot], P, 0));
+            HIP_TRY(dot_async(dY[slot], dY[slot], P, 1));
+            double sy[2];
+            DCA_TRY(read_out(2, sy));
+            if (sy[0] > 0.0) {                                // the Wolfe conditions make y.s > 0; a pair without it is dropped
+                newest = slot;
+                ys[slot] = sy[0];
+                stored = std::min(stored + 1, M);
+            }
+            // two-loop recursion: d = -H g
+            hipLaunchKernelGGL(ar_neg_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dd, dg, P);
+            for (int i = 0, j = newest; i < stored; ++i, j = (j + M - 1) % M) {
+                const double sd = dot(dS[j], dd, &rc);
+                if (rc) return rc;
+                alpha[j] = sd / ys[j];
+                vaxpy(dd, -alpha[j], dY[j]);
+            }
+            if (stored > 0 && sy[0] > 0.0)
+                hipLaunchKernelGGL(ar_scale_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dd, sy[0] / sy[1], P);
+            for (int i = 0, j = (newest + M - stored + 1) % M; i < stored; ++i, j = (j + 1) % M) {
+                const double yd = dot(dY[j], dd, &rc);
+                if (rc) return rc;
+                vaxpy(dd, alpha[j] - yd / ys[j], dS[j]);
+            }
+            dginit = dot(dg, dd, &rc);
+            if (rc) return rc;
+            if (!(dginit < 0.0)) {                            // not a descent direction: restart from steepest descent
+                hipLaunchKernelGGL(ar_neg_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dd, dg, P);
+                dginit = -gg;
+                stored = 0;
+                step = 1.0 / std::sqrt(gg);
+            } else {
+                step = 1.0;
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (st) {
+            st->status = status; st->iterations = k; st->evaluations = evals;
+            st->fx = fx; st->gnorm = std::sqrt(gg);
+            st->seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        }
+        return DCA_OK;
+    }
+
+    int log_probabilities(const uint8_t* X, int n, double* logp_out, double* site_out, double* cond_out)
+    {
+        const size_t perSeq = (size_t)L * (2 + sizeof(double)) + sizeof(double) + (site_out ? (size_t)L * sizeof(double) : 0) +
+                              (cond_out ? (size_t)L * q * sizeof(double) : 0);
+        const int cap = ar_pass_size(n, perSeq);
+        const int S = (int)round_up((size_t)cap, kASeqBlock);
+        uint8_t *dRows = nullptr, *dQ = nullptr;
+        double *dS_ = nullptr, *dLp = nullptr, *dRowsOut = nullptr, *dCond = nullptr;
+        hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)cap * L, false);
+        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dQ), (size_t)L * S, false);
+        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dS_), (size_t)L * S * sizeof(double), false);
+        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dLp), (size_t)S * sizeof(double), false);
+        if (e == hipSuccess && site_out) e = dca_dev_malloc(reinterpret_cast<void**>(&dRowsOut), (size_t)cap * L * sizeof(double), false);
+        if (e == hipSuccess && cond_out) e = dca_dev_malloc(reinterpret_cast<void**>(&dCond), (size_t)cap * L * q * sizeof(double), false);
+        for (int first = 0; first < n && e == hipSuccess; first += cap) {
+            const int nq = std::min(cap, n - first);
+            e = hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream);
+            if (e != hipSuccess) break;
+            hipLaunchKernelGGL(ar_sites_kernel, dim3(blocks_of((size_t)L * S)), dim3(256), 0, ctx->stream, dRows, (size_t)L, nq, L, S, dQ);
+            e = launch_logits(ctx, dx, L, q, dQ, nq, S, nullptr, dS_, nullptr, dCond);
+            if (e != hipSuccess) break;
+            hipLaunchKernelGGL(ar_finish_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, dS_, L, nq, S, dLp, dRowsOut);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(logp_out + first, dLp, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess && site_out)
+                e = hipMemcpyAsync(site_out + (size_t)first * L, dRowsOut, (size_t)nq * L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess && cond_out)
+                e = hipMemcpyAsync(cond_out + (size_t)first * L * q, dCond, (size_t)nq * L * q * sizeof(double), hipMemcpyDeviceToHost,
+                                   ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        }
+        dca_dev_free(dRows); dca_dev_free(dQ); dca_dev_free(dS_); dca_dev_free(dLp); dca_dev_free(dRowsOut); dca_dev_free(dCond);
+        if (e != hipSuccess) return fail(e, "log-probabilities");
+        return DCA_OK;
+    }
+
+    int sample(int n, uint64_t seed, uint64_t first_chain, uint8_t* out)
+    {
+        const size_t lds = (size_t)64 * ceil_div(L, kSSlices);
+        if (lds > 160 * 1024) { dca_set_error("arDCA sample: L = %d exceeds the sampler's %d sites", L, 160 * 1024 / 64 * kSSlices); return DCA_ERR_ARG; }
+        uint8_t* dOutRows = nullptr;
+        hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dOutRows), (size_t)n * L, false);
+        if (e == hipSuccess) {
+            ScopedKernelClock kc(ctx, "ar_sample");
+            auto go = [&](auto kern) {
+                hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                if (r != hipSuccess) return r;
+                hipLaunchKernelGGL(kern, dim3(ceil_div(n, kSChainsPerWave)), dim3(64), lds, ctx->stream, dx, L, q, n, seed, first_chain, dOutRows);
+                return hipGetLastError();
+            };
+            switch (qm_of(q)) {
+            case 8: e = go(ar_sample_kernel<8>); break;
+            case 24: e = go(ar_sample_kernel<24>); break;
+            default: e = go(ar_sample_kernel<32>); break;
+            }
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(out, dOutRows, (size_t)n * L, hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        dca_dev_free(dOutRows);
+        if (e != hipSuccess) return fail(e, "sample");
+        return DCA_OK;
+    }
+};
+
+ArEngine* dca_make_ar_engine(dca_ctx* ctx) { return new ArEngine(ctx); }
+void dca_free_ar_engine(ArEngine* e) { delete e; }
+void dca_ar_engine_weights_changed(ArEngine* e) { if (e) e->configured = false; }
+
+// ---- C-ABI (include/dca_hip.h)
+extern "C" {
+
+static int ar_need_engine(dca_ctx* ctx, bool need_configured)
+{
+    if (!ctx) { dca_set_error("null context"); return DCA_ERR_ARG; }
+    if (!ctx->ar || !ctx->ar->dx) { dca_set_error("dca_ar_configure first"); return DCA_ERR_STATE; }
+    if (need_configured && !ctx->ar->configured) { dca_set_error("dca_ar_configure first (the weights changed since)"); return DCA_ERR_STATE; }
+    hipSetDevice(ctx->device);
+    return DCA_OK;
+}
+
+int dca_ar_configure(dca_ctx* ctx, double lambda_h, double lambda_J)
+{
+    if (!ctx) { dca_set_error("null context"); return DCA_ERR_ARG; }
+    if (!(lambda_h >= 0.0) || !(lambda_J >= 0.0) || std::isinf(lambda_h) || std::isinf(lambda_J)) {
+        dca_set_error("dca_ar_configure: lambda_h %g, lambda_J %g must be finite and >= 0", lambda_h, lambda_J);
+        return DCA_ERR_ARG;
+    }
+    if (!ctx->dX) { dca_set_error("dca_set_msa first"); return DCA_ERR_STATE; }
+    if (!ctx->have_weights) { dca_set_error("dca_compute_weights or dca_set_weights first"); return DCA_ERR_STATE; }
+    hipSetDevice(ctx->device);
+    if (!ctx->ar) ctx->ar = dca_make_ar_engine(ctx);
+    return ctx->ar->configure(lambda_h, lambda_J);
+}
+
+size_t dca_ar_num_params(int L, int q) { return dca_plm_num_params(L, q); }
+
+int dca_ar_init_x(dca_ctx* ctx)
+{
+    DCA_TRY(ar_need_engine(ctx, false));
+    HIP_TRY(hipMemsetAsync(ctx->ar->dx, 0, ctx->ar->P * sizeof(double), ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return DCA_OK;
+}
+
+int dca_ar_set_x(dca_ctx* ctx, const double* x)
+{
+    DCA_TRY(ar_need_engine(ctx, false));
+    if (!x) { dca_set_error("dca_ar_set_x: x is NULL"); return DCA_ERR_ARG; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(ctx->ar->dx, x, ctx->ar->P * sizeof(double), hipMemcpyHostToDevice));
+    return DCA_OK;
+}
+
+int dca_ar_get_x(dca_ctx* ctx, double* x)
+{
+    DCA_TRY(ar_need_engine(ctx, false));
+    if (!x) { dca_set_error("dca_ar_get_x: x is NULL"); return DCA_ERR_ARG; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(x, ctx->ar->dx, ctx->ar->P * sizeof(double), hipMemcpyDeviceToHost));
+    return DCA_OK;
+}
+
+int dca_ar_gradient(dca_ctx* ctx, double* fx_out)
+{
+    DCA_TRY(ar_need_engine(ctx, true));
+    return ctx->ar->gradient(fx_out);
+}
+
+int dca_ar_get_g(dca_ctx* ctx, double* g)
+{
+    DCA_TRY(ar_need_engine(ctx, false));
+    if (!g) { dca_set_error("dca_ar_get_g: g is NULL"); return DCA_ERR_ARG; }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(g, ctx->ar->dg, ctx->ar->P * sizeof(double), hipMemcpyDeviceToHost));
+    return DCA_OK;
+}
+
+int dca_ar_fit(dca_ctx* ctx, int max_iterations, double epsilon, dca_ar_stats* stats_out)
+{
+    if (max_iterations < 0 || !(epsilon >= 0.0) || std::isinf(epsilon)) {
+        dca_set_error("dca_ar_fit: max_iterations %d must be >= 0 and epsilon %g finite and >= 0", max_iterations, epsilon);
+        return DCA_ERR_ARG;
+    }
+    DCA_TRY(ar_need_engine(ctx, true));
+    return ctx->ar->fit(max_iterations, epsilon, stats_out);
+}
+
+int dca_ar_log_probabilities(dca_ctx* ctx, const uint8_t* X, int n, double* logp, double* site, double* cond)
+{
+    if (n < 0 || (n > 0 && (!X || !logp))) { dca_set_error("dca_ar_log_probabilities: bad arguments"); return DCA_ERR_ARG; }
+    DCA_TRY(ar_need_engine(ctx, false));
+    if (n == 0) return DCA_OK;
+    const int L = ctx->ar->L, q = ctx->ar->q;
+    for (size_t k = 0; k < (size_t)n * L; ++k)
+        if (X[k] >= q) { dca_set_error("code %d >= q at element %zu", (int)X[k], k); return DCA_ERR_ARG; }
+    return ctx->ar->log_probabilities(X, n, logp, site, cond);
+}
+
+int dca_ar_sample(dca_ctx* ctx, int n, uint64_t seed, uint64_t first_chain, uint8_t* out)
+{
+    if (n < 0 || (n > 0 && !out)) { dca_set_error("dca_ar_sample: bad arguments (n %d)", n); return DCA_ERR_ARG; }
+    DCA_TRY(ar_need_engine(ctx, false));
+    if (n == 0) return DCA_OK;
+    return ctx->ar->sample(n, seed, first_chain, out);
+}
+
+int dca_ar_release(dca_ctx* ctx)
+{
+    if (!ctx) { dca_set_error("null context"); return DCA_ERR_ARG; }
+    if (!ctx->ar) return DCA_OK;
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { dca_set_error("dca_ar_release: stream synchronisation failed"); return DCA_ERR_HIP; }
+    dca_free_ar_engine(ctx->ar);
+    ctx->ar = nullptr;
+    return DCA_OK;
+}
+
+}  // extern "C"

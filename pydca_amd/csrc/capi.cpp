@@ -233,6 +233,7 @@ static void free_msa(dca_ctx* ctx)
 {
     dca_bm_free(ctx);
     delete ctx->plm; ctx->plm = nullptr;
+    dca_free_ar_engine(ctx->ar); ctx->ar = nullptr;
     if (ctx->mf) { dca_free_mf_engine(ctx->mf); ctx->mf = nullptr; }
     dca_dev_free(ctx->dX); ctx->dX = nullptr;
     dca_dev_free(ctx->dCounts); ctx->dCounts = nullptr;
@@ -344,6 +345,7 @@ static void weights_changed(dca_ctx* ctx)
 {
     dca_bm_free(ctx);          // a Boltzmann-learning run fits the old weights' statistics: it ends
     if (ctx->plm) ctx->plm->weights_changed();
+    dca_ar_engine_weights_changed(ctx->ar);       // the autoregressive engine keeps x and must be configured again
     if (ctx->mf) dca_mf_engine_invalidate(ctx->mf);
 }
 

@@ -54,6 +54,7 @@ struct KernelClock {
 struct PlmEngineBase;
 struct MfEngine;
 struct BmRun;
+struct ArEngine;
 
 #define DCA_SIDE_DEPTHS 3
 
@@ -85,6 +86,7 @@ struct dca_ctx {
     PlmEngineBase* plm = nullptr;
     MfEngine* mf = nullptr;
     BmRun* bm = nullptr;          // Boltzmann-learning run in progress (boltzmann.hip)
+    ArEngine* ar = nullptr;       // autoregressive model (ardca.hip)
 
     // native communicator (comm_rccl.cpp): an RCCL communicator whose collectives run on `stream`
     void* comm = nullptr;
@@ -226,7 +228,8 @@ int dca_potts_sample(dca_ctx* ctx, const void* src, int src_kind, int dtype, con
                      const uint8_t* initial /* host n*L or NULL */, uint8_t* out /* host n*L */);
 
 // Philox4x32-10 of the samplers (sample.hip, ais.hip): key = (seed lo, seed hi), counter = (chain, sweep, site, tag), each
-// word the value mod 2^32; U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  Tags: 0 Gibbs draw, 1 random start, 2 AIS start.
+// word the value mod 2^32; U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  Tags: 0 Gibbs draw, 1 random start, 2 AIS start,
+// 3 ancestral draw of the autoregressive sampler (ardca.hip, counter (chain, 0, site, 3)).
 static __host__ __device__ __forceinline__ void philox4x32_10(const uint32_t in[4], const uint32_t k[2], uint32_t out[4])
 {
     uint32_t c0 = in[0], c1 = in[1], c2 = in[2], c3 = in[3], k0 = k[0], k1 = k[1];
@@ -279,6 +282,11 @@ void dca_bm_free(dca_ctx* ctx);
 
 int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, const double* reg_fi, int L, int q,
                             double* fields_out, double* di_out, const double* fields_in = nullptr);
+
+// ---- ardca.hip : the autoregressive model (dca_ar_*).  Freed with the alignment; unconfigured when the weights change.
+ArEngine* dca_make_ar_engine(dca_ctx* ctx);
+void dca_free_ar_engine(ArEngine*);
+void dca_ar_engine_weights_changed(ArEngine*);
 
 // ---- mf engine
 struct MfEngine;
