@@ -154,6 +154,128 @@ def pseudo_log_likelihood(plls, weights, meff):
     return float(np.dot(np.asarray(weights, dtype=np.float64), np.asarray(plls, dtype=np.float64))) / float(meff)
 
 
+class PottsModel:
+    """The fitted model of PlmDCA and MeanFieldDCA as a sequence model: energies, single-mutant effects, Gibbs samples, log Z and
+    pseudo-log-likelihoods (DESIGN.md sections 11, 12, 14 and 15; no reference counterpart).  E includes the gap state for PlmDCA
+    (after fit_boltzmann: the refined model); under MeanFieldDCA couplings and fields are zero on the gap state, and the
+    couplings of the current pseudocount are computed first if none are there yet.
+
+    A class supplies: _potts_exc (its exception type), _potts_table (residue table of the encoder: 0 plm, 1 mf),
+    _potts_dims() -> (biomolecule code, L, q), _potts_default_source() (the training file or alignment), _potts_devices(),
+    _potts_training() -> (X, weights, meff) of the fit, and _potts_call(name, *args, **kw), which runs Context.plm_<name> /
+    Context.mf_<name> on the fitted model."""
+
+    def _query(self, sequences):
+        bio, L, _q = self._potts_dims()
+        src = self._potts_default_source() if sequences is None else sequences
+        return query_codes(src, bio, L, self._potts_table, self._potts_exc)
+
+    def _one_gpu(self, what):
+        devices = self._potts_devices()
+        if devices and len(devices) > 1:
+            self._potts_logger.error('\n\t{} runs on one GPU; devices={}'.format(what, devices))
+            raise self._potts_exc('{} runs on one GPU, not on devices {}'.format(what, devices))
+
+    def compute_sequence_energies(self, sequences=None):
+        """Statistical energies E(s) = sum_i h_i(s_i) + sum_{i<j} J_ij(s_i, s_j) of the fitted parameters -> float64[n], higher
+        is more probable.  sequences: None (every record of the training alignment, in file order, duplicates kept), a FASTA
+        path or a list of aligned strings."""
+        X = self._query(sequences)
+        self._potts_logger.info('\n\tStatistical energies of {} sequences'.format(X.shape[0]))
+        return self._potts_call('energies', X)
+
+    def compute_single_mutant_effects(self, wildtype):
+        """dE(i, a) = E(wildtype with site i set to state a) - E(wildtype) for every site and state (gap last)
+        -> float64[L, q]; dE(i, w_i) = 0.  wildtype: an aligned string of length L or a FASTA file with one record."""
+        bio, L, _q = self._potts_dims()
+        w = wildtype_codes(wildtype, bio, L, self._potts_table, self._potts_exc)
+        self._potts_logger.info('\n\tSingle-mutant effects of the wild type')
+        return self._potts_call('mutation_scan', w)
+
+    def sample_sequences(self, num_sequences, num_sweeps=1000, seed=0, temperature=1.0, initial=None, return_codes=False):
+        """Draws num_sequences sequences from P(s) ~ exp(E(s) / temperature) by systematic-scan Gibbs sampling on the GPU:
+        one independent chain per sequence, num_sweeps sweeps over all sites (E as in compute_sequence_energies).
+        initial: None (random starts), an aligned string (every chain starts from it), a list of num_sequences aligned
+        strings, or a FASTA file with 1 or num_sequences records.  The draws follow a counter-based generator of `seed`:
+        the same arguments give the same sequences.  -> aligned strings (gap '-'), or uint8[n, L] codes with
+        return_codes."""
+        n = int(num_sequences)
+        beta = sampling_beta(temperature, self._potts_exc)
+        bio, L, _q = self._potts_dims()
+        X0 = initial_codes(initial, n, bio, L, self._potts_table, self._potts_exc)
+        self._potts_logger.info('\n\tGibbs sampling of {} sequences, {} sweeps'.format(n, num_sweeps))
+        codes = self._potts_call('sample', n, num_sweeps, seed=seed, beta=beta, initial=X0)
+        if return_codes:
+            return codes
+        letters = state_letters(bio)
+        return [''.join(letters[c] for c in row) for row in codes]
+
+    def compute_log_partition_function(self, num_chains=1000, num_temperatures=1000, sweeps_per_temperature=1, seed=0, base='profile',
+                                       pseudocount=None):
+        """log Z = log sum_s exp(E(s)) of the fitted model (E as in compute_sequence_energies) by annealed importance sampling
+        on the GPU: num_chains chains start from the independent-site base model and anneal through beta_k = k / K
+        (K = num_temperatures) with sweeps_per_temperature Gibbs sweeps per intermediate temperature.  base: 'profile' (log of
+        the training alignment's weighted single-site frequencies, regularised by (1 - lambda) f + lambda / q, lambda =
+        pseudocount or 1 / Meff), 'fields' (the model's own fields) or an L x q array.
+        -> {'log_z', 'log_z_stderr', 'ess', 'log_z_base', 'log_weights'}"""
+        self._one_gpu('compute_log_partition_function')
+        opts = ais_options(num_chains, num_temperatures, sweeps_per_temperature, seed, pseudocount, self._potts_exc)
+        _bio, L, q = self._potts_dims()
+        X, weights, _meff = self._potts_training() if isinstance(base, str) and base == 'profile' else (None, None, None)
+        h0 = ais_base(base, X, weights, L, q, opts['pseudocount'], self._potts_exc)
+        self._potts_logger.info('\n\tlog Z by annealed importance sampling: {} chains, {} temperatures, {} sweeps per temperature'.format(
+            opts['num_chains'], opts['num_temperatures'], opts['sweeps_per_temperature']))
+        return log_partition_function(
+            lambda n, K, s, sd, h: self._potts_call('ais', n, K, sweeps_per_temperature=s, seed=sd, base_fields=h), opts, h0)
+
+    def compute_sequence_log_probabilities(self, sequences=None, log_z=None, **ais_kwargs):
+        """log P(s) = E(s) - log Z -> float64[n] (sequences as in compute_sequence_energies).  log_z None: estimated first by
+        compute_log_partition_function(**ais_kwargs)."""
+        self._one_gpu('compute_sequence_log_probabilities')
+        if log_z is None:
+            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
+        return self.compute_sequence_energies(sequences) - float(log_z)
+
+    def compute_log_likelihood(self, log_z=None, **ais_kwargs):
+        """(sum_n w_n E(s_n)) / Meff - log Z over the alignment and weights of the fit -> float.  log_z None: estimated first
+        by compute_log_partition_function(**ais_kwargs)."""
+        self._one_gpu('compute_log_likelihood')
+        if log_z is None:
+            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
+        X, weights, meff = self._potts_training()
+        return log_likelihood(self._potts_call('energies', X), weights, meff, log_z)
+
+    def compute_sequence_pseudo_log_likelihoods(self, sequences=None, per_site=False):
+        """PLL(s) = sum_i log P(s_i | s_-i) of the fitted parameters, with log P(s_i = a | s_-i) = u_i(a) - log sum_b exp u_i(b),
+        u_i(a) = h_i(a) + sum_{j != i} J_ij(a, s_j) -> float64[n], or (float64[n], float64[n, L] of log P(s_i | s_-i)) with
+        per_site.  sequences: as in compute_sequence_energies.  This is the true pseudo-log-likelihood, not the fx a PlmDCA fit
+        reports: under the reference's carry-over of the gradient the fit's objective differs from it by
+        design."""
+        per_site = pll_flag(per_site, self._potts_exc)
+        self._one_gpu('compute_sequence_pseudo_log_likelihoods')
+        X = self._query(sequences)
+        self._potts_logger.info('\n\tPseudo-log-likelihoods of {} sequences'.format(X.shape[0]))
+        return self._potts_call('pseudo_likelihood', X, per_site=per_site)
+
+    def compute_conditional_log_probabilities(self, sequences):
+        """log P(s_i = a | s_-i) for every site i and state a (gap last) of each sequence (as in
+        compute_sequence_pseudo_log_likelihoods) -> float64[n, L, q], or float64[L, q] for a single aligned string.
+        sequences: an aligned string, a list of aligned strings or a FASTA path."""
+        single = single_query(sequences, self._potts_exc)
+        self._one_gpu('compute_conditional_log_probabilities')
+        X = self._query([sequences] if single else sequences)
+        _pll, cond = self._potts_call('pseudo_likelihood', X, conditionals=True)
+        return cond[0] if single else cond
+
+    def compute_pseudo_log_likelihood(self):
+        """(sum_n w_n PLL(s_n)) / Meff over the alignment and weights of the fit -> float: the unregularised
+        pseudo-log-likelihood per effective sequence (compute_sequence_pseudo_log_likelihoods), comparable with
+        compute_log_likelihood.  Not a PlmDCA fit's reported fx."""
+        self._one_gpu('compute_pseudo_log_likelihood')
+        X, weights, meff = self._potts_training()
+        return pseudo_log_likelihood(self._potts_call('pseudo_likelihood', X), weights, meff)
+
+
 def add_sampling_arguments(p):
     """The options of the sample_sequences sub-command (plmdca and mfdca command lines)."""
     p.add_argument('--num_sequences', type=int, required=True, help='number of sequences (independent chains) to draw (addition)')

@@ -16,13 +16,6 @@ namespace {
 constexpr int kAisStride = 128;                  // chain stride of the state: the energy kernels' multiple
 constexpr int kAisMaxChains = 1 << 24;
 
-template <typename S>
-__device__ __forceinline__ double field(const S* src, const double* mfh, int kind, int q, int i, int a)
-{
-    if (kind == 0) return (double)src[(size_t)i * q + a];
-    return a == q - 1 ? 0.0 : mfh[(size_t)i * (q - 1) + a];
-}
-
 // x_0 of chain first_chain + c at site s: st[s * nS + c]; chains past n get code 0 (swept, never read)
 __global__ void ais_start_kernel(const double* __restrict__ h0, int n, int L, int q, int nS, uint64_t seed, uint64_t first_chain,
                                  uint8_t* __restrict__ st)
@@ -51,49 +44,48 @@ __global__ void ais_start_kernel(const double* __restrict__ h0, int n, int L, in
 // log w[c] += dbeta * (E(x) - E0(x)); E as energy_finish_kernel forms it from the fields and the slabs
 template <typename S>
 __global__ __launch_bounds__(256)
-void ais_weight_kernel(const S* __restrict__ src, const double* __restrict__ mfh, int kind, int L, int q,
-                       const uint8_t* __restrict__ QT, int n, int NqS, const double* __restrict__ slabs, int G,
+void ais_weight_kernel(const PottsView<S> pv, const uint8_t* __restrict__ QT, int n, int NqS, const double* __restrict__ slabs, int G,
                        const double* __restrict__ h0, double dbeta, double* __restrict__ logw)
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= n) return;
+    const int L = pv.L, q = pv.q;
     double e = 0.0;
-    for (int i = 0; i < L; ++i) e += field(src, mfh, kind, q, i, QT[(size_t)i * NqS + c]);
+    for (int i = 0; i < L; ++i) e += pv.field(i, QT[(size_t)i * NqS + c]);
     for (int g = 0; g < G; ++g) e += slabs[(size_t)g * NqS + c];
     double e0 = 0.0;
     for (int i = 0; i < L; ++i) e0 += h0[(size_t)i * q + QT[(size_t)i * NqS + c]];
     logw[c] = logw[c] + dbeta * (e - e0);
 }
 
-hipError_t weight_step(dca_ctx* ctx, const void* src, int kind, int dtype, const double* mfh, int L, int q, int ld, const DcaChains& ch,
-                       double* dSlabs, int G, const double* dH0, double dbeta, double* dLogW)
+hipError_t weight_step(dca_ctx* ctx, const PottsSource& ps, const DcaChains& ch, double* dSlabs, int G, const double* dH0, double dbeta,
+                       double* dLogW)
 {
     ScopedKernelClock kc(ctx, "ais");
-    hipError_t e = dca_energy_pairs_device(ctx, src, kind, dtype, L, q, ld, ch.dState, ch.n, ch.nS, dSlabs);
+    hipError_t e = dca_energy_pairs_device(ctx, ps, ch.dState, ch.n, ch.nS, dSlabs);
     if (e != hipSuccess) return e;
-    if (dtype == DCA_F32)
-        hipLaunchKernelGGL(ais_weight_kernel<float>, dim3(ceil_div(ch.n, 256)), dim3(256), 0, ctx->stream, static_cast<const float*>(src),
-                           mfh, kind, L, q, ch.dState, ch.n, ch.nS, dSlabs, G, dH0, dbeta, dLogW);
-    else
-        hipLaunchKernelGGL(ais_weight_kernel<double>, dim3(ceil_div(ch.n, 256)), dim3(256), 0, ctx->stream, static_cast<const double*>(src),
-                           mfh, kind, L, q, ch.dState, ch.n, ch.nS, dSlabs, G, dH0, dbeta, dLogW);
+    with_source_type(ps, [&](auto pv) {
+        hipLaunchKernelGGL(ais_weight_kernel, dim3(ceil_div(ch.n, 256)), dim3(256), 0, ctx->stream, pv, ch.dState, ch.n, ch.nS, dSlabs, G,
+                           dH0, dbeta, dLogW);
+    });
     return hipGetLastError();
 }
 
 // the model's own fields h (L x q, gap included) on the host
-int model_fields(dca_ctx* ctx, const void* src, int kind, int dtype, const double* mfh, int L, int q, std::vector<double>& h)
+int model_fields(dca_ctx* ctx, const PottsSource& ps, std::vector<double>& h)
 {
+    const int L = ps.L, q = ps.q;
     h.assign((size_t)L * q, 0.0);
     hipError_t e = hipStreamSynchronize(ctx->stream);
-    if (kind == 0 && dtype == DCA_F32) {
+    if (ps.kind == 0 && ps.dtype == DCA_F32) {
         std::vector<float> f((size_t)L * q);
-        if (e == hipSuccess) e = hipMemcpy(f.data(), src, f.size() * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(f.data(), ps.src, f.size() * sizeof(float), hipMemcpyDeviceToHost);
         for (size_t k = 0; k < f.size(); ++k) h[k] = (double)f[k];
-    } else if (kind == 0) {
-        if (e == hipSuccess) e = hipMemcpy(h.data(), src, h.size() * sizeof(double), hipMemcpyDeviceToHost);
+    } else if (ps.kind == 0) {
+        if (e == hipSuccess) e = hipMemcpy(h.data(), ps.src, h.size() * sizeof(double), hipMemcpyDeviceToHost);
     } else {
         std::vector<double> f((size_t)L * (q - 1));
-        if (e == hipSuccess) e = hipMemcpy(f.data(), mfh, f.size() * sizeof(double), hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(f.data(), ps.mfh, f.size() * sizeof(double), hipMemcpyDeviceToHost);
         for (int i = 0; i < L; ++i)
             for (int a = 0; a < q - 1; ++a) h[(size_t)i * q + a] = f[(size_t)i * (q - 1) + a];
     }
@@ -103,9 +95,10 @@ int model_fields(dca_ctx* ctx, const void* src, int kind, int dtype, const doubl
 
 }  // namespace
 
-int dca_potts_ais(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
-                  const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
+int dca_potts_ais(dca_ctx* ctx, const PottsSource& ps, const dca_ais_args* args, double* log_weights_out, double* log_z0_out,
+                  uint8_t* chains_out)
 {
+    const int L = ps.L, q = ps.q;
     if (!args || !log_weights_out) { dca_set_error("ais: args or log_weights_out is NULL"); return DCA_ERR_ARG; }
     const int n = args->chains, K = args->temperatures, s = args->sweeps_per_temperature;
     if (n < 1 || n > kAisMaxChains || K < 1 || s < 0) {
@@ -134,13 +127,13 @@ int dca_potts_ais(dca_ctx* ctx, const void* src, int src_kind, int dtype, const 
         for (size_t k = 0; k < h0.size(); ++k)
             if (!std::isfinite(h0[k])) { dca_set_error("ais: base field %zu is not finite", k); return DCA_ERR_ARG; }
     } else {
-        DCA_TRY(model_fields(ctx, src, src_kind, dtype, dMfFields, L, q, h0));
+        DCA_TRY(model_fields(ctx, ps, h0));
     }
     if (log_z0_out) *log_z0_out = dca_ais_log_z0(h0.data(), L, q);
 
     DcaChains ch;
     ch.n = n; ch.L = L; ch.nS = (int)round_up((size_t)n, kAisStride);
-    const int G = dca_energy_slab_count(L, q, dtype);
+    const int G = dca_energy_slab_count(ps);
     double *dH0 = nullptr, *dLogW = nullptr, *dSlabs = nullptr;
     const size_t sites = (size_t)L * ch.nS;
     hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&ch.dState), sites, false);
@@ -157,11 +150,10 @@ int dca_potts_ais(dca_ctx* ctx, const void* src, int src_kind, int dtype, const 
     }
     int rc = e == hipSuccess ? DCA_OK : DCA_ERR_HIP;
     for (int k = 1; k <= K && rc == DCA_OK; ++k) {
-        e = weight_step(ctx, src, src_kind, dtype, dMfFields, L, q, ld, ch, dSlabs, G, dH0, beta[k] - beta[k - 1], dLogW);
+        e = weight_step(ctx, ps, ch, dSlabs, G, dH0, beta[k] - beta[k - 1], dLogW);
         if (e != hipSuccess) { rc = DCA_ERR_HIP; break; }
         if (k < K && s > 0)
-            rc = dca_chains_sweeps(ctx, ch, src, src_kind, dtype, dMfFields, q, ld, s, args->seed, args->first_chain,
-                                   (uint64_t)(k - 1) * (uint64_t)s, 1.0, dH0, beta[k]);
+            rc = dca_chains_sweeps(ctx, ch, ps, s, args->seed, args->first_chain, (uint64_t)(k - 1) * (uint64_t)s, 1.0, dH0, beta[k]);
     }
     if (rc == DCA_OK) {
         e = hipMemcpyAsync(log_weights_out, dLogW, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);

@@ -39,11 +39,6 @@ constexpr int kSSlices = 4;                        // sampler: lanes per chain (
 constexpr int kSChainsPerWave = 64 / kSSlices;
 constexpr int kDotBlocks = 256;
 
-__device__ __forceinline__ size_t pair_index(int L, int i, int j)
-{
-    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
-}
-
 // site-major copy of n rows (row stride ld): QT[s * NpS + k], zero past n
 __global__ void ar_sites_kernel(const uint8_t* __restrict__ rows, size_t ld, int n, int L, int NpS, uint8_t* __restrict__ QT)
 {

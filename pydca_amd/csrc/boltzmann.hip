@@ -20,11 +20,6 @@ namespace {
 constexpr int kBmThreads = 256;
 constexpr int kBmSums = 6;                 // slab: max |d|, sum Cd, sum Cm, sum Cd^2, sum Cm^2, sum Cd Cm
 
-__device__ __forceinline__ size_t pair_index(int L, int i, int j)
-{
-    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
-}
-
 // theta' = theta + eta * ((f - g) - mu * theta), every step in double, rounded once to S
 template <typename S>
 __device__ __forceinline__ void bm_update(S* p, double d, double eta, double mu)
@@ -227,6 +222,9 @@ hipError_t bm_stats(dca_ctx* ctx, BmRun* r, S* x, int slot, double* gij)
 
 bool finite_nonneg(double v) { return v >= 0.0 && std::isfinite(v); }
 
+// the x a run learns, as the sampler's source
+PottsSource bm_model(const BmRun* r, const void* dx) { return PottsSource{dx, 0, r->dtype, nullptr, r->L, r->q, 0}; }
+
 }  // namespace
 
 void dca_bm_free(dca_ctx* ctx)
@@ -247,12 +245,7 @@ int dca_bm_begin_impl(dca_ctx* ctx, void* dx, int dtype, const dca_bm_args* a)
                       a->chains, a->sweeps, a->equilibration_sweeps, a->eta_h, a->eta_J, a->mu_h, a->mu_J, a->pseudocount);
         return DCA_ERR_ARG;
     }
-    if (a->initial)
-        for (size_t k = 0; k < (size_t)a->chains * L; ++k)
-            if (a->initial[k] >= q) {
-                dca_set_error("dca_plm_bm_begin: initial code %d >= q at element %zu", (int)a->initial[k], k);
-                return DCA_ERR_ARG;
-            }
+    if (a->initial) DCA_TRY(dca_check_codes(a->initial, (size_t)a->chains * L, q, "dca_plm_bm_begin: initial "));
     BmRun* r = new BmRun();
     r->L = L; r->q = q; r->dtype = dtype;
     r->k = a->sweeps; r->E = a->equilibration_sweeps; r->seed = a->seed;
@@ -278,7 +271,7 @@ int dca_bm_begin_impl(dca_ctx* ctx, void* dx, int dtype, const dca_bm_args* a)
         if (rc != DCA_OK) return fail(rc);
     }
     int rc = dca_chains_start(ctx, &r->ch, a->chains, L, q, a->seed, 0, a->initial);
-    if (rc == DCA_OK) rc = dca_chains_sweeps(ctx, r->ch, dx, 0, dtype, nullptr, q, 0, r->E, r->seed, 0, 0, 1.0);
+    if (rc == DCA_OK) rc = dca_chains_sweeps(ctx, r->ch, bm_model(r, dx), r->E, r->seed, 0, 0, 1.0);
     if (rc == DCA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { dca_set_error("dca_plm_bm_begin: stream failed"); rc = DCA_ERR_HIP; }
     if (rc != DCA_OK) return fail(rc);
     ctx->bm = r;
@@ -298,7 +291,7 @@ int dca_bm_iterate_impl(dca_ctx* ctx, void* dx, int iterations, dca_bm_record* r
     }
     for (int it = 0; it < iterations; ++it) {
         const uint64_t first = (uint64_t)r->E + (uint64_t)r->t * (uint64_t)r->k;
-        DCA_TRY(dca_chains_sweeps(ctx, r->ch, dx, 0, r->dtype, nullptr, r->q, 0, r->k, r->seed, 0, first, 1.0));
+        DCA_TRY(dca_chains_sweeps(ctx, r->ch, bm_model(r, dx), r->k, r->seed, 0, first, 1.0));
         const hipError_t e = r->dtype == DCA_F32 ? bm_stats<float, true>(ctx, r, static_cast<float*>(dx), it, nullptr)
                                                  : bm_stats<double, true>(ctx, r, static_cast<double*>(dx), it, nullptr);
         if (e != hipSuccess) { dca_set_error("dca_plm_bm_iterate: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }

@@ -506,28 +506,36 @@ int dca_plm_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out
     CHECK_CTX(ctx);
     DCA_TRY(need_plm(ctx));
     if (n < 0 || (n > 0 && (!X || !energies_out))) return DCA_ERR_ARG;
-    return ctx->plm->energies(X, n, energies_out);
+    PottsSource ps;
+    DCA_TRY(ctx->plm->potts_source(&ps, false));
+    return dca_potts_energies(ctx, ps, X, n, energies_out);
 }
 int dca_plm_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out)
 {
     CHECK_CTX(ctx);
     DCA_TRY(need_plm(ctx));
     if (!wildtype || !dE_out) return DCA_ERR_ARG;
-    return ctx->plm->mutation_scan(wildtype, dE_out);
+    PottsSource ps;
+    DCA_TRY(ctx->plm->potts_source(&ps, false));
+    return dca_potts_mutation_scan(ctx, ps, wildtype, dE_out);
 }
 int dca_plm_pseudo_likelihood(dca_ctx* ctx, const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out)
 {
     CHECK_CTX(ctx);
     DCA_TRY(need_plm(ctx));
     if (n < 0 || (n > 0 && (!X || !pll_out))) return DCA_ERR_ARG;
-    return ctx->plm->pseudo_likelihood(X, n, pll_out, site_out, cond_out);
+    PottsSource ps;
+    DCA_TRY(ctx->plm->potts_source(&ps, false));
+    return dca_potts_pseudo_likelihood(ctx, ps, X, n, pll_out, site_out, cond_out);
 }
 int dca_plm_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                    const uint8_t* initial, uint8_t* out)
 {
     CHECK_CTX(ctx);
     DCA_TRY(need_plm(ctx));
-    return ctx->plm->sample(n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
+    PottsSource ps;
+    DCA_TRY(ctx->plm->potts_source(&ps, false));
+    return dca_potts_sample(ctx, ps, n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
 }
 // annealed importance sampling (ais.hip) of the plm engine's x
 int dca_plm_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
@@ -535,7 +543,9 @@ int dca_plm_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out,
     CHECK_CTX(ctx);
     DCA_TRY(need_plm(ctx));
     if (!args || !log_weights_out) { dca_set_error("dca_plm_ais: args or log_weights_out is NULL"); return DCA_ERR_ARG; }
-    return ctx->plm->ais(args, log_weights_out, log_z0_out, chains_out);
+    PottsSource ps;
+    DCA_TRY(ctx->plm->potts_source(&ps, true));
+    return dca_potts_ais(ctx, ps, args, log_weights_out, log_z0_out, chains_out);
 }
 // Boltzmann learning (boltzmann.hip) on the plm engine's x
 int dca_plm_bm_begin(dca_ctx* ctx, const dca_bm_args* args)
@@ -575,6 +585,19 @@ static int need_mf(dca_ctx* ctx)
     if (!ctx->mf) ctx->mf = dca_make_mf_engine(ctx);
     return ctx->mf ? DCA_OK : DCA_ERR_NOMEM;
 }
+// the mean-field model for the dca_potts_* calls; its device fields live until the call's stream work has drained
+struct MfPotts {
+    dca_ctx* ctx = nullptr;
+    PottsSource ps{};
+    double* dH = nullptr;
+    int get(dca_ctx* c) { ctx = c; return dca_mf_engine_potts_source(c->mf, &ps, &dH); }
+    ~MfPotts()
+    {
+        if (!dH) return;
+        hipStreamSynchronize(ctx->stream);
+        dca_dev_free(dH);
+    }
+};
 int dca_mf_single_site_freqs(dca_ctx* ctx, double* fi_out) { CHECK_CTX(ctx); DCA_TRY(need_mf(ctx)); return dca_mf_engine_site_freqs(ctx->mf, fi_out); }
 int dca_mf_pair_site_freqs(dca_ctx* ctx, double* fij_out) { CHECK_CTX(ctx); DCA_TRY(need_mf(ctx)); return dca_mf_engine_pair_freqs(ctx->mf, fij_out); }
 int dca_mf_corr_mat(dca_ctx* ctx, double pseudocount, double* corr_out) { CHECK_CTX(ctx); DCA_TRY(need_mf(ctx)); return dca_mf_engine_corr(ctx->mf, pseudocount, corr_out); }
@@ -691,35 +714,45 @@ int dca_mf_energies(dca_ctx* ctx, const uint8_t* X, int n, double* energies_out)
     CHECK_CTX(ctx);
     DCA_TRY(need_mf(ctx));
     if (n < 0 || (n > 0 && (!X || !energies_out))) return DCA_ERR_ARG;
-    return dca_mf_engine_energies(ctx->mf, X, n, energies_out);
+    MfPotts m;
+    DCA_TRY(m.get(ctx));
+    return dca_potts_energies(ctx, m.ps, X, n, energies_out);
 }
 int dca_mf_mutation_scan(dca_ctx* ctx, const uint8_t* wildtype, double* dE_out)
 {
     CHECK_CTX(ctx);
     DCA_TRY(need_mf(ctx));
     if (!wildtype || !dE_out) return DCA_ERR_ARG;
-    return dca_mf_engine_mutation_scan(ctx->mf, wildtype, dE_out);
+    MfPotts m;
+    DCA_TRY(m.get(ctx));
+    return dca_potts_mutation_scan(ctx, m.ps, wildtype, dE_out);
 }
 int dca_mf_pseudo_likelihood(dca_ctx* ctx, const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out)
 {
     CHECK_CTX(ctx);
     DCA_TRY(need_mf(ctx));
     if (n < 0 || (n > 0 && (!X || !pll_out))) return DCA_ERR_ARG;
-    return dca_mf_engine_pseudo_likelihood(ctx->mf, X, n, pll_out, site_out, cond_out);
+    MfPotts m;
+    DCA_TRY(m.get(ctx));
+    return dca_potts_pseudo_likelihood(ctx, m.ps, X, n, pll_out, site_out, cond_out);
 }
 int dca_mf_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                   const uint8_t* initial, uint8_t* out)
 {
     CHECK_CTX(ctx);
     DCA_TRY(need_mf(ctx));
-    return dca_mf_engine_sample(ctx->mf, n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
+    MfPotts m;
+    DCA_TRY(m.get(ctx));
+    return dca_potts_sample(ctx, m.ps, n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
 }
 int dca_mf_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
 {
     CHECK_CTX(ctx);
     DCA_TRY(need_mf(ctx));
     if (!args || !log_weights_out) { dca_set_error("dca_mf_ais: args or log_weights_out is NULL"); return DCA_ERR_ARG; }
-    return dca_mf_engine_ais(ctx->mf, args, log_weights_out, log_z0_out, chains_out);
+    MfPotts m;
+    DCA_TRY(m.get(ctx));
+    return dca_potts_ais(ctx, m.ps, args, log_weights_out, log_z0_out, chains_out);
 }
 int dca_mf_pair_couplings(dca_ctx* ctx, const int* pairs, int npairs, int shift, double* out)
 {

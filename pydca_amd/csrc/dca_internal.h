@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/dca_hip.h"
+#include "potts_source.h"
 
 void dca_set_error(const char* fmt, ...);
 
@@ -170,17 +171,12 @@ struct PlmEngineBase {
     virtual int scores(int apc, double* out) = 0;
     virtual int di_scores(const double* reg_fi, int apc, double* out) = 0;
     virtual int pair_couplings(const int* pairs, int npairs, int shift, double* out) = 0;
-    virtual int energies(const uint8_t* X, int n, double* out) = 0;            // energy.hip on the current x
-    virtual int mutation_scan(const uint8_t* wildtype, double* out) = 0;
-    virtual int pseudo_likelihood(const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out) = 0;   // pll.hip
-    virtual int sample(int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
-                       const uint8_t* initial, uint8_t* out) = 0;                  // sample.hip on the current x
+    // the current x as a Potts source (energy.hip, pll.hip, sample.hip, ais.hip); column strips gather x first, as scores() does.
+    // one_gpu_only (AIS): DCA_ERR_STATE under column strips, vector sharding, a reduce / comm hook or a native-comm mode instead
+    virtual int potts_source(PottsSource* out, bool one_gpu_only) = 0;
     // the device x a Boltzmann-learning run updates in place; DCA_ERR_STATE (with the reason) unconfigured, during an L-BFGS
     // run, under column strips, vector sharding, a reduce / comm hook or a native-comm mode
     virtual int bm_source(void** dx) = 0;
-    // annealed importance sampling of the current x (ais.hip); DCA_ERR_STATE unconfigured, under column strips, vector sharding,
-    // a reduce / comm hook or a native-comm mode
-    virtual int ais(const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out) = 0;
     virtual int set_vector_sharding(int rank, int world, dca_comm_hook hook, void* user) = 0;
     dca_reduce_hook hook = nullptr;
     void* hook_user = nullptr;
@@ -192,7 +188,7 @@ struct PlmEngineBase {
 PlmEngineBase* dca_make_plm_engine(dca_ctx* ctx);
 
 // ---- scoring.hip
-// FN of (q-1)x(q-1) blocks.  src_kind 0: packed plm vector of element type `dtype`
+// FN of (q-1)x(q-1) blocks.  Source kind 0: packed plm vector of element type `dtype`
 // (DCA_F32/DCA_F64); 1: dense n x n double couplings with leading dimension ld.
 int dca_fn_scores(dca_ctx* ctx, const void* src, int src_kind, int dtype, int L, int q, int ld,
                   int apc, double* dScoresOut /* device, pairs */);
@@ -204,28 +200,24 @@ int dca_pair_blocks(dca_ctx* ctx, const void* src, int src_kind, int dtype, int 
                     int shift, double* out /* host */);
 
 // ---- energy.hip : Potts energies of host query rows (n x L codes < q) and single-mutant scans of a wild type (L codes).
-// Same source conventions as dca_fn_scores; src_kind 1 also takes the mf fields (device, L*(q-1) doubles).  out: host.
-int dca_potts_energies(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
-                       const uint8_t* X, int n, double* out);
-int dca_potts_mutation_scan(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
-                            const uint8_t* wildtype, double* out /* L*q */);
+// The model: a PottsSource (potts_source.h).  out: host.
+int dca_potts_energies(dca_ctx* ctx, const PottsSource& ps, const uint8_t* X, int n, double* out);
+int dca_potts_mutation_scan(dca_ctx* ctx, const PottsSource& ps, const uint8_t* wildtype, double* out /* L*q */);
 
 // ---- pll.hip : site conditionals and pseudo-log-likelihoods of host query rows under the same sources (dca_plm_pseudo_likelihood
 // semantics).  site_out (n*L) and cond_out (n*L*q) may be NULL; all outputs on the host.
-int dca_potts_pseudo_likelihood(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
-                                const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out);
+int dca_potts_pseudo_likelihood(dca_ctx* ctx, const PottsSource& ps, const uint8_t* X, int n, double* pll_out, double* site_out,
+                                double* cond_out);
 
 // The pair stage of dca_potts_energies on device codes QT[s * NqS + k] (k < nq, NqS a multiple of 128): slab g of query k at
-// dSlabs[g * NqS + k], g < dca_energy_slab_count(L, q, dtype).  E(k) = sum_i h_i (ascending i) + sum_g slab (ascending g) is then
+// dSlabs[g * NqS + k], g < dca_energy_slab_count(ps).  E(k) = sum_i h_i (ascending i) + sum_g slab (ascending g) is then
 // bit for bit what dca_potts_energies returns for those codes.
-int dca_energy_slab_count(int L, int q, int dtype);
-hipError_t dca_energy_pairs_device(dca_ctx* ctx, const void* src, int src_kind, int dtype, int L, int q, int ld, const uint8_t* dQT, int nq,
-                                   int NqS, double* dSlabs);
+int dca_energy_slab_count(const PottsSource& ps);
+hipError_t dca_energy_pairs_device(dca_ctx* ctx, const PottsSource& ps, const uint8_t* dQT, int nq, int NqS, double* dSlabs);
 
 // ---- sample.hip : Gibbs sampling of n chains (one launch per sweep) under the same sources.  initial / out: host, n x L.
-int dca_potts_sample(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld, int n,
-                     int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
-                     const uint8_t* initial /* host n*L or NULL */, uint8_t* out /* host n*L */);
+int dca_potts_sample(dca_ctx* ctx, const PottsSource& ps, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep,
+                     double beta, const uint8_t* initial /* host n*L or NULL */, uint8_t* out /* host n*L */);
 
 // Philox4x32-10 of the samplers (sample.hip, ais.hip): key = (seed lo, seed hi), counter = (chain, sweep, site, tag), each
 // word the value mod 2^32; U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  Tags: 0 Gibbs draw, 1 random start, 2 AIS start,
@@ -259,15 +251,14 @@ static __device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t 
 // uses multiples of 128, the energy kernels' stride).
 struct DcaChains { int n = 0, L = 0, nS = 0; uint8_t* dState = nullptr; };
 int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial);
-int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const void* src, int src_kind, int dtype, const double* dMfFields, int q, int ld,
-                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
-                      const double* dBase = nullptr, double bk = 0.0);
+int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const PottsSource& ps, int sweeps, uint64_t seed, uint64_t first_chain,
+                      uint64_t first_sweep, double beta, const double* dBase = nullptr, double bk = 0.0);
 int dca_chains_read(dca_ctx* ctx, const DcaChains& ch, uint8_t* out);
 void dca_chains_free(DcaChains* ch);
 
 // ---- ais.hip : annealed importance sampling of log Z under the same sources (dca_plm_ais / dca_mf_ais; arguments checked here)
-int dca_potts_ais(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
-                  const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out);
+int dca_potts_ais(dca_ctx* ctx, const PottsSource& ps, const dca_ais_args* args, double* log_weights_out, double* log_z0_out,
+                  uint8_t* chains_out);
 double dca_ais_log_z0(const double* h0, int L, int q);    // host, L x q base fields
 
 // ---- boltzmann.hip : Boltzmann machine learning of the plm vector (dca_plm_bm_*).  The run lives in ctx->bm; dca_bm_free ends
@@ -304,15 +295,12 @@ void dca_mf_engine_set_native(MfEngine*, bool on);
 int dca_mf_engine_set_row_window(MfEngine*, int first, int count);   // count < 0: all rows
 void dca_mf_engine_invalidate(MfEngine*);      // weights changed: counts, frequencies, C and J are recomputed on demand
 int dca_mf_engine_pair_couplings(MfEngine*, const int* pairs, int npairs, int shift, double* out);
-int dca_mf_engine_energies(MfEngine*, const uint8_t* X, int n, double* out);
-int dca_mf_engine_mutation_scan(MfEngine*, const uint8_t* wildtype, double* out);
-int dca_mf_engine_pseudo_likelihood(MfEngine*, const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out);
+// the mean-field model as a Potts source: J = -inv(C), h = the fields of dca_mf_engine_fields in a device buffer allocated here
+// (*dH_owned; the caller frees it once the stream has drained)
+int dca_mf_engine_potts_source(MfEngine*, PottsSource* out, double** dH_owned);
 // data statistics of a Boltzmann-learning run from this engine's weighted counts (dca_plm_bm_begin): device outputs
 // fi (L*q) = (1 - lambda) * f_i + lambda / q and fij (pairs*q*q, pair order, gap included) = (1 - lambda) * f_ij + lambda / q^2
 int dca_mf_engine_bm_freqs(MfEngine*, double lambda, double* dFi, double* dFij);
-int dca_mf_engine_sample(MfEngine*, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
-                         const uint8_t* initial, uint8_t* out);
-int dca_mf_engine_ais(MfEngine*, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out);
 
 // ---- cholinv.hip : scale * inverse of an SPD matrix on the device (f64 MFMA)
 // dA: n x n row-major (ld = n), n multiple of 64; destroyed (holds the triangular factor's inverse afterwards).

@@ -1,9 +1,7 @@
 // Statistical energies of query sequences and single-mutant scans under a fitted Potts model:
 //   E(s) = sum_i h_i(s_i) + sum_{i<j} J_ij(s_i, s_j),
 //   dE(i,a) = h_i(a) - h_i(w_i) + sum_{j != i} [J_ij(a, w_j) - J_ij(w_i, w_j)].
-// Parameter sources (as in scoring.hip): kind 0 = the packed plm vector x (fields L*q first, then the upper-triangle q x q
-// blocks in pair order), element type float or double; kind 1 = the dense mf couplings -inv(C) (double, leading dimension ld,
-// (q-1) x (q-1) blocks) with the mf fields (L*(q-1) doubles); both are zero on the gap state q-1.
+// The model arrives as a PottsSource and is read through PottsView (potts_source.h).
 //
 // Every term is widened to double and summed in double in an order fixed by (L, q, dtype) alone:
 //   pair kernel: the site pairs are cut into TS x TS tiles (site blocks bi <= bj, row-major), the tiles into G groups of
@@ -25,37 +23,6 @@ constexpr int kESeqBlock = kEThreads * kESeqPerThread;
 constexpr size_t kETileBudget = 72 * 1024;         // LDS per tile: two workgroups per CU (160 KiB), one loads while one gathers
 constexpr int kETargetGroups = 128;                // tile groups (slabs) for large L
 constexpr int kEChunk = 16 * kESeqBlock;           // query sequences per pass (bounds the slabs: G x 65536 doubles)
-
-__host__ __device__ __forceinline__ size_t pair_index(int L, int i, int j)
-{
-    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
-}
-
-// J_ij(a, b) for i < j, widened to double
-template <typename S>
-__device__ __forceinline__ double coupling(const S* src, int kind, int L, int q, int ld, int i, int j, int a, int b)
-{
-    if (kind == 0) return (double)src[(size_t)L * q + pair_index(L, i, j) * (size_t)q * q + (size_t)a * q + b];
-    const int qm = q - 1;
-    if (a == qm || b == qm) return 0.0;
-    return (double)src[(size_t)(i * qm + a) * ld + (size_t)j * qm + b];
-}
-
-template <typename S>
-__device__ __forceinline__ double field(const S* src, const double* mfh, int kind, int q, int i, int a)
-{
-    if (kind == 0) return (double)src[(size_t)i * q + a];
-    return a == q - 1 ? 0.0 : mfh[(size_t)i * (q - 1) + a];
-}
-
-// site-major copy of n query rows (n x L bytes): QT[s * NqS + k], zero past n
-__global__ void query_sites_kernel(const uint8_t* __restrict__ rows, int n, int L, int NqS, uint8_t* __restrict__ QT)
-{
-    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (t >= (size_t)L * NqS) return;
-    const int s = (int)(t / NqS), k = (int)(t % NqS);
-    QT[t] = k < n ? rows[(size_t)k * L + s] : 0;
-}
 
 // grid (G, sequence blocks).  LDS: one tile, TS*TS pairs of q*q values of type S (pair (ii, jj) at (ii*TS + jj) * q*q).
 template <typename S, int TS>
@@ -86,7 +53,7 @@ void energy_pairs_kernel(const S* __restrict__ src, int kind, int L, int q, int 
             const int k = e / qq, ab = e - k * qq;
             const int ii = k / TS, jj = k - ii * TS;
             S v = (S)0;
-            if (ii < ni && jj < nj && (!diag || jj > ii)) v = (S)coupling(src, kind, L, q, ld, i0 + ii, j0 + jj, ab / q, ab % q);
+            if (ii < ni && jj < nj && (!diag || jj > ii)) v = (S)potts_coupling(src, kind, L, q, ld, i0 + ii, j0 + jj, ab / q, ab % q);
             tile[e] = v;
         }
         __syncthreads();
@@ -120,14 +87,13 @@ void energy_pairs_kernel(const S* __restrict__ src, int kind, int L, int q, int 
 // E(n) = sum_i h_i(s_i) (ascending i) + sum_g slab[g][n] (ascending g)
 template <typename S>
 __global__ __launch_bounds__(256)
-void energy_finish_kernel(const S* __restrict__ src, const double* __restrict__ mfh, int kind, int L, int q,
-                          const uint8_t* __restrict__ QT, int nq, int NqS, const double* __restrict__ slabs, int G,
-                          double* __restrict__ out)
+void energy_finish_kernel(const PottsView<S> pv, const uint8_t* __restrict__ QT, int nq, int NqS, const double* __restrict__ slabs,
+                          int G, double* __restrict__ out)
 {
     const int n = blockIdx.x * 256 + threadIdx.x;
     if (n >= nq) return;
     double e = 0.0;
-    for (int i = 0; i < L; ++i) e += field(src, mfh, kind, q, i, QT[(size_t)i * NqS + n]);
+    for (int i = 0; i < pv.L; ++i) e += pv.field(i, QT[(size_t)i * NqS + n]);
     for (int g = 0; g < G; ++g) e += slabs[(size_t)g * NqS + n];
     out[n] = e;
 }
@@ -136,19 +102,19 @@ void energy_finish_kernel(const S* __restrict__ src, const double* __restrict__ 
 // pair, as the energy reads it), dE(i, a) = (h_i(a) - h_i(w_i)) + (S(a) - S(w_i)); dE(i, w_i) = 0.
 template <typename S>
 __global__ __launch_bounds__(64)
-void mutation_scan_kernel(const S* __restrict__ src, const double* __restrict__ mfh, int kind, int L, int q, int ld,
-                          const uint8_t* __restrict__ wt, double* __restrict__ dE)
+void mutation_scan_kernel(const PottsView<S> pv, const uint8_t* __restrict__ wt, double* __restrict__ dE)
 {
     __shared__ double sumW, hW;
+    const int L = pv.L, q = pv.q;
     const int i = blockIdx.x, a = threadIdx.x;
     const int wi = wt[i];
     double s = 0.0, h = 0.0;
     if (a < q) {
         for (int j = 0; j < L; ++j) {
             if (j == i) continue;
-            s += j > i ? coupling(src, kind, L, q, ld, i, j, a, wt[j]) : coupling(src, kind, L, q, ld, j, i, wt[j], a);
+            s += j > i ? pv.coupling(i, j, a, wt[j]) : pv.coupling(j, i, wt[j], a);
         }
-        h = field(src, mfh, kind, q, i, a);
+        h = pv.field(i, a);
         if (a == wi) { sumW = s; hW = h; }
     }
     __syncthreads();
@@ -171,43 +137,36 @@ EnergyGeom energy_geometry(int L, int q, size_t elem)
 }
 
 template <typename S, int TS>
-hipError_t launch_pairs(dca_ctx* ctx, const EnergyGeom& eg, const S* src, int kind, int L, int q, int ld, const uint8_t* QT, int nq,
-                        int NqS, double* slabs)
+hipError_t launch_pairs(dca_ctx* ctx, const EnergyGeom& eg, const PottsView<S>& pv, const uint8_t* QT, int nq, int NqS, double* slabs)
 {
-    const size_t lds = (size_t)TS * TS * q * q * sizeof(S);
+    const size_t lds = (size_t)TS * TS * pv.q * pv.q * sizeof(S);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(energy_pairs_kernel<S, TS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((energy_pairs_kernel<S, TS>), dim3(eg.G, ceil_div(nq, kESeqBlock)), dim3(kEThreads), lds, ctx->stream,
-                       src, kind, L, q, ld, QT, nq, NqS, eg.nb, eg.ntiles, eg.tpg, slabs);
+                       pv.src, pv.kind, pv.L, pv.q, pv.ld, QT, nq, NqS, eg.nb, eg.ntiles, eg.tpg, slabs);
     return hipGetLastError();
 }
 
 template <typename S>
-hipError_t dispatch_pairs(dca_ctx* ctx, const EnergyGeom& eg, const S* src, int kind, int L, int q, int ld, const uint8_t* QT, int nq,
-                          int NqS, double* slabs)
+hipError_t dispatch_pairs(dca_ctx* ctx, const PottsView<S>& pv, const uint8_t* QT, int nq, int NqS, double* slabs)
 {
+    const EnergyGeom eg = energy_geometry(pv.L, pv.q, sizeof(S));
     switch (eg.TS) {
-    case 24: return launch_pairs<S, 24>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
-    case 16: return launch_pairs<S, 16>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
-    case 12: return launch_pairs<S, 12>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
-    case 8: return launch_pairs<S, 8>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
-    case 6: return launch_pairs<S, 6>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
-    case 4: return launch_pairs<S, 4>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
-    default: return launch_pairs<S, 3>(ctx, eg, src, kind, L, q, ld, QT, nq, NqS, slabs);
+    case 24: return launch_pairs<S, 24>(ctx, eg, pv, QT, nq, NqS, slabs);
+    case 16: return launch_pairs<S, 16>(ctx, eg, pv, QT, nq, NqS, slabs);
+    case 12: return launch_pairs<S, 12>(ctx, eg, pv, QT, nq, NqS, slabs);
+    case 8: return launch_pairs<S, 8>(ctx, eg, pv, QT, nq, NqS, slabs);
+    case 6: return launch_pairs<S, 6>(ctx, eg, pv, QT, nq, NqS, slabs);
+    case 4: return launch_pairs<S, 4>(ctx, eg, pv, QT, nq, NqS, slabs);
+    default: return launch_pairs<S, 3>(ctx, eg, pv, QT, nq, NqS, slabs);
     }
 }
 
-int check_codes(const uint8_t* X, size_t count, int q)
-{
-    for (size_t k = 0; k < count; ++k)
-        if (X[k] >= q) { dca_set_error("code %d >= q at element %zu", (int)X[k], k); return DCA_ERR_ARG; }
-    return DCA_OK;
-}
-
 template <typename S>
-int energies_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q, int ld, const uint8_t* X, int n, double* out)
+int energies_t(dca_ctx* ctx, const PottsView<S>& pv, const uint8_t* X, int n, double* out)
 {
-    const EnergyGeom eg = energy_geometry(L, q, sizeof(S));
+    const int L = pv.L;
+    const EnergyGeom eg = energy_geometry(L, pv.q, sizeof(S));
     const int cap = std::min(n, kEChunk);
     const int NqS = (int)round_up((size_t)cap, 128);
     uint8_t *dRows = nullptr, *dQT = nullptr;
@@ -220,14 +179,14 @@ int energies_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, i
         const int nq = std::min(cap, n - first);
         e = hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) break;
-        const size_t total = (size_t)L * NqS;
-        hipLaunchKernelGGL(query_sites_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dRows, nq, L, NqS, dQT);
+        e = dca_rows_to_sites(ctx, dRows, nq, L, NqS, dQT);
+        if (e != hipSuccess) break;
         {
             ScopedKernelClock kc(ctx, "energies");
-            e = dispatch_pairs<S>(ctx, eg, src, kind, L, q, ld, dQT, nq, NqS, dSlabs);
+            e = dispatch_pairs<S>(ctx, pv, dQT, nq, NqS, dSlabs);
             if (e == hipSuccess)
-                hipLaunchKernelGGL(energy_finish_kernel<S>, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, src, mfh, kind, L, q, dQT, nq,
-                                   NqS, dSlabs, eg.G, dOut);
+                hipLaunchKernelGGL(energy_finish_kernel<S>, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, pv, dQT, nq, NqS, dSlabs,
+                                   eg.G, dOut);
         }
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess) e = hipMemcpyAsync(out + first, dOut, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
@@ -239,8 +198,9 @@ int energies_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, i
 }
 
 template <typename S>
-int mutation_scan_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q, int ld, const uint8_t* wt, double* out)
+int mutation_scan_t(dca_ctx* ctx, const PottsView<S>& pv, const uint8_t* wt, double* out)
 {
+    const int L = pv.L, q = pv.q;
     uint8_t* dWt = nullptr;
     double* dOut = nullptr;
     hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dWt), (size_t)L);
@@ -248,7 +208,7 @@ int mutation_scan_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int
     if (e == hipSuccess) e = hipMemcpyAsync(dWt, wt, (size_t)L, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) {
         ScopedKernelClock kc(ctx, "mutation_scan");
-        hipLaunchKernelGGL(mutation_scan_kernel<S>, dim3(L), dim3(64), 0, ctx->stream, src, mfh, kind, L, q, ld, dWt, dOut);
+        hipLaunchKernelGGL(mutation_scan_kernel<S>, dim3(L), dim3(64), 0, ctx->stream, pv, dWt, dOut);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t)L * q * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
@@ -260,38 +220,35 @@ int mutation_scan_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int
 
 }  // namespace
 
-int dca_potts_energies(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
-                       const uint8_t* X, int n, double* out)
+int dca_check_codes(const uint8_t* codes, size_t count, int q, const char* what)
+{
+    for (size_t k = 0; k < count; ++k)
+        if (codes[k] >= q) { dca_set_error("%scode %d >= q at element %zu", what, (int)codes[k], k); return DCA_ERR_ARG; }
+    return DCA_OK;
+}
+
+int dca_potts_energies(dca_ctx* ctx, const PottsSource& ps, const uint8_t* X, int n, double* out)
 {
     if (n < 0 || (n > 0 && (!X || !out))) { dca_set_error("energies: bad arguments"); return DCA_ERR_ARG; }
     if (n == 0) return DCA_OK;
-    DCA_TRY(check_codes(X, (size_t)n * L, q));
-    if (dtype == DCA_F32) return energies_t(ctx, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, X, n, out);
-    return energies_t(ctx, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, X, n, out);
+    DCA_TRY(dca_check_codes(X, (size_t)n * ps.L, ps.q, ""));
+    return with_source_type(ps, [&](auto pv) { return energies_t(ctx, pv, X, n, out); });
 }
 
-int dca_potts_mutation_scan(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
-                            const uint8_t* wt, double* out)
+int dca_potts_mutation_scan(dca_ctx* ctx, const PottsSource& ps, const uint8_t* wt, double* out)
 {
     if (!wt || !out) { dca_set_error("mutation scan: bad arguments"); return DCA_ERR_ARG; }
-    DCA_TRY(check_codes(wt, (size_t)L, q));
-    if (dtype == DCA_F32) return mutation_scan_t(ctx, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, wt, out);
-    return mutation_scan_t(ctx, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, wt, out);
+    DCA_TRY(dca_check_codes(wt, (size_t)ps.L, ps.q, ""));
+    return with_source_type(ps, [&](auto pv) { return mutation_scan_t(ctx, pv, wt, out); });
 }
 
 // ---- the pair stage on device-resident site-major codes (ais.hip): the same kernels, geometry and order as above
-int dca_energy_slab_count(int L, int q, int dtype)
+int dca_energy_slab_count(const PottsSource& ps)
 {
-    return energy_geometry(L, q, dtype == DCA_F32 ? sizeof(float) : sizeof(double)).G;
+    return energy_geometry(ps.L, ps.q, ps.dtype == DCA_F32 ? sizeof(float) : sizeof(double)).G;
 }
 
-hipError_t dca_energy_pairs_device(dca_ctx* ctx, const void* src, int src_kind, int dtype, int L, int q, int ld, const uint8_t* dQT, int nq,
-                                   int NqS, double* dSlabs)
+hipError_t dca_energy_pairs_device(dca_ctx* ctx, const PottsSource& ps, const uint8_t* dQT, int nq, int NqS, double* dSlabs)
 {
-    if (dtype == DCA_F32) {
-        const EnergyGeom eg = energy_geometry(L, q, sizeof(float));
-        return dispatch_pairs<float>(ctx, eg, static_cast<const float*>(src), src_kind, L, q, ld, dQT, nq, NqS, dSlabs);
-    }
-    const EnergyGeom eg = energy_geometry(L, q, sizeof(double));
-    return dispatch_pairs<double>(ctx, eg, static_cast<const double*>(src), src_kind, L, q, ld, dQT, nq, NqS, dSlabs);
+    return with_source_type(ps, [&](auto pv) { return dispatch_pairs(ctx, pv, dQT, nq, NqS, dSlabs); });
 }

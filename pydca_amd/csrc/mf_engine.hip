@@ -14,11 +14,6 @@
 
 namespace {
 
-__host__ __device__ __forceinline__ size_t pair_index(int L, int i, int j)
-{
-    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
-}
-
 // XT[i][n] = X[n][i]  (64x64 byte tiles through LDS; makes per-site passes coalesced)
 __global__ __launch_bounds__(256)
 void mf_transpose_kernel(const uint8_t* __restrict__ X, uint8_t* __restrict__ XT, int N, int L, int Ls, int Nt)
@@ -636,57 +631,12 @@ int dca_mf_engine_fields(MfEngine* m, double* out)
     return DCA_OK;
 }
 
-// Potts energies / single-mutant scan under the mean-field model: J = dJ, h = the fields above, both zero on the gap state
-int dca_mf_engine_energies(MfEngine* m, const uint8_t* X, int n, double* out)
+// The mean-field model as a Potts source: J = dJ, h = the fields above, both zero on the gap state
+int dca_mf_engine_potts_source(MfEngine* m, PottsSource* out, double** dH_owned)
 {
-    double* dH = nullptr;
-    DCA_TRY(mf_fields_device(m, &dH));
-    const int rc = dca_potts_energies(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, X, n, out);
-    hipStreamSynchronize(m->ctx->stream);
-    dca_dev_free(dH);
-    return rc;
-}
-
-int dca_mf_engine_mutation_scan(MfEngine* m, const uint8_t* wildtype, double* out)
-{
-    double* dH = nullptr;
-    DCA_TRY(mf_fields_device(m, &dH));
-    const int rc = dca_potts_mutation_scan(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, wildtype, out);
-    hipStreamSynchronize(m->ctx->stream);
-    dca_dev_free(dH);
-    return rc;
-}
-
-int dca_mf_engine_pseudo_likelihood(MfEngine* m, const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out)
-{
-    double* dH = nullptr;
-    DCA_TRY(mf_fields_device(m, &dH));
-    const int rc = dca_potts_pseudo_likelihood(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, X, n, pll_out, site_out, cond_out);
-    hipStreamSynchronize(m->ctx->stream);
-    dca_dev_free(dH);
-    return rc;
-}
-
-int dca_mf_engine_sample(MfEngine* m, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
-                         const uint8_t* initial, uint8_t* out)
-{
-    double* dH = nullptr;
-    DCA_TRY(mf_fields_device(m, &dH));
-    const int rc = dca_potts_sample(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, n, sweeps, seed, first_chain, first_sweep, beta,
-                                    initial, out);
-    hipStreamSynchronize(m->ctx->stream);
-    dca_dev_free(dH);
-    return rc;
-}
-
-int dca_mf_engine_ais(MfEngine* m, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
-{
-    double* dH = nullptr;
-    DCA_TRY(mf_fields_device(m, &dH));
-    const int rc = dca_potts_ais(m->ctx, m->dJ, 1, DCA_F64, dH, m->L, m->q, m->np, args, log_weights_out, log_z0_out, chains_out);
-    hipStreamSynchronize(m->ctx->stream);
-    dca_dev_free(dH);
-    return rc;
+    DCA_TRY(mf_fields_device(m, dH_owned));
+    *out = PottsSource{m->dJ, 1, DCA_F64, *dH_owned, m->L, m->q, m->np};
+    return DCA_OK;
 }
 
 int dca_mf_engine_pair_couplings(MfEngine* m, const int* pairs, int npairs, int shift, double* out)

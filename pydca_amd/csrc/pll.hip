@@ -2,8 +2,7 @@
 //   u_i(a) = h_i(a) + sum_{j != i} J_ij(a, s_j)          (J read from the pair block (min(i,j), max(i,j)), as energy.hip reads it)
 //   m_i = max_b u_i(b),  Z_i = sum_b exp(u_i(b) - m_i) (ascending b),  cond[i][a] = (u_i(a) - m_i) - log Z_i,
 //   site[i] = cond[i][s_i],  PLL(s) = sum_i site[i] (ascending i).
-// Parameter sources (as in energy.hip): kind 0 = the packed plm vector x (float or double), kind 1 = the dense mf -inv(C)
-// (double, leading dimension ld) with the mf fields; both zero on the gap state q-1.
+// The model arrives as a PottsSource (potts_source.h); the site kernel's loads are specialised per source kind (KIND).
 //
 // Summation order (depends on (L, q, dtype) only): every term widened to double; u_i(a) = h_i(a) first, then j ascending, one
 // accumulator per (sequence, site, state) held by one lane.  No cross-lane or cross-workgroup sums, no atomics.
@@ -29,30 +28,6 @@ constexpr int kPMaxCJ = 16;                        // blocks per chunk at most (
 constexpr size_t kPChunkBudget = 16 * 1024;        // LDS per J chunk buffer (two of them)
 constexpr size_t kPPassBudget = 256ull << 20;      // device scratch of one pass
 
-__device__ __forceinline__ size_t pair_index(int L, int i, int j)
-{
-    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
-}
-
-template <typename S>
-__device__ __forceinline__ double field(const S* src, const double* mfh, int kind, int q, int i, int a)
-{
-    if (kind == 0) return (double)src[(size_t)i * q + a];
-    return a == q - 1 ? 0.0 : mfh[(size_t)i * (q - 1) + a];
-}
-
-// floor(e / d) for e * d < 2^32: m = floor(2^32 / d) + 1
-__device__ __forceinline__ int fast_div(int e, uint32_t m) { return (int)__umulhi((uint32_t)e, m); }
-
-// site-major copy of n query rows (n x L bytes): QT[s * NqS + k], zero past n
-__global__ void pll_sites_kernel(const uint8_t* __restrict__ rows, int n, int L, int NqS, uint8_t* __restrict__ QT)
-{
-    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (t >= (size_t)L * NqS) return;
-    const int s = (int)(t / NqS), k = (int)(t % NqS);
-    QT[t] = k < n ? rows[(size_t)k * L + s] : 0;
-}
-
 // Blocks per chunk: a J chunk buffer holds CJ blocks of up to QM x QM values within kPChunkBudget (at most kPMaxCJ)
 template <typename S, int QM>
 constexpr int chunk_blocks() { return (int)(kPChunkBudget / (QM * QM * sizeof(S))) < kPMaxCJ ? (int)(kPChunkBudget / (QM * QM * sizeof(S))) : kPMaxCJ; }
@@ -62,9 +37,13 @@ constexpr int chunk_blocks() { return (int)(kPChunkBudget / (QM * QM * sizeof(S)
 // >= gridDim.y * 512 (codes past nq are 0).  site: L x NqS doubles (site-major); cond: nq x L x q doubles or NULL.
 template <typename S, int KIND, int QM>
 __global__ __launch_bounds__(kPThreads)
-void pll_site_kernel(const S* __restrict__ src, const double* __restrict__ mfh, int L, int q, int ld,
-                     const uint8_t* __restrict__ QT, int nq, int NqS, double* __restrict__ site, double* __restrict__ cond)
+void pll_site_kernel(const PottsView<S> pvIn, const uint8_t* __restrict__ QT, int nq, int NqS, double* __restrict__ site,
+                     double* __restrict__ cond)
 {
+    PottsView<S> pv = pvIn;
+    pv.kind = KIND;                                           // a compile-time constant from here on
+    const S* src = pv.src;
+    const int L = pv.L, q = pv.q, ld = pv.ld;
     constexpr int CJ = chunk_blocks<S, QM>();
     constexpr int KPB = (QM * QM + kPThreads - 1) / kPThreads;
     constexpr int codeBytes = CJ * kPSeqBlock;
@@ -147,7 +126,7 @@ void pll_site_kernel(const S* __restrict__ src, const double* __restrict__ mfh, 
     double u[kPPerLane][QM];
 #pragma unroll
     for (int a = 0; a < QM; ++a) {
-        const double h = a < q ? field(src, mfh, KIND, q, i, a) : 0.0;
+        const double h = a < q ? pv.field(i, a) : 0.0;
 #pragma unroll
         for (int p = 0; p < kPPerLane; ++p) u[p][a] = h;
     }
@@ -236,34 +215,31 @@ size_t pll_lds(int q)
 }
 
 template <typename S, int KIND, int QM>
-hipError_t launch_site(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q, int ld,
-                       const uint8_t* dQT, int nq, int NqS, double* dSite, double* dCond)
+hipError_t launch_site(dca_ctx* ctx, const PottsView<S>& pv, const uint8_t* dQT, int nq, int NqS, double* dSite, double* dCond)
 {
     auto kern = pll_site_kernel<S, KIND, QM>;
-    const size_t lds = pll_lds<S, QM>(q);
+    const size_t lds = pll_lds<S, QM>(pv.q);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(L, ceil_div(nq, kPSeqBlock)), dim3(kPThreads), lds, ctx->stream, src, mfh, L, q, ld,
-                       dQT, nq, NqS, dSite, dCond);
+    hipLaunchKernelGGL(kern, dim3(pv.L, ceil_div(nq, kPSeqBlock)), dim3(kPThreads), lds, ctx->stream, pv, dQT, nq, NqS, dSite, dCond);
     return hipGetLastError();
 }
 
 template <typename S>
-hipError_t dispatch_site(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q, int ld,
-                         const uint8_t* dQT, int nq, int NqS, double* dSite, double* dCond)
+hipError_t dispatch_site(dca_ctx* ctx, const PottsView<S>& pv, const uint8_t* dQT, int nq, int NqS, double* dSite, double* dCond)
 {
+    const int QM = pv.q <= 8 ? 8 : pv.q <= 24 ? 24 : 32;
     if constexpr (sizeof(S) == 8) {                           // the mf source is double
-        if (kind == 1) switch (q <= 8 ? 8 : q <= 24 ? 24 : 32) {
-        case 8: return launch_site<S, 1, 8>(ctx, src, kind, mfh, L, q, ld, dQT, nq, NqS, dSite, dCond);
-        case 24: return launch_site<S, 1, 24>(ctx, src, kind, mfh, L, q, ld, dQT, nq, NqS, dSite, dCond);
-        default: return launch_site<S, 1, 32>(ctx, src, kind, mfh, L, q, ld, dQT, nq, NqS, dSite, dCond);
+        if (pv.kind == 1) switch (QM) {
+        case 8: return launch_site<S, 1, 8>(ctx, pv, dQT, nq, NqS, dSite, dCond);
+        case 24: return launch_site<S, 1, 24>(ctx, pv, dQT, nq, NqS, dSite, dCond);
+        default: return launch_site<S, 1, 32>(ctx, pv, dQT, nq, NqS, dSite, dCond);
         }
     }
-    const int QM = q <= 8 ? 8 : q <= 24 ? 24 : 32;
     switch (QM) {
-    case 8: return launch_site<S, 0, 8>(ctx, src, kind, mfh, L, q, ld, dQT, nq, NqS, dSite, dCond);
-    case 24: return launch_site<S, 0, 24>(ctx, src, kind, mfh, L, q, ld, dQT, nq, NqS, dSite, dCond);
-    default: return launch_site<S, 0, 32>(ctx, src, kind, mfh, L, q, ld, dQT, nq, NqS, dSite, dCond);
+    case 8: return launch_site<S, 0, 8>(ctx, pv, dQT, nq, NqS, dSite, dCond);
+    case 24: return launch_site<S, 0, 24>(ctx, pv, dQT, nq, NqS, dSite, dCond);
+    default: return launch_site<S, 0, 32>(ctx, pv, dQT, nq, NqS, dSite, dCond);
     }
 }
 
@@ -281,9 +257,9 @@ int pll_pass_size(int n, int L, int q, bool want_site, bool want_cond)
 }
 
 template <typename S>
-int pll_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q, int ld, const uint8_t* X, int n, double* pll_out,
-          double* site_out, double* cond_out)
+int pll_t(dca_ctx* ctx, const PottsView<S>& pv, const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out)
 {
+    const int L = pv.L, q = pv.q;
     const int cap = pll_pass_size(n, L, q, site_out != nullptr, cond_out != nullptr);
     const int NqS = cap;                                      // a multiple of 512
     uint8_t *dRows = nullptr, *dQT = nullptr;
@@ -298,11 +274,11 @@ int pll_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q,
         const int nq = std::min(cap, n - first);
         e = hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) break;
-        const size_t total = (size_t)L * NqS;
-        hipLaunchKernelGGL(pll_sites_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dRows, nq, L, NqS, dQT);
+        e = dca_rows_to_sites(ctx, dRows, nq, L, NqS, dQT);
+        if (e != hipSuccess) break;
         {
             ScopedKernelClock kc(ctx, "pll");
-            e = dispatch_site<S>(ctx, src, kind, mfh, L, q, ld, dQT, nq, NqS, dSite, dCond);
+            e = dispatch_site<S>(ctx, pv, dQT, nq, NqS, dSite, dCond);
             if (e == hipSuccess)
                 hipLaunchKernelGGL(pll_finish_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, dSite, L, nq, NqS, dPll, dSiteRows);
         }
@@ -322,14 +298,11 @@ int pll_t(dca_ctx* ctx, const S* src, int kind, const double* mfh, int L, int q,
 
 }  // namespace
 
-int dca_potts_pseudo_likelihood(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld,
-                                const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out)
+int dca_potts_pseudo_likelihood(dca_ctx* ctx, const PottsSource& ps, const uint8_t* X, int n, double* pll_out, double* site_out,
+                                double* cond_out)
 {
     if (n < 0 || (n > 0 && (!X || !pll_out))) { dca_set_error("pseudo-likelihood: bad arguments"); return DCA_ERR_ARG; }
     if (n == 0) return DCA_OK;
-    for (size_t k = 0; k < (size_t)n * L; ++k)
-        if (X[k] >= q) { dca_set_error("code %d >= q at element %zu", (int)X[k], k); return DCA_ERR_ARG; }
-    if (dtype == DCA_F32)
-        return pll_t(ctx, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, X, n, pll_out, site_out, cond_out);
-    return pll_t(ctx, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, X, n, pll_out, site_out, cond_out);
+    DCA_TRY(dca_check_codes(X, (size_t)n * ps.L, ps.q, ""));
+    return with_source_type(ps, [&](auto pv) { return pll_t(ctx, pv, X, n, pll_out, site_out, cond_out); });
 }

@@ -35,11 +35,6 @@ __device__ __forceinline__ double t_exp(double v) { return exp(v); }
 __device__ __forceinline__ float t_log(float v) { return logf(v); }
 __device__ __forceinline__ double t_log(double v) { return log(v); }
 
-__host__ __device__ __forceinline__ size_t pair_index(int L, int i, int j)
-{
-    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
-}
-
 // block (i<j) from linear pair index (host side builds the table once)
 struct PairIJ { uint16_t i, j; };
 
@@ -2241,16 +2236,22 @@ struct PlmEngine : PlmEngineBase {
         *x = dx;
         return DCA_OK;
     }
-    // annealed importance sampling of the current x; one GPU only, an L-BFGS run in progress is allowed (as for sample())
-    int ais(const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out) override
+    // the current x for energy.hip, pll.hip, sample.hip and ais.hip; an L-BFGS run in progress is allowed.  Column strips gather
+    // x first, as scores() does; one_gpu_only (AIS) refuses them instead
+    int potts_source(PottsSource* out, bool one_gpu_only) override
     {
         if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
-        if (strips || native_mode == 4) { dca_set_error("AIS runs on one GPU: configured for column strips"); return DCA_ERR_STATE; }
-        if (comm || hook || native_mode != 0) {
-            dca_set_error("AIS runs on one GPU: vector sharding, a reduce / comm hook or a native-comm mode is set");
-            return DCA_ERR_STATE;
+        if (one_gpu_only) {
+            if (strips || native_mode == 4) { dca_set_error("AIS runs on one GPU: configured for column strips"); return DCA_ERR_STATE; }
+            if (comm || hook || native_mode != 0) {
+                dca_set_error("AIS runs on one GPU: vector sharding, a reduce / comm hook or a native-comm mode is set");
+                return DCA_ERR_STATE;
+            }
+        } else if (native_mode == 4 && !stripEmulate) {
+            DCA_TRY(strip_allgather(dx));
         }
-        return dca_potts_ais(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, args, log_weights_out, log_z0_out, chains_out);
+        *out = PottsSource{dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0};
+        return DCA_OK;
     }
     int set_vector_sharding(int rank, int world, dca_comm_hook h, void* user) override
     {
@@ -2548,36 +2549,6 @@ struct PlmEngine : PlmEngineBase {
         if (!configured) return DCA_ERR_STATE;
         if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
         return dca_pair_blocks(ctx, dx, 0, (int)sizeof(T) * 8, L, q, 0, pairs, npairs, shift, out);
-    }
-
-    // Potts energies / single-mutant scan of the current x (energy.hip); column strips gather x first, as scores() does
-    int energies(const uint8_t* X, int n, double* out) override
-    {
-        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
-        if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
-        return dca_potts_energies(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, X, n, out);
-    }
-    int mutation_scan(const uint8_t* wildtype, double* out) override
-    {
-        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
-        if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
-        return dca_potts_mutation_scan(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, wildtype, out);
-    }
-    // site conditionals and pseudo-log-likelihoods of the current x (pll.hip); column strips gather x first, as energies() does
-    int pseudo_likelihood(const uint8_t* X, int n, double* pll_out, double* site_out, double* cond_out) override
-    {
-        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
-        if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
-        return dca_potts_pseudo_likelihood(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, X, n, pll_out, site_out, cond_out);
-    }
-    // Gibbs samples of the current x (sample.hip); column strips gather x first, as energies() does
-    int sample(int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta, const uint8_t* initial,
-               uint8_t* out) override
-    {
-        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
-        if (native_mode == 4 && !stripEmulate) DCA_TRY(strip_allgather(dx));
-        return dca_potts_sample(ctx, dx, 0, (int)sizeof(T) * 8, nullptr, L, q, 0, n, sweeps, seed, first_chain, first_sweep, beta,
-                                initial, out);
     }
 
     // DI of the current x (plmdca.py:683-790); reg_fi: host, L*q regularised single-site frequencies

@@ -2,8 +2,7 @@
 //   one sweep visits sites i = 0 .. L-1 in order; at site i chain c forms
 //     u_i(a) = h_i(a) + sum_{j != i} J(a, s_j)        (J read from the pair block (min(i,j), max(i,j)), as energy.hip reads it)
 //   for every state a < q (gap included) and draws s_i from p_a = exp(beta * (u_i(a) - max_b u_i(b))).
-// Parameter sources: kind 0 = the packed plm vector x (float or double), kind 1 = the dense mf -inv(C) (double, leading
-// dimension ld) with the mf fields; both zero on the gap state q-1.
+// The model arrives as a PottsSource and is read through PottsView (potts_source.h).
 //
 // Summation order (depends on (L, q, dtype) only): every term widened to double;
 //   u(a) = (((h_i(a) + S_0(a)) + S_1(a)) + S_2(a)) + S_3(a),  S_w(a) = sum over j = w (mod 4), j != i, ascending j.
@@ -32,31 +31,6 @@ constexpr int kSThreads = 256;                    // 4 waves, 64 chains
 constexpr int kSChains = 64;
 constexpr int kSResidentL = 512;                  // chain codes in LDS up to 32 KiB
 constexpr size_t kSChunkBudget = 40 * 1024;       // LDS per J chunk buffer (two of them)
-
-__device__ __forceinline__ size_t pair_index(int L, int i, int j)
-{
-    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
-}
-
-// J_ij(a, b) for i < j, widened to double (energy.hip's coupling())
-template <typename S>
-__device__ __forceinline__ double coupling(const S* src, int kind, int L, int q, int ld, int i, int j, int a, int b)
-{
-    if (kind == 0) return (double)src[(size_t)L * q + pair_index(L, i, j) * (size_t)q * q + (size_t)a * q + b];
-    const int qm = q - 1;
-    if (a == qm || b == qm) return 0.0;
-    return (double)src[(size_t)(i * qm + a) * ld + (size_t)j * qm + b];
-}
-
-template <typename S>
-__device__ __forceinline__ double field(const S* src, const double* mfh, int kind, int q, int i, int a)
-{
-    if (kind == 0) return (double)src[(size_t)i * q + a];
-    return a == q - 1 ? 0.0 : mfh[(size_t)i * (q - 1) + a];
-}
-
-// floor(e / d) for e * d < 2^32: m = floor(2^32 / d) + 1
-__device__ __forceinline__ int fast_div(int e, uint32_t m) { return (int)__umulhi((uint32_t)e, m); }
 
 // rows (n x L) <-> site-major state (st[s * nS + c], nS a multiple of 64; chains past n start at code 0)
 __global__ void rows_to_sites_kernel(const uint8_t* __restrict__ rows, int n, int L, int nS, uint8_t* __restrict__ st)
@@ -128,7 +102,7 @@ void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __res
             if (j >= L || j == i) continue;
             const int hi = fast_div(k, mq), lo = k - hi * q;
             const int a = j > i ? hi : lo, b = j > i ? lo : hi;          // source order: (a, b) rows for j > i, (b, a) for j < i
-            val[r] = (S)(j > i ? coupling(src, kind, L, q, ld, i, j, a, b) : coupling(src, kind, L, q, ld, j, i, b, a));
+            val[r] = (S)(j > i ? potts_coupling(src, kind, L, q, ld, i, j, a, b) : potts_coupling(src, kind, L, q, ld, j, i, b, a));
             dst[r] = jj * blk + b * QM + a;
         }
     };
@@ -149,7 +123,7 @@ void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __res
         const int i = t / nch, ch = t - i * nch, j0 = ch * CJ;
         if (ch == 0) {
 #pragma unroll
-            for (int a = 0; a < QM; ++a) u[a] = (wave == 0 && a < q) ? field(src, mfh, kind, q, i, a) : 0.0;
+            for (int a = 0; a < QM; ++a) u[a] = (wave == 0 && a < q) ? potts_field(src, mfh, kind, q, i, a) : 0.0;
         }
         if (t + 1 < steps) load(t + 1);
         const S* cur = buf0 + (t & 1) * bufVals;
@@ -240,48 +214,61 @@ SampleGeom sample_geometry(int L, int q, size_t elem)
     return g;
 }
 
+// what one sweep launch takes besides the model
+struct SweepArgs { uint8_t* dState; int nS; uint64_t seed, first_chain, sweep; double beta; const double* h0; double bk; };
+
 template <typename S, int QM, bool RES, bool INTERP>
-hipError_t launch_sweep(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
-                        uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta, const double* h0, double bk)
+hipError_t launch_sweep(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
     constexpr int R = sizeof(S) == 4 ? 32 : 16;
     auto kern = gibbs_sweep_kernel<S, QM, RES, R, INTERP>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(nS / kSChains), dim3(kSThreads), sg.lds, ctx->stream, src, kind, mfh, L, q, ld, sg.CJ, dState, nS,
-                       seed, first_chain, sweep, beta, h0, bk);
+    hipLaunchKernelGGL(kern, dim3(a.nS / kSChains), dim3(kSThreads), sg.lds, ctx->stream, pv.src, pv.kind, pv.mfh, pv.L, pv.q, pv.ld,
+                       sg.CJ, a.dState, a.nS, a.seed, a.first_chain, a.sweep, a.beta, a.h0, a.bk);
     return hipGetLastError();
 }
 
 template <typename S, int QM, bool INTERP>
-hipError_t dispatch_res(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
-                        uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta, const double* h0, double bk)
+hipError_t dispatch_res(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
-    if (sg.res) return launch_sweep<S, QM, true, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
-    return launch_sweep<S, QM, false, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
+    if (sg.res) return launch_sweep<S, QM, true, INTERP>(ctx, sg, pv, a);
+    return launch_sweep<S, QM, false, INTERP>(ctx, sg, pv, a);
 }
 
 template <typename S, bool INTERP>
-hipError_t dispatch_qm(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
-                       uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta, const double* h0, double bk)
+hipError_t dispatch_qm(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
     switch (sg.QM) {
-    case 8: return dispatch_res<S, 8, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
-    case 24: return dispatch_res<S, 24, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
-    default: return dispatch_res<S, 32, INTERP>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
+    case 8: return dispatch_res<S, 8, INTERP>(ctx, sg, pv, a);
+    case 24: return dispatch_res<S, 24, INTERP>(ctx, sg, pv, a);
+    default: return dispatch_res<S, 32, INTERP>(ctx, sg, pv, a);
     }
 }
 
 // h0 NULL: the plain sweep under beta; otherwise the interpolated one (INTERP above)
 template <typename S>
-hipError_t dispatch_sweep(dca_ctx* ctx, const SampleGeom& sg, const S* src, int kind, const double* mfh, int L, int q, int ld,
-                          uint8_t* dState, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta, const double* h0, double bk)
+hipError_t dispatch_sweep(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
-    if (h0) return dispatch_qm<S, true>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
-    return dispatch_qm<S, false>(ctx, sg, src, kind, mfh, L, q, ld, dState, nS, seed, first_chain, sweep, beta, h0, bk);
+    if (a.h0) return dispatch_qm<S, true>(ctx, sg, pv, a);
+    return dispatch_qm<S, false>(ctx, sg, pv, a);
 }
 
 }  // namespace
+
+hipError_t dca_rows_to_sites(dca_ctx* ctx, const uint8_t* dRows, int n, int L, int nS, uint8_t* dSites)
+{
+    const size_t total = (size_t)L * nS;
+    hipLaunchKernelGGL(rows_to_sites_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dRows, n, L, nS, dSites);
+    return hipGetLastError();
+}
+
+hipError_t dca_sites_to_rows(dca_ctx* ctx, const uint8_t* dSites, int n, int L, int nS, uint8_t* dRows)
+{
+    const size_t total = (size_t)n * L;
+    hipLaunchKernelGGL(sites_to_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dSites, n, L, nS, dRows);
+    return hipGetLastError();
+}
 
 // ---- device-resident chains (dca_internal.h): the sampler's state between calls
 int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial)
@@ -296,9 +283,7 @@ int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t 
         if (initial) {
             e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)n * L, false);
             if (e == hipSuccess) e = hipMemcpyAsync(dRows, initial, (size_t)n * L, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(rows_to_sites_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, dRows, n, L, ch->nS,
-                                   ch->dState);
+            if (e == hipSuccess) e = dca_rows_to_sites(ctx, dRows, n, L, ch->nS, ch->dState);
         } else {
             hipLaunchKernelGGL(initial_state_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, n, L, q, ch->nS, seed,
                                first_chain, ch->dState);
@@ -310,26 +295,18 @@ int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t 
     return DCA_OK;
 }
 
-int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const void* src, int src_kind, int dtype, const double* dMfFields, int q, int ld,
-                      int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta, const double* dBase, double bk)
+int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const PottsSource& ps, int sweeps, uint64_t seed, uint64_t first_chain,
+                      uint64_t first_sweep, double beta, const double* dBase, double bk)
 {
-    const int L = ch.L;
-    hipError_t e = hipSuccess;
-    if (dtype == DCA_F32) {
-        const SampleGeom sg = sample_geometry(L, q, sizeof(float));
+    const hipError_t e = with_source_type(ps, [&](auto pv) {
+        const SampleGeom sg = sample_geometry(pv.L, pv.q, sizeof(*pv.src));
+        hipError_t e = hipSuccess;
         for (int t = 0; t < sweeps && e == hipSuccess; ++t) {       // one launch per sweep
             ScopedKernelClock kc(ctx, "sample");
-            e = dispatch_sweep<float>(ctx, sg, static_cast<const float*>(src), src_kind, dMfFields, L, q, ld, ch.dState, ch.nS, seed,
-                                      first_chain, first_sweep + (uint64_t)t, beta, dBase, bk);
+            e = dispatch_sweep(ctx, sg, pv, SweepArgs{ch.dState, ch.nS, seed, first_chain, first_sweep + (uint64_t)t, beta, dBase, bk});
         }
-    } else {
-        const SampleGeom sg = sample_geometry(L, q, sizeof(double));
-        for (int t = 0; t < sweeps && e == hipSuccess; ++t) {
-            ScopedKernelClock kc(ctx, "sample");
-            e = dispatch_sweep<double>(ctx, sg, static_cast<const double*>(src), src_kind, dMfFields, L, q, ld, ch.dState, ch.nS, seed,
-                                       first_chain, first_sweep + (uint64_t)t, beta, dBase, bk);
-        }
-    }
+        return e;
+    });
     if (e != hipSuccess) { dca_set_error("sample: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
     return DCA_OK;
 }
@@ -339,10 +316,7 @@ int dca_chains_read(dca_ctx* ctx, const DcaChains& ch, uint8_t* out)
     const size_t total = (size_t)ch.n * ch.L;
     uint8_t* dRows = nullptr;
     hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), total, false);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(sites_to_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, ch.dState, ch.n, ch.L, ch.nS, dRows);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = dca_sites_to_rows(ctx, ch.dState, ch.n, ch.L, ch.nS, dRows);
     if (e == hipSuccess) e = hipMemcpyAsync(out, dRows, total, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     dca_dev_free(dRows);
@@ -356,21 +330,18 @@ void dca_chains_free(DcaChains* ch)
     *ch = DcaChains();
 }
 
-int dca_potts_sample(dca_ctx* ctx, const void* src, int src_kind, int dtype, const double* dMfFields, int L, int q, int ld, int n,
-                     int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta, const uint8_t* initial,
-                     uint8_t* out)
+int dca_potts_sample(dca_ctx* ctx, const PottsSource& ps, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep,
+                     double beta, const uint8_t* initial, uint8_t* out)
 {
     if (n < 0 || sweeps < 0 || !(beta >= 0.0) || std::isinf(beta) || (n > 0 && !out)) {
         dca_set_error("sample: bad arguments (n %d, sweeps %d, beta %g)", n, sweeps, beta);
         return DCA_ERR_ARG;
     }
     if (n == 0) return DCA_OK;
-    if (initial)
-        for (size_t k = 0; k < (size_t)n * L; ++k)
-            if (initial[k] >= q) { dca_set_error("sample: initial code %d >= q at element %zu", (int)initial[k], k); return DCA_ERR_ARG; }
+    if (initial) DCA_TRY(dca_check_codes(initial, (size_t)n * ps.L, ps.q, "sample: initial "));
     DcaChains ch;
-    int rc = dca_chains_start(ctx, &ch, n, L, q, seed, first_chain, initial);
-    if (rc == DCA_OK) rc = dca_chains_sweeps(ctx, ch, src, src_kind, dtype, dMfFields, q, ld, sweeps, seed, first_chain, first_sweep, beta);
+    int rc = dca_chains_start(ctx, &ch, n, ps.L, ps.q, seed, first_chain, initial);
+    if (rc == DCA_OK) rc = dca_chains_sweeps(ctx, ch, ps, sweeps, seed, first_chain, first_sweep, beta);
     if (rc == DCA_OK) rc = dca_chains_read(ctx, ch, out);
     dca_chains_free(&ch);
     return rc;

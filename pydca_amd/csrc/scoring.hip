@@ -8,11 +8,6 @@
 
 namespace {
 
-__host__ __device__ __forceinline__ size_t pair_index(int L, int i, int j)
-{
-    return (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2 + (size_t)(j - i - 1);
-}
-
 // one 64-lane workgroup per site pair; block values go through LDS
 template <typename S>
 __global__ __launch_bounds__(64)

@@ -25,7 +25,7 @@ def _ranked(scores, L, ctx=None):
     return _ranking.ranked(scores, L, ctx.scores_order() if ctx is not None else None)
 
 
-class MeanFieldDCA:
+class MeanFieldDCA(_potts.PottsModel):
     """Mean-field DCA (meanfield_dca.py:43-139)."""
 
     def __init__(self, msa, biomolecule, pseudocount=None, seqid=None, device=0, devices=None):
@@ -270,117 +270,25 @@ class MeanFieldDCA:
             raise
         return call()
 
-    def compute_sequence_energies(self, sequences=None):
-        """Statistical energies E(s) = sum_i h_i(s_i) + sum_{i<j} J_ij(s_i, s_j) with J the couplings and h the fields of
-        compute_fields (both zero on the gap state) -> float64[n], higher is more probable.  sequences: None (every record
-        of the training alignment, in file order, duplicates kept), a FASTA path or a list of aligned strings."""
-        src = self.__msa if sequences is None else sequences
+    _potts_exc = MeanFieldDCAException
+    _potts_table = 1
+    _potts_logger = logger
+
+    def _potts_dims(self):
         bio = _lib.DCA_BIOMOLECULE_PROTEIN if self.__num_site_states == 21 else _lib.DCA_BIOMOLECULE_RNA
-        X = _potts.query_codes(src, bio, self.__sequences_len, 1, MeanFieldDCAException)
-        logger.info('\n\tStatistical energies of {} sequences'.format(X.shape[0]))
-        return self._with_couplings(lambda: self.__ctx.mf_energies(X))
+        return bio, self.__sequences_len, self.__num_site_states
 
-    def compute_single_mutant_effects(self, wildtype):
-        """dE(i, a) = E(wildtype with site i set to state a) - E(wildtype) for every site and state (gap last)
-        -> float64[L, q]; dE(i, w_i) = 0.  wildtype: an aligned string of length L or a FASTA file with one record."""
-        bio = _lib.DCA_BIOMOLECULE_PROTEIN if self.__num_site_states == 21 else _lib.DCA_BIOMOLECULE_RNA
-        w = _potts.wildtype_codes(wildtype, bio, self.__sequences_len, 1, MeanFieldDCAException)
-        logger.info('\n\tSingle-mutant effects of the wild type')
-        return self._with_couplings(lambda: self.__ctx.mf_mutation_scan(w))
+    def _potts_default_source(self):
+        return self.__msa
 
-    def sample_sequences(self, num_sequences, num_sweeps=1000, seed=0, temperature=1.0, initial=None, return_codes=False):
-        """Draws num_sequences sequences from P(s) ~ exp(E(s) / temperature) by systematic-scan Gibbs sampling on the GPU:
-        one independent chain per sequence, num_sweeps sweeps over all sites (E as in compute_sequence_energies; the couplings are computed first if
-        none are there yet).
-        initial: None (random starts), an aligned string (every chain starts from it), a list of num_sequences aligned
-        strings, or a FASTA file with 1 or num_sequences records.  The draws follow a counter-based generator of `seed`:
-        the same arguments give the same sequences.  -> aligned strings (gap '-'), or uint8[n, L] codes with
-        return_codes."""
-        n = int(num_sequences)
-        beta = _potts.sampling_beta(temperature, MeanFieldDCAException)
-        bio = _lib.DCA_BIOMOLECULE_PROTEIN if self.__num_site_states == 21 else _lib.DCA_BIOMOLECULE_RNA
-        X0 = _potts.initial_codes(initial, n, bio, self.__sequences_len, 1, MeanFieldDCAException)
-        logger.info('\n\tGibbs sampling of {} sequences, {} sweeps'.format(n, num_sweeps))
-        codes = self._with_couplings(lambda: self.__ctx.mf_sample(n, num_sweeps, seed=seed, beta=beta, initial=X0))
-        if return_codes:
-            return codes
-        letters = _potts.state_letters(bio)
-        return [''.join(letters[c] for c in row) for row in codes]
+    def _potts_devices(self):
+        return self.__devices
 
-    # ---- normalised probabilities: log Z by annealed importance sampling (DESIGN.md section 14; no reference counterpart)
-    def _one_gpu(self, what):
-        if self.__devices and len(self.__devices) > 1:
-            logger.error('\n\t{} runs on one GPU; devices={}'.format(what, self.__devices))
-            raise MeanFieldDCAException('{} runs on one GPU, not on devices {}'.format(what, self.__devices))
+    def _potts_training(self):
+        return self.__X0, self.__sequences_weight, self.__effective_num_sequences
 
-    def compute_log_partition_function(self, num_chains=1000, num_temperatures=1000, sweeps_per_temperature=1, seed=0, base='profile',
-                                       pseudocount=None):
-        """log Z = log sum_s exp(E(s)) of the mean-field model (E as in compute_sequence_energies) by annealed importance
-        sampling on the GPU: num_chains chains start from the independent-site base model and anneal through beta_k = k / K
-        (K = num_temperatures) with sweeps_per_temperature Gibbs sweeps per intermediate temperature.  base: 'profile' (log of
-        the alignment's weighted single-site frequencies, regularised by (1 - lambda) f + lambda / q, lambda = pseudocount or
-        1 / Meff), 'fields' (the model's own fields, 0 on the gap state) or an L x q array.
-        -> {'log_z', 'log_z_stderr', 'ess', 'log_z_base', 'log_weights'}"""
-        self._one_gpu('compute_log_partition_function')
-        opts = _potts.ais_options(num_chains, num_temperatures, sweeps_per_temperature, seed, pseudocount, MeanFieldDCAException)
-        h0 = _potts.ais_base(base, self.__X0, self.__sequences_weight, self.__sequences_len, self.__num_site_states,
-                             opts['pseudocount'], MeanFieldDCAException)
-        logger.info('\n\tlog Z by annealed importance sampling: {} chains, {} temperatures, {} sweeps per temperature'.format(
-            opts['num_chains'], opts['num_temperatures'], opts['sweeps_per_temperature']))
-        return _potts.log_partition_function(
-            lambda n, K, s, sd, h: self._with_couplings(lambda: self.__ctx.mf_ais(n, K, sweeps_per_temperature=s, seed=sd, base_fields=h)),
-            opts, h0)
-
-    def compute_sequence_log_probabilities(self, sequences=None, log_z=None, **ais_kwargs):
-        """log P(s) = E(s) - log Z -> float64[n] (sequences as in compute_sequence_energies).  log_z None: estimated first by
-        compute_log_partition_function(**ais_kwargs)."""
-        self._one_gpu('compute_sequence_log_probabilities')
-        if log_z is None:
-            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
-        return self.compute_sequence_energies(sequences) - float(log_z)
-
-    def compute_log_likelihood(self, log_z=None, **ais_kwargs):
-        """(sum_n w_n E(s_n)) / Meff - log Z over the alignment and weights of this instance -> float.  log_z None: estimated
-        first by compute_log_partition_function(**ais_kwargs)."""
-        self._one_gpu('compute_log_likelihood')
-        if log_z is None:
-            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
-        E = self._with_couplings(lambda: self.__ctx.mf_energies(self.__X0))
-        return _potts.log_likelihood(E, self.__sequences_weight, self.__effective_num_sequences, log_z)
-
-    # ---- pseudo-log-likelihoods (DESIGN.md section 15; no reference counterpart)
-    def _query(self, sequences):
-        src = self.__msa if sequences is None else sequences
-        bio = _lib.DCA_BIOMOLECULE_PROTEIN if self.__num_site_states == 21 else _lib.DCA_BIOMOLECULE_RNA
-        return _potts.query_codes(src, bio, self.__sequences_len, 1, MeanFieldDCAException)
-
-    def compute_sequence_pseudo_log_likelihoods(self, sequences=None, per_site=False):
-        """PLL(s) = sum_i log P(s_i | s_-i) of the mean-field model (J the couplings, h the fields of compute_fields, both
-        zero on the gap state), log P(s_i = a | s_-i) = u_i(a) - log sum_b exp u_i(b), u_i(a) = h_i(a) + sum_{j != i}
-        J_ij(a, s_j) -> float64[n], or (float64[n], float64[n, L] of log P(s_i | s_-i)) with per_site.  sequences: as in
-        compute_sequence_energies.  This is the true pseudo-log-likelihood of the model."""
-        per_site = _potts.pll_flag(per_site, MeanFieldDCAException)
-        self._one_gpu('compute_sequence_pseudo_log_likelihoods')
-        X = self._query(sequences)
-        logger.info('\n\tPseudo-log-likelihoods of {} sequences'.format(X.shape[0]))
-        return self._with_couplings(lambda: self.__ctx.mf_pseudo_likelihood(X, per_site=per_site))
-
-    def compute_conditional_log_probabilities(self, sequences):
-        """log P(s_i = a | s_-i) for every site i and state a (gap last) of each sequence (as in
-        compute_sequence_pseudo_log_likelihoods) -> float64[n, L, q], or float64[L, q] for a single aligned string.
-        sequences: an aligned string, a list of aligned strings or a FASTA path."""
-        single = _potts.single_query(sequences, MeanFieldDCAException)
-        self._one_gpu('compute_conditional_log_probabilities')
-        X = self._query([sequences] if single else sequences)
-        _pll, cond = self._with_couplings(lambda: self.__ctx.mf_pseudo_likelihood(X, conditionals=True))
-        return cond[0] if single else cond
-
-    def compute_pseudo_log_likelihood(self):
-        """(sum_n w_n PLL(s_n)) / Meff over the alignment and weights of this instance -> float: the pseudo-log-likelihood
-        per effective sequence (compute_sequence_pseudo_log_likelihoods), comparable with compute_log_likelihood."""
-        self._one_gpu('compute_pseudo_log_likelihood')
-        plls = self._with_couplings(lambda: self.__ctx.mf_pseudo_likelihood(self.__X0))
-        return _potts.pseudo_log_likelihood(plls, self.__sequences_weight, self.__effective_num_sequences)
+    def _potts_call(self, name, *args, **kw):
+        return self._with_couplings(lambda: getattr(self.__ctx, 'mf_' + name)(*args, **kw))
 
     def shift_couplings(self, couplings_ij):
         """meanfield_dca.py:636-658 (zero-sum gauge of one block)."""

@@ -52,7 +52,7 @@ def _boltzmann_options(iterations, num_chains, sweeps_per_iteration, equilibrati
     return opts
 
 
-class PlmDCA:
+class PlmDCA(_potts.PottsModel):
     """plmdca.py:25-104.  Extra keyword arguments (not in the reference): device,
     precision (32: float storage as the reference; 64: float64 checking mode) and
     exact_gradient (opt-in mathematically exact pseudolikelihood gradient instead of the
@@ -323,38 +323,26 @@ class PlmDCA:
         """The model this instance holds from an earlier compute_* call; fitted once here if there is none."""
         return self.__ctx if self.__ctx is not None else self._run_backend()
 
-    def compute_sequence_energies(self, sequences=None):
-        """Statistical energies E(s) = sum_i h_i(s_i) + sum_{i<j} J_ij(s_i, s_j) of the fitted parameters (gap state
-        included) -> float64[n], higher is more probable.  sequences: None (every record of the training file, in file
-        order, duplicates kept), a FASTA path or a list of aligned strings."""
-        src = self.__msa_file if sequences is None else sequences
-        X = _potts.query_codes(src, self.__biomolecule_int, self.__seqs_len, 0, PlmDCAException)
-        logger.info('\n\tStatistical energies of {} sequences'.format(X.shape[0]))
-        return self._fitted_context().plm_energies(X)
+    _potts_exc = PlmDCAException
+    _potts_table = 0
+    _potts_logger = logger
 
-    def compute_single_mutant_effects(self, wildtype):
-        """dE(i, a) = E(wildtype with site i set to state a) - E(wildtype) for every site and state (gap last)
-        -> float64[L, q]; dE(i, w_i) = 0.  wildtype: an aligned string of length L or a FASTA file with one record."""
-        w = _potts.wildtype_codes(wildtype, self.__biomolecule_int, self.__seqs_len, 0, PlmDCAException)
-        logger.info('\n\tSingle-mutant effects of the wild type')
-        return self._fitted_context().plm_mutation_scan(w)
+    def _potts_dims(self):
+        return self.__biomolecule_int, self.__seqs_len, self.__num_site_states
 
-    def sample_sequences(self, num_sequences, num_sweeps=1000, seed=0, temperature=1.0, initial=None, return_codes=False):
-        """Draws num_sequences sequences from P(s) ~ exp(E(s) / temperature) by systematic-scan Gibbs sampling on the GPU:
-        one independent chain per sequence, num_sweeps sweeps over all sites (E as in compute_sequence_energies).
-        initial: None (random starts), an aligned string (every chain starts from it), a list of num_sequences aligned
-        strings, or a FASTA file with 1 or num_sequences records.  The draws follow a counter-based generator of `seed`:
-        the same arguments give the same sequences.  -> aligned strings (gap '-'), or uint8[n, L] codes with
-        return_codes."""
-        n = int(num_sequences)
-        beta = _potts.sampling_beta(temperature, PlmDCAException)
-        X0 = _potts.initial_codes(initial, n, self.__biomolecule_int, self.__seqs_len, 0, PlmDCAException)
-        logger.info('\n\tGibbs sampling of {} sequences, {} sweeps'.format(n, num_sweeps))
-        codes = self._fitted_context().plm_sample(n, num_sweeps, seed=seed, beta=beta, initial=X0)
-        if return_codes:
-            return codes
-        letters = _potts.state_letters(self.__biomolecule_int)
-        return [''.join(letters[c] for c in row) for row in codes]
+    def _potts_default_source(self):
+        return self.__msa_file
+
+    def _potts_devices(self):
+        return self.__devices
+
+    def _potts_training(self):
+        ctx = self._fitted_context()
+        X = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)[0]
+        return X, ctx.weights(), ctx.meff()
+
+    def _potts_call(self, name, *args, **kw):
+        return getattr(self._fitted_context(), 'plm_' + name)(*args, **kw)
 
     def _unfitted_context(self):
         """Alignment, weights and configuration as _run_backend sets them up, without the L-BFGS run."""
@@ -404,85 +392,6 @@ class PlmDCA:
         if history.shape[0]:
             logger.info('\n\tLast iteration: eps_h {:.3g}, eps_J {:.3g}, pearson {:.4f}'.format(*history[-1]))
         return {'history': history, 'fields_and_couplings': ctx.plm_get_x(dt)}
-
-    # ---- normalised probabilities: log Z by annealed importance sampling (no reference counterpart)
-    def _one_gpu(self, what):
-        if self.__devices and len(self.__devices) > 1:
-            logger.error('\n\t{} runs on one GPU; devices={}'.format(what, self.__devices))
-            raise PlmDCAException('{} runs on one GPU, not on devices {}'.format(what, self.__devices))
-
-    def compute_log_partition_function(self, num_chains=1000, num_temperatures=1000, sweeps_per_temperature=1, seed=0, base='profile',
-                                       pseudocount=None):
-        """log Z = log sum_s exp(E(s)) of the fitted model (E as in compute_sequence_energies; after fit_boltzmann the refined
-        model) by annealed importance sampling on the GPU: num_chains chains start from the independent-site base model and
-        anneal through beta_k = k / K (K = num_temperatures) with sweeps_per_temperature Gibbs sweeps per intermediate
-        temperature.  base: 'profile' (log of the training alignment's weighted single-site frequencies, regularised by
-        (1 - lambda) f + lambda / q, lambda = pseudocount or 1 / Meff), 'fields' (the model's own fields) or an L x q array.
-        -> {'log_z', 'log_z_stderr', 'ess', 'log_z_base', 'log_weights'}"""
-        self._one_gpu('compute_log_partition_function')
-        opts = _potts.ais_options(num_chains, num_temperatures, sweeps_per_temperature, seed, pseudocount, PlmDCAException)
-        ctx = self._fitted_context()
-        X = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)[0] if isinstance(base, str) and base == 'profile' else None
-        h0 = _potts.ais_base(base, X, ctx.weights() if X is not None else None, self.__seqs_len, self.__num_site_states,
-                             opts['pseudocount'], PlmDCAException)
-        logger.info('\n\tlog Z by annealed importance sampling: {} chains, {} temperatures, {} sweeps per temperature'.format(
-            opts['num_chains'], opts['num_temperatures'], opts['sweeps_per_temperature']))
-        return _potts.log_partition_function(
-            lambda n, K, s, sd, h: ctx.plm_ais(n, K, sweeps_per_temperature=s, seed=sd, base_fields=h), opts, h0)
-
-    def compute_sequence_log_probabilities(self, sequences=None, log_z=None, **ais_kwargs):
-        """log P(s) = E(s) - log Z -> float64[n] (sequences as in compute_sequence_energies).  log_z None: estimated first by
-        compute_log_partition_function(**ais_kwargs)."""
-        self._one_gpu('compute_sequence_log_probabilities')
-        if log_z is None:
-            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
-        return self.compute_sequence_energies(sequences) - float(log_z)
-
-    def compute_log_likelihood(self, log_z=None, **ais_kwargs):
-        """(sum_n w_n E(s_n)) / Meff - log Z over the alignment and weights of the fit -> float.  log_z None: estimated first
-        by compute_log_partition_function(**ais_kwargs)."""
-        self._one_gpu('compute_log_likelihood')
-        if log_z is None:
-            log_z = self.compute_log_partition_function(**ais_kwargs)['log_z']
-        ctx = self._fitted_context()
-        X = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)[0]
-        return _potts.log_likelihood(ctx.plm_energies(X), ctx.weights(), ctx.meff(), log_z)
-
-    # ---- pseudo-log-likelihoods (DESIGN.md section 15; no reference counterpart)
-    def _query(self, sequences):
-        src = self.__msa_file if sequences is None else sequences
-        return _potts.query_codes(src, self.__biomolecule_int, self.__seqs_len, 0, PlmDCAException)
-
-    def compute_sequence_pseudo_log_likelihoods(self, sequences=None, per_site=False):
-        """PLL(s) = sum_i log P(s_i | s_-i) of the fitted parameters (after fit_boltzmann the refined model), with
-        log P(s_i = a | s_-i) = u_i(a) - log sum_b exp u_i(b), u_i(a) = h_i(a) + sum_{j != i} J_ij(a, s_j) (gap state included)
-        -> float64[n], or (float64[n], float64[n, L] of log P(s_i | s_-i)) with per_site.  sequences: as in
-        compute_sequence_energies.  This is the true pseudo-log-likelihood, not the fx the fit reports: under the reference's
-        carry-over of the gradient the fit's objective differs from it by design."""
-        per_site = _potts.pll_flag(per_site, PlmDCAException)
-        self._one_gpu('compute_sequence_pseudo_log_likelihoods')
-        X = self._query(sequences)
-        logger.info('\n\tPseudo-log-likelihoods of {} sequences'.format(X.shape[0]))
-        return self._fitted_context().plm_pseudo_likelihood(X, per_site=per_site)
-
-    def compute_conditional_log_probabilities(self, sequences):
-        """log P(s_i = a | s_-i) for every site i and state a (gap last) of each sequence (as in
-        compute_sequence_pseudo_log_likelihoods) -> float64[n, L, q], or float64[L, q] for a single aligned string.
-        sequences: an aligned string, a list of aligned strings or a FASTA path."""
-        single = _potts.single_query(sequences, PlmDCAException)
-        self._one_gpu('compute_conditional_log_probabilities')
-        X = self._query([sequences] if single else sequences)
-        _pll, cond = self._fitted_context().plm_pseudo_likelihood(X, conditionals=True)
-        return cond[0] if single else cond
-
-    def compute_pseudo_log_likelihood(self):
-        """(sum_n w_n PLL(s_n)) / Meff over the alignment and weights of the fit -> float: the unregularised
-        pseudo-log-likelihood per effective sequence (compute_sequence_pseudo_log_likelihoods), comparable with
-        compute_log_likelihood.  Not the fit's reported fx."""
-        self._one_gpu('compute_pseudo_log_likelihood')
-        ctx = self._fitted_context()
-        X = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)[0]
-        return _potts.pseudo_log_likelihood(ctx.plm_pseudo_likelihood(X), ctx.weights(), ctx.meff())
 
     def compute_seqs_weight(self):
         """plmdca.py:565-591: weights of the PYTHON reader's alignment (float64 comparison,
