@@ -116,7 +116,8 @@ int dca_create(dca_ctx** out, int device, int precision /* DCA_F32 | DCA_F64 */)
 void dca_destroy(dca_ctx* ctx);
 /* X: N x L, 0-based codes < q, gap = q-1 (the C++ coding; the Python mfDCA layer
  * converts from the reference's 1-based coding).  Copies to the device; the range of the codes is checked there (a code >= q
- * is DCA_ERR_ARG with the element's position, and the context then holds NO alignment -- not the one it held before). */
+ * is DCA_ERR_ARG with the element's position, and the context then holds NO alignment -- not the one it held before).
+ * N >= 1, L >= 1, 2 <= q <= 32; the model entries (plm, mf, ar) need L >= 2 and answer DCA_ERR_STATE on a one-site alignment. */
 int dca_set_msa(dca_ctx* ctx, const uint8_t* X, int N, int L, int q);
 
 /* Sequence weights: PlmDCA::computeSeqsWeight (plmdca_numerics.cpp:611-671) when
@@ -575,12 +576,49 @@ int dca_ar_log_probabilities(dca_ctx* ctx, const uint8_t* X, int n, double* logp
 int dca_ar_sample(dca_ctx* ctx, int n, uint64_t seed, uint64_t first_chain, uint8_t* out);
 int dca_ar_release(dca_ctx* ctx);
 
+/* ------------------------------------------------------------------ comparing sequence sets with the alignment
+ * Model-free: these entries use the context's alignment (and, for the comparison, its weights), never its parameters; the
+ * alignment, the weights and any fitted model (plm, mf, ar, a Boltzmann run) stay untouched.  DESIGN.md section 17.
+ *
+ * Hamming distances between a query set and a reference set of aligned, encoded sequences (same table, same L).  L and q are
+ * those of the context's alignment, so dca_set_msa comes first in every case (DCA_ERR_STATE otherwise); Q and R are host rows
+ * (nq x L, nr x L codes < q; a larger code is DCA_ERR_ARG).
+ * R == NULL: the reference set is the context's alignment (dca_set_msa), already on the device; nr is ignored.  Q == NULL: the
+ * query set IS the reference set; nq is ignored.  skip_same_index != 0: the pairs (k, m) with k == m are left out (a set against
+ * itself).  dist_out[k] = min_m d(Q_k, R_m); index_out[k] = the SMALLEST m that attains it; hist_out[d] = number of
+ * compared pairs (k, m) at distance d, d = 0..L (so sum(hist) = nq*nr, or nq*nr - min(nq,nr) with skip_same_index).
+ * index_out and hist_out may be NULL.  A query with no partner (nr == 1 and skipped) gets dist -1, index -1.
+ * Everything is integer: the outputs do not depend on the batch a query is in, on the pass split (DCA_NN_PASS, a positive
+ * count, caps the queries per pass) or on the launch geometry.  DCA_ERR_ARG: dist_out NULL, nq < 1 with Q, nr < 1 with R.
+ * Profiling tag "hamming". */
+int dca_hamming_nearest(dca_ctx* ctx, const uint8_t* Q, int nq, const uint8_t* R, int nr, int skip_same_index,
+                        int32_t* dist_out, int32_t* index_out, uint64_t* hist_out);
+
+typedef struct {           /* one block per quantity: [0] f_i, [1] f_ij, [2] c_ij (connected) */
+    double pearson[3], slope[3], max_abs_diff[3];
+    double sxx[3], syy[3], sxy[3];      /* the centred sums the three above are formed from; x = alignment, y = query set */
+    double terms[3];                    /* number of terms: L*q, pairs*q*q, pairs*q*q */
+} dca_set_comparison;
+
+/* One- and two-site frequencies of nq encoded sequences (unweighted: count / nq, all q states), optionally returned
+ * (fi_out: L*q; fij_out: pairs*q*q in pair order, either may be NULL), and their comparison with the context's
+ * alignment under the context's sequence weights (dca_compute_weights / dca_set_weights first), no pseudocount.
+ * Centred with the analytic means (1/q, 1/q^2, 0):  sxx = sum (x - mu)^2, syy, sxy over all terms, c_ij(a, b) = f_ij(a, b) -
+ * f_i(a) f_j(b) of each side; pearson = sxy / sqrt(sxx syy) (0 when sxx syy <= 0), slope = sxy / sxx (0 when sxx == 0),
+ * max_abs_diff = max |x - y|.  All in double, without contraction, in an order fixed by (L, q): no float atomics.
+ * cmp_out may be NULL (frequencies only; no weights needed then).  DCA_ERR_ARG: Q NULL, nq < 1, a code >= q, all three outputs
+ * NULL; DCA_ERR_STATE: no alignment, cmp_out without weights.  Profiling tags "bm_stats" (the counts), "set_compare". */
+int dca_sequence_statistics(dca_ctx* ctx, const uint8_t* Q, int nq, double* fi_out, double* fij_out, dca_set_comparison* cmp_out);
+/* The alignment's side of that comparison: the weighted frequencies of all q states, no pseudocount (fi_out: L*q, fij_out:
+ * pairs*q*q in pair order; either may be NULL, not both) -- the x that dca_sequence_statistics compares with, bit for bit. */
+int dca_alignment_statistics(dca_ctx* ctx, double* fi_out, double* fij_out);
+
 /* ------------------------------------------------------------------ timing
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
  * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "ar_logits", "ar_grad", "ar_sample",
- * "bm_stats", "ais"). */
+ * "bm_stats", "ais", "hamming", "set_compare"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it
  * instead of two per stage (an event record costs the stream ~5 us: 14 per plmDCA iteration are 5 % of config C's step, 0.4 % of

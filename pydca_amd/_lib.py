@@ -54,6 +54,11 @@ class ArStats(C.Structure):
                 ("seconds", C.c_double)]
 
 
+class SetComparison(C.Structure):
+    """dca_set_comparison (include/dca_hip.h): one entry per quantity, [0] f_i, [1] f_ij, [2] c_ij"""
+    _fields_ = [(k, C.c_double * 3) for k in ("pearson", "slope", "max_abs_diff", "sxx", "syy", "sxy", "terms")]
+
+
 AR_CONVERGED, AR_MAX_ITERATIONS, AR_LINE_SEARCH_FAILED = 0, 1, 2
 
 COMM_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
@@ -160,6 +165,9 @@ def lib():
         "dca_plm_bm_freqs": (i, [vp, i, vp, vp]),
         "dca_plm_bm_chains": (i, [vp, vp]),
         "dca_plm_bm_end": (i, [vp]),
+        "dca_hamming_nearest": (i, [vp, vp, i, vp, i, i, vp, vp, vp]),
+        "dca_sequence_statistics": (i, [vp, vp, i, vp, vp, C.POINTER(SetComparison)]),
+        "dca_alignment_statistics": (i, [vp, vp, vp]),
         "dca_plm_ais": (i, [vp, C.POINTER(AisArgs), vp, C.POINTER(d), vp]),
         "dca_mf_ais": (i, [vp, C.POINTER(AisArgs), vp, C.POINTER(d), vp]),
         "dca_ais_estimate": (i, [vp, i, d, C.POINTER(d), C.POINTER(d), C.POINTER(d)]),
@@ -209,6 +217,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_ar_fit", "dca_ar_log_probabilities", "dca_ar_sample", "dca_ar_release",
            "dca_plm_bm_begin", "dca_plm_bm_iterate", "dca_plm_bm_freqs", "dca_plm_bm_chains", "dca_plm_bm_end",
            "dca_plm_ais", "dca_mf_ais", "dca_ais_estimate",
+           "dca_hamming_nearest", "dca_sequence_statistics", "dca_alignment_statistics",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
            "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
@@ -809,6 +818,42 @@ class Context:
 
     def plm_bm_end(self):
         check(self._l.dca_plm_bm_end(self._h))
+
+    # ---- a sequence set against the alignment (distance.hip, set_stats.hip): model-free, nothing of the context changes
+    def hamming_nearest(self, Q=None, R=None, skip_same_index=False, return_index=True, return_histogram=True):
+        """Hamming distance of every row of Q (uint8[nq, L]; None: the reference set itself) to its nearest row of R (uint8[nr, L];
+        None: the context's alignment) -> (int32[nq] distances, int32[nq] smallest nearest index or None, uint64[L + 1] histogram
+        of all compared pairs or None).  skip_same_index leaves the pairs k == m out; a query without partner gets -1, -1."""
+        q_ = None if Q is None else np.ascontiguousarray(Q, dtype=np.uint8).reshape(-1, self.L)
+        r_ = None if R is None else np.ascontiguousarray(R, dtype=np.uint8).reshape(-1, self.L)
+        nr = self.N if r_ is None else r_.shape[0]
+        nq = nr if q_ is None else q_.shape[0]
+        dist = np.zeros(nq, dtype=np.int32)
+        index = np.zeros(nq, dtype=np.int32) if return_index else None
+        hist = np.zeros(self.L + 1, dtype=np.uint64) if return_histogram else None
+        check(self._l.dca_hamming_nearest(self._h, None if q_ is None else _ptr(q_), int(nq), None if r_ is None else _ptr(r_), int(nr),
+                                          int(bool(skip_same_index)), _ptr(dist), None if index is None else _ptr(index),
+                                          None if hist is None else _ptr(hist)))
+        return dist, index, hist
+
+    def sequence_statistics(self, Q, frequencies=True, compare=True):
+        """Unweighted frequencies of the rows of Q (uint8[n, L]) and their comparison with the alignment's weighted ones ->
+        (fi float64[L, q] or None, fij float64[pairs, q, q] or None, dict of the dca_set_comparison fields (3-vectors) or None)"""
+        Q = np.ascontiguousarray(Q, dtype=np.uint8).reshape(-1, self.L)
+        fi = np.zeros((self.L, self.q), dtype=np.float64) if frequencies else None
+        fij = np.zeros((self.L * (self.L - 1) // 2, self.q, self.q), dtype=np.float64) if frequencies else None
+        cmp_ = SetComparison() if compare else None
+        check(self._l.dca_sequence_statistics(self._h, _ptr(Q), int(Q.shape[0]), None if fi is None else _ptr(fi),
+                                              None if fij is None else _ptr(fij), None if cmp_ is None else C.byref(cmp_)))
+        out = None if cmp_ is None else {k: np.array(getattr(cmp_, k), dtype=np.float64) for k, _t in SetComparison._fields_}
+        return fi, fij, out
+
+    def alignment_statistics(self):
+        """The alignment's weighted frequencies of all q states, no pseudocount -> (float64[L, q], float64[pairs, q, q])"""
+        fi = np.zeros((self.L, self.q), dtype=np.float64)
+        fij = np.zeros((self.L * (self.L - 1) // 2, self.q, self.q), dtype=np.float64)
+        check(self._l.dca_alignment_statistics(self._h, _ptr(fi), _ptr(fij)))
+        return fi, fij
 
     # ---- log Z by annealed importance sampling (ais.hip) -> (float64[n] log weights, log Z0, uint8[n, L] final chains or None)
     def _ais(self, fn, chains, temperatures, sweeps_per_temperature, seed, first_chain, betas, base_fields, return_chains):

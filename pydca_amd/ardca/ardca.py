@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .. import _lib, _potts
+from .. import _compare, _lib, _potts
 
 logger = logging.getLogger(__name__)
 
@@ -61,7 +61,7 @@ def _number(name, v, low, integer=False):
     return int(f) if integer else f
 
 
-class ArDCA:
+class ArDCA(_compare.SequenceComparison):
     """arDCA of a FASTA alignment: ArDCA(msa_file, 'protein' | 'rna', seqid=0.8, lambda_h=1e-6, lambda_J=1e-2,
     max_iterations=1000, epsilon=1e-5, order='entropy', device=0).  lambda_h, lambda_J weigh the L2 penalty against the
     weighted log-likelihood per effective sequence.  order: 'entropy' (ascending entropy of the weighted
@@ -164,6 +164,25 @@ class ArDCA:
         self.__weights = w
         self.__ctx = ctx
         return ctx
+
+    # ---- sequence sets against the alignment (_compare.SequenceComparison): the unfitted context serves; its columns are in
+    # model order, so the queries are permuted the same way and distances and row indices come out as for the file's order
+    _compare_exc = ArDCAException
+    _compare_table = 0
+    _compare_logger = logger
+
+    def _compare_dims(self):
+        return self.__biomolecule_int, self.__L, self.__q
+
+    def _compare_devices(self):
+        return None
+
+    def _compare_context(self):
+        return self._context()
+
+    def _compare_order(self):
+        self._context()
+        return None if np.array_equal(self.__order, np.arange(self.__L)) else self.__order
 
     def _fitted_context(self):
         """The fitted model; fitted once here on first use."""

@@ -1,5 +1,5 @@
-"""`ardca` command line: fit, compute_log_probabilities, compute_log_likelihood, sample_sequences and compute_mutation_effects
-of the autoregressive model (ArDCA), with the argument names, output directory and file naming of the plmdca / mfdca
+"""`ardca` command line: fit, compute_log_probabilities, compute_log_likelihood, sample_sequences, compute_mutation_effects
+and compare_sequences of the autoregressive model (ArDCA), with the argument names, output directory and file naming of the plmdca / mfdca
 sub-commands: <output_dir>/ARDCA_<what>_<alignment base>.txt / .fa / .npy.  No pydca counterpart."""
 import logging
 import os
@@ -13,7 +13,8 @@ from .ardca import ardca
 from .dca_utilities import dca_utilities
 
 logger = logging.getLogger(__name__)
-ARDCA_SUBCOMMANDS = ('fit', 'compute_log_probabilities', 'compute_log_likelihood', 'sample_sequences', 'compute_mutation_effects')
+ARDCA_SUBCOMMANDS = ('fit', 'compute_log_probabilities', 'compute_log_likelihood', 'sample_sequences', 'compute_mutation_effects',
+                    'compare_sequences')
 _RULE = '#' + '=' * 70
 
 
@@ -93,6 +94,9 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, seqid=Non
         write_fit(fit_file, status, site_order, metadata=ardca_param_metadata(instance))
         return params, fit_file
     meta = ardca_param_metadata(instance)
+    if the_command == 'compare_sequences':
+        from . import _compare
+        return _compare.run_compare(instance, 'ARDCA', msa_file, output_dir, meta, query_file, ardca.ArDCAException)
     if the_command == 'compute_log_probabilities':
         logp = instance.compute_sequence_log_probabilities(query_file)
         out = path('log_probabilities', '.txt')
@@ -137,6 +141,8 @@ def build_parser():
         p.add_argument('--verbose', action='store_true')
         if name == 'compute_log_probabilities':
             p.add_argument('--query_file', help='FASTA file of aligned query sequences (default: the records of msa_file)')
+        if name == 'compare_sequences':
+            p.add_argument('--query_file', required=True, help='FASTA file of aligned sequences to compare with the alignment; no fit is run')
         if name == 'compute_mutation_effects':
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence')
         if name == 'sample_sequences':

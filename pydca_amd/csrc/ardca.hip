@@ -939,6 +939,7 @@ int dca_ar_configure(dca_ctx* ctx, double lambda_h, double lambda_J)
         return DCA_ERR_ARG;
     }
     if (!ctx->dX) { dca_set_error("dca_set_msa first"); return DCA_ERR_STATE; }
+    if (ctx->L < 2) { dca_set_error("the model needs an alignment of at least two sites"); return DCA_ERR_STATE; }
     if (!ctx->have_weights) { dca_set_error("dca_compute_weights or dca_set_weights first"); return DCA_ERR_STATE; }
     hipSetDevice(ctx->device);
     if (!ctx->ar) ctx->ar = dca_make_ar_engine(ctx);

@@ -220,6 +220,24 @@ hipError_t bm_stats(dca_ctx* ctx, BmRun* r, S* x, int slot, double* gij)
     return e;
 }
 
+}  // namespace
+
+hipError_t dca_bm_count_chains(dca_ctx* ctx, const DcaChains& ch, int q, double* dGi, double* dGij)
+{
+    BmRun r;                               // a view of the caller's chains and buffers for the launchers above; it owns nothing
+    r.L = ch.L; r.q = q;
+    r.tb = bm_tile(q);
+    r.nb = ceil_div(ch.L, r.tb);
+    r.ch = ch;
+    r.dGi = dGi;
+    const hipError_t e = bm_stats<float, false>(ctx, &r, nullptr, 0, dGij);
+    r.ch = DcaChains();
+    r.dGi = nullptr;
+    return e;
+}
+
+namespace {
+
 bool finite_nonneg(double v) { return v >= 0.0 && std::isfinite(v); }
 
 // the x a run learns, as the sampler's source

@@ -297,7 +297,8 @@ void dca_destroy(dca_ctx* ctx)
 int dca_set_msa(dca_ctx* ctx, const uint8_t* X, int N, int L, int q)
 {
     CHECK_CTX(ctx);
-    if (!X || N <= 0 || L <= 1 || q < 2 || q > 32) { dca_set_error("dca_set_msa: bad arguments"); return DCA_ERR_ARG; }
+    // (one site is enough for the distance entries; the models ask for two themselves)
+    if (!X || N <= 0 || L < 1 || q < 2 || q > 32) { dca_set_error("dca_set_msa: bad arguments"); return DCA_ERR_ARG; }
     free_msa(ctx);
     ctx->N = ctx->L = ctx->q = ctx->Ls = 0;                // the context holds no alignment until everything below succeeded
     const int Ls = (int)round_up((size_t)L, 128);
@@ -440,6 +441,7 @@ int dca_get_meff(dca_ctx* ctx, double* meff_out)
 static int need_plm(dca_ctx* ctx)
 {
     if (!ctx->dX) { dca_set_error("dca_set_msa first"); return DCA_ERR_STATE; }
+    if (ctx->L < 2) { dca_set_error("the model needs an alignment of at least two sites"); return DCA_ERR_STATE; }
     if (!ctx->plm) ctx->plm = dca_make_plm_engine(ctx);
     return DCA_OK;
 }
@@ -569,6 +571,36 @@ int dca_plm_bm_freqs(dca_ctx* ctx, int which, double* fi_out, double* fij_out) {
 int dca_plm_bm_chains(dca_ctx* ctx, uint8_t* out) { CHECK_CTX(ctx); return dca_bm_chains_impl(ctx, out); }
 int dca_plm_bm_end(dca_ctx* ctx) { CHECK_CTX(ctx); dca_bm_free(ctx); return DCA_OK; }
 
+// ------------------------------------------------------------------ sequence sets against the alignment (distance.hip, set_stats.hip)
+int dca_hamming_nearest(dca_ctx* ctx, const uint8_t* Q, int nq, const uint8_t* R, int nr, int skip_same_index,
+                        int32_t* dist_out, int32_t* index_out, uint64_t* hist_out)
+{
+    CHECK_CTX(ctx);
+    if (!dist_out) { dca_set_error("dca_hamming_nearest: dist_out is NULL"); return DCA_ERR_ARG; }
+    if (!ctx->dX) { dca_set_error("dca_hamming_nearest: dca_set_msa first (the alignment gives L and q, and is the reference set when R is NULL)"); return DCA_ERR_STATE; }
+    if ((Q && nq < 1) || (R && nr < 1)) { dca_set_error("dca_hamming_nearest: nq %d, nr %d must be >= 1", nq, nr); return DCA_ERR_ARG; }
+    return dca_hamming_nearest_impl(ctx, Q, nq, R, nr, skip_same_index != 0, dist_out, index_out, hist_out);
+}
+int dca_sequence_statistics(dca_ctx* ctx, const uint8_t* Q, int nq, double* fi_out, double* fij_out, dca_set_comparison* cmp_out)
+{
+    CHECK_CTX(ctx);
+    if (!Q || nq < 1) { dca_set_error("dca_sequence_statistics: Q is NULL or nq %d < 1", nq); return DCA_ERR_ARG; }
+    if (!fi_out && !fij_out && !cmp_out) { dca_set_error("dca_sequence_statistics: every output is NULL"); return DCA_ERR_ARG; }
+    if (!ctx->dX) { dca_set_error("dca_set_msa first"); return DCA_ERR_STATE; }
+    if (ctx->L < 2) { dca_set_error("dca_sequence_statistics: the alignment needs at least two sites"); return DCA_ERR_STATE; }
+    if (cmp_out && !ctx->have_weights) { dca_set_error("dca_sequence_statistics: dca_compute_weights or dca_set_weights first"); return DCA_ERR_STATE; }
+    return dca_set_statistics_impl(ctx, Q, nq, fi_out, fij_out, cmp_out);
+}
+int dca_alignment_statistics(dca_ctx* ctx, double* fi_out, double* fij_out)
+{
+    CHECK_CTX(ctx);
+    if (!fi_out && !fij_out) { dca_set_error("dca_alignment_statistics: both outputs are NULL"); return DCA_ERR_ARG; }
+    if (!ctx->dX) { dca_set_error("dca_set_msa first"); return DCA_ERR_STATE; }
+    if (ctx->L < 2) { dca_set_error("dca_alignment_statistics: the alignment needs at least two sites"); return DCA_ERR_STATE; }
+    if (!ctx->have_weights) { dca_set_error("dca_alignment_statistics: dca_compute_weights or dca_set_weights first"); return DCA_ERR_STATE; }
+    return dca_set_statistics_impl(ctx, nullptr, 0, fi_out, fij_out, nullptr);
+}
+
 int dca_plm_di_scores(dca_ctx* ctx, const double* reg_fi, int apc, double* out)
 {
     CHECK_CTX(ctx);
@@ -581,6 +613,7 @@ int dca_plm_di_scores(dca_ctx* ctx, const double* reg_fi, int apc, double* out)
 static int need_mf(dca_ctx* ctx)
 {
     if (!ctx->dX) { dca_set_error("dca_set_msa first"); return DCA_ERR_STATE; }
+    if (ctx->L < 2) { dca_set_error("the model needs an alignment of at least two sites"); return DCA_ERR_STATE; }
     if (!ctx->have_weights) { dca_set_error("weights must be computed or set first"); return DCA_ERR_STATE; }
     if (!ctx->mf) ctx->mf = dca_make_mf_engine(ctx);
     return ctx->mf ? DCA_OK : DCA_ERR_NOMEM;

@@ -271,6 +271,17 @@ int dca_bm_freqs_impl(dca_ctx* ctx, int which, double* fi_out, double* fij_out);
 int dca_bm_chains_impl(dca_ctx* ctx, uint8_t* out);
 void dca_bm_free(dca_ctx* ctx);
 
+// the chains' unweighted frequencies by the UPDATE = false instantiations of the statistics kernels (exact integer LDS
+// histograms): dGi (L*q) and dGij (pairs*q*q, pair order), device.  Under the tag "bm_stats"; no run is needed or touched.
+hipError_t dca_bm_count_chains(dca_ctx* ctx, const DcaChains& ch, int q, double* dGi, double* dGij);
+
+// ---- distance.hip / set_stats.hip : a sequence set against the alignment (dca_hamming_nearest, dca_sequence_statistics,
+// dca_alignment_statistics; arguments checked by the callers in capi.cpp).  Q == NULL in dca_set_statistics_impl: the alignment's
+// weighted frequencies go to fi_out / fij_out instead of the set's.
+int dca_hamming_nearest_impl(dca_ctx* ctx, const uint8_t* Q, int nq, const uint8_t* R, int nr, bool skip_same, int32_t* dist_out,
+                             int32_t* index_out, uint64_t* hist_out);
+int dca_set_statistics_impl(dca_ctx* ctx, const uint8_t* Q, int nq, double* fi_out, double* fij_out, dca_set_comparison* cmp_out);
+
 int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, const double* reg_fi, int L, int q,
                             double* fields_out, double* di_out, const double* fields_in = nullptr);
 

@@ -8,6 +8,8 @@ import errno
 import logging
 import os
 
+import numpy as np
+
 from ..fasta_reader import fasta_reader
 
 logger = logging.getLogger(__name__)
@@ -106,6 +108,29 @@ def write_pseudo_log_likelihoods(file_name, plls, metadata=None, query_file=None
                '# Second its pseudo-log-likelihood PLL(s) = sum_i log P(s_i | s_-i) under the model', _RULE]
     rows = ('{0:<7} {1}'.format(k + 1, '%.17g' % float(v)) for k, v in enumerate(plls))
     _stream(file_name, header, rows, 'pseudo-log-likelihoods')
+
+
+def write_sequence_comparison(file_name, summary, dist, index, hist, self_hist, seqs_len, metadata=None, query_file=None):
+    """Header: the summary of compare_with_alignment (one '#\t<name>: <value>' line per scalar, %.17g) and the non-zero bins of the
+    two distance histograms ('#\tdistance <d>: <query-alignment pairs> <alignment-alignment pairs>'); then one row per query record:
+    its number (1-based, input order), the Hamming distance to the nearest alignment sequence, that sequence's row index
+    (0-based, smallest on ties) and the identity 1 - d / L (no reference counterpart)."""
+    header = [_RULE] + list(metadata or [])
+    if query_file:
+        header.append('#\tQuery sequences: {}'.format(query_file))
+    for key in sorted(summary):
+        v = summary[key]
+        if np.ndim(v) == 0:
+            header.append('#\t{}: {}'.format(key, int(v) if isinstance(v, (int, np.integer)) else '%.17g' % float(v)))
+    header.append('# Pairs at every Hamming distance with at least one: query against alignment, alignment against itself (other rows)')
+    for d in range(len(hist)):
+        if int(hist[d]) or int(self_hist[d]):
+            header.append('#\tdistance {}: {} {}'.format(d, int(hist[d]), int(self_hist[d])))
+    header += ['# The First column is the record number (1-based) of the query sequence, the Second its Hamming distance',
+               '# to the nearest alignment sequence, the Third that sequence\'s row (0-based) and the Fourth the identity 1 - d / L', _RULE]
+    L = float(seqs_len)
+    rows = ('{0:<7} {1:<5} {2:<7} {3}'.format(k + 1, int(d), int(m), '%.17g' % (1.0 - int(d) / L)) for k, (d, m) in enumerate(zip(dist, index)))
+    _stream(file_name, header, rows, 'sequence comparison')
 
 
 def write_mutation_effects(file_name, dE, wildtype_letters, state_letters, metadata=None, wildtype_file=None):

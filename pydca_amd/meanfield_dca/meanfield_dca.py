@@ -6,7 +6,7 @@ import time
 
 import numpy as np
 
-from .. import _lib, _potts, _ranking, multi_gpu
+from .. import _compare, _lib, _potts, _ranking, multi_gpu
 from ..fasta_reader import fasta_reader
 from . import msa_numerics
 
@@ -25,7 +25,7 @@ def _ranked(scores, L, ctx=None):
     return _ranking.ranked(scores, L, ctx.scores_order() if ctx is not None else None)
 
 
-class MeanFieldDCA(_potts.PottsModel):
+class MeanFieldDCA(_potts.PottsModel, _compare.SequenceComparison):
     """Mean-field DCA (meanfield_dca.py:43-139)."""
 
     def __init__(self, msa, biomolecule, pseudocount=None, seqid=None, device=0, devices=None):
@@ -283,6 +283,23 @@ class MeanFieldDCA(_potts.PottsModel):
 
     def _potts_devices(self):
         return self.__devices
+
+    # ---- sequence sets against the alignment (_compare.SequenceComparison): the context of the constructor, no couplings
+    _compare_exc = MeanFieldDCAException
+    _compare_table = 1
+    _compare_logger = logger
+
+    def _compare_dims(self):
+        return self._potts_dims()
+
+    def _compare_devices(self):
+        return self.__devices
+
+    def _compare_order(self):
+        return None
+
+    def _compare_context(self):
+        return self.__ctx
 
     def _potts_training(self):
         return self.__X0, self.__sequences_weight, self.__effective_num_sequences

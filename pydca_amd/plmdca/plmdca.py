@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from .. import _lib, _potts, _ranking, multi_gpu
+from .. import _compare, _lib, _potts, _ranking, multi_gpu
 
 logger = logging.getLogger(__name__)
 
@@ -52,7 +52,7 @@ def _boltzmann_options(iterations, num_chains, sweeps_per_iteration, equilibrati
     return opts
 
 
-class PlmDCA(_potts.PottsModel):
+class PlmDCA(_potts.PottsModel, _compare.SequenceComparison):
     """plmdca.py:25-104.  Extra keyword arguments (not in the reference): device,
     precision (32: float storage as the reference; 64: float64 checking mode) and
     exact_gradient (opt-in mathematically exact pseudolikelihood gradient instead of the
@@ -96,6 +96,7 @@ class PlmDCA(_potts.PottsModel):
         self.__data_size = int((self.__seqs_len * (self.__seqs_len - 1) * (self.__num_site_states ** 2)) / 2
                                + self.__seqs_len * self.__num_site_states)
         self.__ctx = None
+        self.__compare_ctx = None          # alignment and weights only (_compare_context), when no fit has run
         self.__fields_and_couplings_all = None
         self.last_status = None
         logger.info('Created plmDCA instance: biomolecule {}, L {}, sequences {}, seqid {}, lambda_h {}, lambda_J {}, '
@@ -343,6 +344,29 @@ class PlmDCA(_potts.PottsModel):
 
     def _potts_call(self, name, *args, **kw):
         return getattr(self._fitted_context(), 'plm_' + name)(*args, **kw)
+
+    # ---- sequence sets against the alignment (_compare.SequenceComparison): alignment and weights only, no fit
+    _compare_exc = PlmDCAException
+    _compare_table = 0
+    _compare_logger = logger
+    _compare_dims = _potts_dims
+    _compare_devices = _potts_devices
+
+    def _compare_order(self):
+        return None
+
+    def _compare_context(self):
+        """The fitted context if there is one (its alignment and weights are what the comparison needs); otherwise a context
+        of its own with the de-duplicated alignment and its weights, kept for later calls -- no optimisation is run."""
+        if self.__ctx is not None:
+            return self.__ctx
+        if self.__compare_ctx is None:
+            X, _raw = _lib.read_msa(self.__msa_file, self.__biomolecule_int, self.__seqs_len)
+            ctx = _lib.Context(self.__device, self.__precision)
+            ctx.set_msa(X, self.__num_site_states)
+            ctx.compute_weights(self.__seqid, self.__precision)
+            self.__compare_ctx = ctx
+        return self.__compare_ctx
 
     def _unfitted_context(self):
         """Alignment, weights and configuration as _run_backend sets them up, without the L-BFGS run."""

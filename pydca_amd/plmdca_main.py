@@ -113,6 +113,9 @@ def run_plm_dca(argv=None):
             p.add_argument('--apc', action='store_true')
         if name in ('compute_energies', 'compute_pseudo_log_likelihood'):
             p.add_argument('--query_file', help='FASTA file of aligned query sequences (default: the records of msa_file) (addition)')
+        if name == 'compare_sequences':
+            p.add_argument('--query_file', required=True, help='FASTA file of aligned sequences to compare with the alignment; no fit '
+                           'is run (addition)')
         if name == 'compute_mutation_effects':
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence (addition)')
         if name == 'sample_sequences':
