@@ -191,3 +191,11 @@ int oracle_read_msa(const char* path, int biomolecule, int L, uint8_t* out, int 
 #define REAL_SQRT sqrt
 #define REAL_ABS fabs
 #include "plm_oracle_impl.h"
+
+/* The float64 line search on its own: tests/test_more_thuente_host.py holds the product's copy
+ * (pydca_amd/csrc/more_thuente.h) against it, trial step for trial step. */
+int oracle_mt_search_f64(size_t n, double* x, double* f, double* g, const double* s, double* stp,
+                         const double* xp, eval_fn_f64 eval, void* ctx, int* nevals)
+{
+    return mt_search_f64(n, x, f, g, s, stp, xp, eval, ctx, nevals);
+}

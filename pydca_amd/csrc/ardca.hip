@@ -12,12 +12,15 @@
 // and the pass results are added in ascending pass order; then g += 2 lambda x and fx = -(sum of F_pass) + lambda_h |h|^2 + lambda_J |J|^2.
 // No atomics anywhere: every element is summed in an order fixed by (N, L, q, pass size), so repeated calls give the same bits.
 //
-// Optimiser: L-BFGS (m = 5) on device vectors with the More-Thuente line search (strong Wolfe conditions, as plm_engine.hip's,
-// whose interval update is restated here); only scalars cross to the host.
+// Optimiser: L-BFGS (m = 5) on device vectors with the More-Thuente line search (strong Wolfe conditions) that plmDCA runs
+// too: more_thuente.h, with up to 20 evaluations per search here; the elementwise vector kernels are vec_kernels.h's.  Only
+// scalars cross to the host.
 //
 // Sampler ("ar_sample"): chain c visits sites 0 .. L-1 once and draws s_l with sample.hip's rule at beta = 1 from
 // U = Philox(seed; chain, 0, site, 3).  DESIGN.md section 16 has the geometry and the measured numbers.
 #include "dca_internal.h"
+#include "more_thuente.h"
+#include "vec_kernels.h"
 
 #include <algorithm>
 #include <chrono>
@@ -314,36 +317,11 @@ void ar_dot_final_kernel(const double* __restrict__ part, double* __restrict__ o
     if (threadIdx.x == 0) out[0] = sh[0];
 }
 
-__global__ void ar_axpy_kernel(double* __restrict__ y, double a, const double* __restrict__ x, size_t n)
-{
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n) y[i] = y[i] + a * x[i];
-}
-
-__global__ void ar_scale_kernel(double* __restrict__ y, double a, size_t n)
-{
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n) y[i] = a * y[i];
-}
-
 // y = a - b
 __global__ void ar_diff_kernel(double* __restrict__ y, const double* __restrict__ a, const double* __restrict__ b, size_t n)
 {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i < n) y[i] = a[i] - b[i];
-}
-
-// x = xp + t d
-__global__ void ar_step_kernel(double* __restrict__ x, const double* __restrict__ xp, double t, const double* __restrict__ d, size_t n)
-{
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n) x[i] = xp[i] + t * d[i];
-}
-
-__global__ void ar_neg_kernel(double* __restrict__ d, const double* __restrict__ g, size_t n)
-{
-    const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (i < n) d[i] = -g[i];
 }
 
 // Ancestral sampling.  A wave holds 16 chains x 4 lanes; lane w of a chain sums the terms k = w (mod 4), k < l, ascending k
@@ -456,93 +434,6 @@ int ar_pass_size(int n, size_t perSeq)
 }
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
-
-// ---- More-Thuente interval update (More & Thuente 1994), restated from plm_engine.hip
-struct LsPoint { double st, f, d; };
-
-double cubic_min(double u, double fu, double du, double v, double fv, double dv)
-{
-    const double d = v - u;
-    const double theta = (fu - fv) * 3 / d + du + dv;
-    const double s = std::max(std::fabs(theta), std::max(std::fabs(du), std::fabs(dv)));
-    const double a = theta / s;
-    double gamma = s * std::sqrt(a * a - (du / s) * (dv / s));
-    if (v < u) gamma = -gamma;
-    const double p = gamma - du + theta, qd = gamma - du + gamma + dv;
-    return u + (p / qd) * d;
-}
-double cubic_min_clamped(double u, double fu, double du, double v, double fv, double dv, double lo, double hi)
-{
-    const double d = v - u;
-    const double theta = (fu - fv) * 3 / d + du + dv;
-    const double s = std::max(std::fabs(theta), std::max(std::fabs(du), std::fabs(dv)));
-    const double a = theta / s;
-    double gamma = s * std::sqrt(std::max(0.0, a * a - (du / s) * (dv / s)));
-    if (u < v) gamma = -gamma;
-    const double p = gamma - dv + theta, qd = gamma - dv + gamma + du;
-    const double r = p / qd;
-    if (r < 0. && gamma != 0.) return v - r * d;
-    return a < 0 ? hi : lo;
-}
-double quad_min_f(double u, double fu, double du, double v, double fv)
-{
-    const double a = v - u;
-    return u + du / ((fu - fv) / a + du) / 2 * a;
-}
-double quad_min_d(double u, double du, double v, double dv)
-{
-    const double a = u - v;
-    return v + dv / (dv - du) * a;
-}
-
-// 0, or < 0 when the trial point leaves the interval / the direction is no descent
-int mt_update(LsPoint& best, LsPoint& other, double& t, double ft, double dt, double tmin, double tmax, bool& brackt)
-{
-    const bool opposite = (dt * (best.d / std::fabs(best.d)) < 0.);
-    bool bound;
-    double newt;
-    if (brackt) {
-        if (t <= std::min(best.st, other.st) || std::max(best.st, other.st) <= t) return -1;
-        if (0. <= best.d * (t - best.st)) return -2;
-        if (tmax < tmin) return -3;
-    }
-    if (best.f < ft) {
-        brackt = true; bound = true;
-        const double mc = cubic_min(best.st, best.f, best.d, t, ft, dt);
-        const double mq = quad_min_f(best.st, best.f, best.d, t, ft);
-        newt = (std::fabs(mc - best.st) < std::fabs(mq - best.st)) ? mc : mc + 0.5 * (mq - mc);
-    } else if (opposite) {
-        brackt = true; bound = false;
-        const double mc = cubic_min(best.st, best.f, best.d, t, ft, dt);
-        const double mq = quad_min_d(best.st, best.d, t, dt);
-        newt = (std::fabs(mc - t) > std::fabs(mq - t)) ? mc : mq;
-    } else if (std::fabs(dt) < std::fabs(best.d)) {
-        bound = true;
-        const double mc = cubic_min_clamped(best.st, best.f, best.d, t, ft, dt, tmin, tmax);
-        const double mq = quad_min_d(best.st, best.d, t, dt);
-        if (brackt) newt = (std::fabs(t - mc) < std::fabs(t - mq)) ? mc : mq;
-        else newt = (std::fabs(t - mc) > std::fabs(t - mq)) ? mc : mq;
-    } else {
-        bound = false;
-        if (brackt) newt = cubic_min(t, ft, dt, other.st, other.f, other.d);
-        else newt = (best.st < t) ? tmax : tmin;
-    }
-    if (best.f < ft) {
-        other = LsPoint{t, ft, dt};
-    } else {
-        if (opposite) other = best;
-        best = LsPoint{t, ft, dt};
-    }
-    newt = std::min(newt, tmax);
-    newt = std::max(newt, tmin);
-    if (brackt && bound) {
-        const double mq = best.st + 0.66 * (other.st - best.st);
-        if (best.st < other.st) newt = std::min(newt, mq);
-        else newt = std::max(newt, mq);
-    }
-    t = newt;
-    return 0;
-}
 
 }  // namespace
 
@@ -704,65 +595,22 @@ struct ArEngine {
         return DCA_OK;
     }
 
-    void vstep(double* x, const double* xp, double t, const double* d)
-    {
-        hipLaunchKernelGGL(ar_step_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, x, xp, t, d, P);
-    }
-    void vaxpy(double* y, double a, const double* x)
-    {
-        hipLaunchKernelGGL(ar_axpy_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, y, a, x, P);
-    }
+    // elementwise vector kernels (vec_kernels.h) over the P parameters
+    dim3 vgrid() const { return dim3(std::min(blocks_of(P), (unsigned)kVecBlocks)); }
+    void vneg(double* d, const double* g) { hipLaunchKernelGGL(vec_neg_kernel<double>, vgrid(), dim3(kVecThreads), 0, ctx->stream, d, g, P); }
+    void vstep(double* x, const double* xp, double t, const double* d) { hipLaunchKernelGGL(vec_step_kernel<double>, vgrid(), dim3(kVecThreads), 0, ctx->stream, x, xp, t, d, P); }
+    void vaxpy(double* y, double a, const double* x) { hipLaunchKernelGGL(vec_axpy_kernel<double>, vgrid(), dim3(kVecThreads), 0, ctx->stream, y, a, x, P); }
+    void vscale(double* y, double a) { hipLaunchKernelGGL(vec_scale_kernel<double>, vgrid(), dim3(kVecThreads), 0, ctx->stream, y, a, P); }
 
-    // More-Thuente line search from xp along dd (x = xp + stp d): > 0 evaluations on success, < 0 failure; *rc runtime errors
+    // More-Thuente line search (more_thuente.h) from xp along dd (x = xp + stp d): > 0 evaluations on success, < 0 failure;
+    // *rc runtime errors
     int line_search(double* stp, double* f, double dginit, double* gg, double* xx, int* rc)
     {
-        const double ftol = 1e-4, gtol = 0.9, xtol = 1e-16, min_step = 1e-20, max_step = 1e20;
-        const int max_ls = 20;
-        int count = 0, uinfo = 0;
-        bool brackt = false, stage1 = true;
-        *rc = DCA_OK;
-        if (*stp <= 0.) return -1;
-        if (0 <= dginit) return -2;
-        const double finit = *f;
-        const double dgtest = ftol * dginit;
-        double width = max_step - min_step, prev_width = 2.0 * width;
-        LsPoint bx{0., finit, dginit}, by{0., finit, dginit};
-        for (;;) {
-            double stmin, stmax;
-            if (brackt) { stmin = std::min(bx.st, by.st); stmax = std::max(bx.st, by.st); }
-            else { stmin = bx.st; stmax = *stp + 4.0 * (*stp - bx.st); }
-            if (*stp < min_step) *stp = min_step;
-            if (max_step < *stp) *stp = max_step;
-            if ((brackt && ((*stp <= stmin || stmax <= *stp) || max_ls <= count + 1 || uinfo != 0)) ||
-                (brackt && (stmax - stmin <= xtol * stmax)))
-                *stp = bx.st;
-            vstep(dx, dxp, *stp, dd);
-            double dg_ = 0.0;
-            if ((*rc = evaluate(f, dd, &dg_, gg, xx))) return -100;
-            const double ftest1 = finit + *stp * dgtest;
-            ++count;
-            if (brackt && ((*stp <= stmin || stmax <= *stp) || uinfo != 0)) return -3;
-            if (*stp == max_step && *f <= ftest1 && dg_ <= dgtest) return -4;
-            if (*stp == min_step && (ftest1 < *f || dgtest <= dg_)) return -5;
-            if (brackt && (stmax - stmin) <= xtol * stmax) return -6;
-            if (max_ls <= count) return -7;
-            if (*f <= ftest1 && std::fabs(dg_) <= gtol * (-dginit)) return count;      // strong Wolfe conditions
-            if (stage1 && *f <= ftest1 && std::min(ftol, gtol) * dginit <= dg_) stage1 = false;
-            if (stage1 && ftest1 < *f && *f <= bx.f) {
-                LsPoint mx{bx.st, bx.f - bx.st * dgtest, bx.d - dgtest};
-                LsPoint my{by.st, by.f - by.st * dgtest, by.d - dgtest};
-                uinfo = mt_update(mx, my, *stp, *f - *stp * dgtest, dg_ - dgtest, stmin, stmax, brackt);
-                bx = LsPoint{mx.st, mx.f + mx.st * dgtest, mx.d + dgtest};
-                by = LsPoint{my.st, my.f + my.st * dgtest, my.d + dgtest};
-            } else {
-                uinfo = mt_update(bx, by, *stp, *f, dg_, stmin, stmax, brackt);
-            }
-            if (brackt) {
-                if (0.66 * prev_width <= std::fabs(by.st - bx.st)) *stp = bx.st + 0.5 * (by.st - bx.st);
-                prev_width = width;
-                width = std::fabs(by.st - bx.st);
-            }
-        }
+        const MtParams params{1e-4, 0.9, 1e-16, 1e-20, 1e20, 20};
+        return mt_line_search(params, stp, f, &dginit, false, [&](double t, double* ft, double* dgt) {
+            vstep(dx, dxp, t, dd);
+            return evaluate(ft, dd, dgt, gg, xx);
+        }, rc);
     }
 
     int fit(int max_iterations, double epsilon, dca_ar_stats* st)
@@ -781,7 +629,7 @@ struct ArEngine {
         DCA_TRY(evaluate(&fx, nullptr, nullptr, &gg, &xx));
         int status = DCA_AR_MAX_ITERATIONS, k = 0, stored = 0, newest = -1;
         double ys[M] = {}, alpha[M] = {};
-        hipLaunchKernelGGL(ar_neg_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dd, dg, P);
+        vneg(dd, dg);
         double dginit = -gg;
         double step = gg > 0.0 ? 1.0 / std::sqrt(gg) : 1.0;
         int rc = DCA_OK;
@@ -791,6 +639,8 @@ struct ArEngine {
             std::swap(dx, dxp);
             std::swap(dg, dgp);
             const double fprev = fx, ggprev = gg, xxprev = xx;
+            // the search rejects 0 < dginit, as the reference's does, and would take a zero slope; none reaches it: dginit
+            // is -gg, where gg = 0 has converged above (epsilon >= 0), or the g.d that the reset below found < 0
             const int ls = line_search(&step, &fx, dginit, &gg, &xx, &rc);
             if (rc) return rc;
             if (ls < 0) {                                     // back to the last accepted point
@@ -817,7 +667,7 @@ struct ArEngine {
                 stored = std::min(stored + 1, M);
             }
             // two-loop recursion: d = -H g
-            hipLaunchKernelGGL(ar_neg_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dd, dg, P);
+            vneg(dd, dg);
             for (int i = 0, j = newest; i < stored; ++i, j = (j + M - 1) % M) {
                 const double sd = dot(dS[j], dd, &rc);
                 if (rc) return rc;
@@ -825,7 +675,7 @@ struct ArEngine {
                 vaxpy(dd, -alpha[j], dY[j]);
             }
             if (stored > 0 && sy[0] > 0.0)
-                hipLaunchKernelGGL(ar_scale_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dd, sy[0] / sy[1], P);
+                vscale(dd, sy[0] / sy[1]);
             for (int i = 0, j = (newest + M - stored + 1) % M; i < stored; ++i, j = (j + 1) % M) {
                 const double yd = dot(dY[j], dd, &rc);
                 if (rc) return rc;
@@ -834,7 +684,7 @@ struct ArEngine {
             dginit = dot(dg, dd, &rc);
             if (rc) return rc;
             if (!(dginit < 0.0)) {                            // not a descent direction: restart from steepest descent
-                hipLaunchKernelGGL(ar_neg_kernel, dim3(blocks_of(P)), dim3(256), 0, ctx->stream, dd, dg, P);
+                vneg(dd, dg);
                 dginit = -gg;
                 stored = 0;
                 step = 1.0 / std::sqrt(gg);

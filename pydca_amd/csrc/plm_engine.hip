@@ -18,13 +18,10 @@
 #include <cmath>
 
 #include "dca_internal.h"
+#include "more_thuente.h"
+#include "vec_kernels.h"
 
 namespace {
-
-template <typename T> struct V16;
-template <> struct V16<float> { using type = float4; };
-template <> struct V16<double> { using type = double2; };
-
 
 #ifdef DCA_FAST_EXP
 __device__ __forceinline__ float t_exp(float v) { return __expf(v); }
@@ -964,94 +961,7 @@ void plm_fold_pairs_kernel(const T* __restrict__ x, const T* __restrict__ G, T* 
     if (lane == 0) { regPart[2 * (size_t)p] = reg; regPart[2 * (size_t)p + 1] = regLo; }
 }
 
-// ------------------------------------------------------------------ L-BFGS vector kernels
-constexpr int kVecBlocks = 1024;
-constexpr int kVecThreads = 256;
-
-// All vector kernels stream 16 bytes per lane and load (4 floats / 2 doubles): with 4-byte loads a
-// wave has too few bytes in flight to approach HBM bandwidth.  Element k of a pack is element
-// iv*VEC + k; the n % VEC tail is handled by the first threads with scalar accesses.  The mapping
-// of elements to threads is fixed, so every reduction is deterministic.
-template <typename T> struct Pack { T v[16 / sizeof(T)]; };
-template <typename T> __device__ __forceinline__ Pack<T> ldp_at(const T* p, size_t iv)
-{
-    using V = typename V16<T>::type;
-    const V r = reinterpret_cast<const V*>(p)[iv];
-    Pack<T> o;
-    if constexpr (sizeof(T) == 4) { o.v[0] = r.x; o.v[1] = r.y; o.v[2] = r.z; o.v[3] = r.w; }
-    else { o.v[0] = r.x; o.v[1] = r.y; }
-    return o;
-}
-template <typename T> __device__ __forceinline__ void stp_at(T* p, size_t iv, const Pack<T>& o)
-{
-    using V = typename V16<T>::type;
-    V r;
-    if constexpr (sizeof(T) == 4) { r.x = o.v[0]; r.y = o.v[1]; r.z = o.v[2]; r.w = o.v[3]; }
-    else { r.x = o.v[0]; r.y = o.v[1]; }
-    reinterpret_cast<V*>(p)[iv] = r;
-}
-// The vectors of one call all start at the SAME element offset of 256-byte aligned allocations (base + vlo), so they share
-// their misalignment.  With sequence sharding vlo is a multiple of four elements (set_slices); with column strips (exchange
-// mode 4) it is the start of the rank's pair range, L q + pairs q^2 -- any parity.  ALIGNP names one of the vectors: the
-// head_ elements in front of its first 16-byte boundary are handled with the tail, one element per thread, and the packs
-// start at that boundary (ldp / stp inside the loop body index from there), so every 16-byte access is aligned.
-#define ldp(p, iv) ldp_at((p) + head_, iv)
-#define stp(p, iv, o) stp_at((p) + head_, iv, o)
-#define DCA_VEC_LOOP(n, ALIGNP, BODY_PACK, BODY_TAIL) DCA_VEC_LOOP_G(n, ALIGNP, gridDim.x, BODY_PACK, BODY_TAIL)
-/* GRID: the number of workgroups that walk the vector (a launch may carry other workgroups behind them) */
-#define DCA_VEC_LOOP_G(n, ALIGNP, GRID, BODY_PACK, BODY_TAIL)                                             \
-    {                                                                                                      \
-        constexpr int VEC = 16 / (int)sizeof(T);                                                           \
-        const size_t lead_ = ((16 - (reinterpret_cast<uintptr_t>(ALIGNP) & 15)) & 15) / sizeof(T);         \
-        const size_t head_ = lead_ < (size_t)(n) ? lead_ : (size_t)(n);                                    \
-        const size_t nv_ = ((n) - head_) / VEC, stride_ = (size_t)(GRID) * blockDim.x;                     \
-        const size_t t0_ = blockIdx.x * (size_t)blockDim.x + threadIdx.x;                                  \
-        for (size_t iv = t0_; iv < nv_; iv += stride_) { BODY_PACK }                                       \
-        const size_t rest_ = (n) - nv_ * VEC;                     /* head_ + tail, fewer than 2 VEC */      \
-        for (size_t r_ = t0_; r_ < rest_; r_ += stride_) {                                                 \
-            const size_t i = r_ < head_ ? r_ : r_ + nv_ * VEC;                                             \
-            BODY_TAIL                                                                                      \
-        }                                                                                                  \
-    }
-
-template <typename T>
-__global__ void vec_neg_kernel(T* __restrict__ d, const T* __restrict__ g, size_t n)
-{
-    DCA_VEC_LOOP(n, d,
-        Pack<T> a = ldp(g, iv);
-        _Pragma("unroll") for (int k = 0; k < VEC; ++k) a.v[k] = -a.v[k];
-        stp(d, iv, a);,
-        d[i] = -g[i];)
-}
-template <typename T>
-__global__ void vec_axpy_kernel(T* __restrict__ y, T a, const T* __restrict__ x, size_t n)
-{
-    DCA_VEC_LOOP(n, y,
-        Pack<T> yy = ldp(y, iv); const Pack<T> xx = ldp(x, iv);
-        _Pragma("unroll") for (int k = 0; k < VEC; ++k) yy.v[k] += a * xx.v[k];
-        stp(y, iv, yy);,
-        y[i] += a * x[i];)
-}
-template <typename T>
-__global__ void vec_scale_kernel(T* __restrict__ y, T a, size_t n)
-{
-    DCA_VEC_LOOP(n, y,
-        Pack<T> yy = ldp(y, iv);
-        _Pragma("unroll") for (int k = 0; k < VEC; ++k) yy.v[k] *= a;
-        stp(y, iv, yy);,
-        y[i] *= a;)
-}
-// x = xp + stp*d, as lbfgs.cpp:902-903 (copy, then add the rounded product)
-template <typename T>
-__global__ void vec_step_kernel(T* __restrict__ x, const T* __restrict__ xp, T stpv, const T* __restrict__ d, size_t n)
-{
-    DCA_VEC_LOOP(n, x,
-        const Pack<T> dd = ldp(d, iv); Pack<T> xx = ldp(xp, iv);
-        _Pragma("unroll") for (int k = 0; k < VEC; ++k) { const T v = stpv * dd.v[k]; xx.v[k] = xx.v[k] + v; }
-        stp(x, iv, xx);,
-        { const T v = stpv * d[i]; x[i] = xp[i] + v; })
-}
-
+// ------------------------------------------------------------------ L-BFGS vector kernels (the elementwise ones: vec_kernels.h)
 __device__ __forceinline__ void block_reduce_store(double v, double* red, double* out)
 {
     red[threadIdx.x] = v;
@@ -1422,100 +1332,6 @@ __global__ void cast_weights_kernel(const double* __restrict__ wd, T* __restrict
 {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n < N) w[n] = (T)wd[n];
-}
-
-// ======================================================================
-// More-Thuente trial-interval update, restated from More & Thuente (1994) with the
-// safeguards the reference's library applies (lbfgs.cpp:1128-1295).  Scalars are double.
-struct LsPoint { double st, f, d; };
-
-double cubic_min(double u, double fu, double du, double v, double fv, double dv)
-{
-    const double d = v - u;
-    const double theta = (fu - fv) * 3 / d + du + dv;
-    const double s = std::max(std::fabs(theta), std::max(std::fabs(du), std::fabs(dv)));
-    const double a = theta / s;
-    double gamma = s * std::sqrt(a * a - (du / s) * (dv / s));
-    if (v < u) gamma = -gamma;
-    const double p = gamma - du + theta, q = gamma - du + gamma + dv;
-    return u + (p / q) * d;
-}
-double cubic_min_clamped(double u, double fu, double du, double v, double fv, double dv, double lo, double hi)
-{
-    const double d = v - u;
-    const double theta = (fu - fv) * 3 / d + du + dv;
-    const double s = std::max(std::fabs(theta), std::max(std::fabs(du), std::fabs(dv)));
-    const double a = theta / s;
-    double gamma = s * std::sqrt(std::max(0.0, a * a - (du / s) * (dv / s)));
-    if (u < v) gamma = -gamma;
-    const double p = gamma - dv + theta, q = gamma - dv + gamma + du;
-    const double r = p / q;
-    if (r < 0. && gamma != 0.) return v - r * d;
-    return a < 0 ? hi : lo;
-}
-double quad_min_f(double u, double fu, double du, double v, double fv)
-{
-    const double a = v - u;
-    return u + du / ((fu - fv) / a + du) / 2 * a;
-}
-double quad_min_d(double u, double du, double v, double dv)
-{
-    const double a = u - v;
-    return v + dv / (dv - du) * a;
-}
-
-enum {
-    LB_OUTOFINTERVAL = -1003, LB_INCORRECT_TMINMAX = -1002, LB_ROUNDING_ERROR = -1001, LB_MINIMUMSTEP = -1000,
-    LB_MAXIMUMSTEP = -999, LB_MAXIMUMLINESEARCH = -998, LB_MAXIMUMITERATION = -997, LB_WIDTHTOOSMALL = -996,
-    LB_INVALIDPARAMETERS = -995, LB_INCREASEGRADIENT = -994, LB_ALREADY_MINIMIZED = 2
-};
-
-int mt_update(LsPoint& best, LsPoint& other, double& t, double ft, double dt, double tmin, double tmax, bool& brackt)
-{
-    const bool opposite = (dt * (best.d / std::fabs(best.d)) < 0.);
-    bool bound;
-    double newt;
-    if (brackt) {
-        if (t <= std::min(best.st, other.st) || std::max(best.st, other.st) <= t) return LB_OUTOFINTERVAL;
-        if (0. <= best.d * (t - best.st)) return LB_INCREASEGRADIENT;
-        if (tmax < tmin) return LB_INCORRECT_TMINMAX;
-    }
-    if (best.f < ft) {
-        brackt = true; bound = true;
-        const double mc = cubic_min(best.st, best.f, best.d, t, ft, dt);
-        const double mq = quad_min_f(best.st, best.f, best.d, t, ft);
-        newt = (std::fabs(mc - best.st) < std::fabs(mq - best.st)) ? mc : mc + 0.5 * (mq - mc);
-    } else if (opposite) {
-        brackt = true; bound = false;
-        const double mc = cubic_min(best.st, best.f, best.d, t, ft, dt);
-        const double mq = quad_min_d(best.st, best.d, t, dt);
-        newt = (std::fabs(mc - t) > std::fabs(mq - t)) ? mc : mq;
-    } else if (std::fabs(dt) < std::fabs(best.d)) {
-        bound = true;
-        const double mc = cubic_min_clamped(best.st, best.f, best.d, t, ft, dt, tmin, tmax);
-        const double mq = quad_min_d(best.st, best.d, t, dt);
-        if (brackt) newt = (std::fabs(t - mc) < std::fabs(t - mq)) ? mc : mq;
-        else newt = (std::fabs(t - mc) > std::fabs(t - mq)) ? mc : mq;
-    } else {
-        bound = false;
-        if (brackt) newt = cubic_min(t, ft, dt, other.st, other.f, other.d);
-        else newt = (best.st < t) ? tmax : tmin;
-    }
-    if (best.f < ft) {
-        other = LsPoint{t, ft, dt};
-    } else {
-        if (opposite) other = best;
-        best = LsPoint{t, ft, dt};
-    }
-    newt = std::min(newt, tmax);
-    newt = std::max(newt, tmin);
-    if (brackt && bound) {
-        const double mq = best.st + 0.66 * (other.st - best.st);
-        if (best.st < other.st) newt = std::min(newt, mq);
-        else newt = std::max(newt, mq);
-    }
-    t = newt;
-    return 0;
 }
 
 template <typename T>
@@ -2384,71 +2200,23 @@ struct PlmEngine : PlmEngineBase {
         return DCA_OK;
     }
 
-    // More-Thuente line search (lbfgs.cpp:815-1004) on device vectors.  Returns the number
-    // of evaluations (>0) or a libLBFGS error code; *rc_hip carries runtime failures.
+    // More-Thuente line search (more_thuente.h) on device vectors.  Returns the number of evaluations (>0) or a libLBFGS
+    // error code; *rc_hip carries runtime failures.
     int line_search(double* stp, double* f, double* xx, double* gg, int* rc_hip)
     {
-        const double ftol = 1e-4, gtol = 0.9, xtol = 1e-16, min_step = 1e-20, max_step = 1e20;
-        const int max_ls = 5;
-        int count = 0, uinfo = 0;
-        bool brackt = false, stage1 = true;
-        // g.d of the direction: known on the host, or still on its way from the device's two-loop recursion -- then it
-        // arrives with the scalars of the first evaluation (nothing before that evaluation depends on it)
-        double dginit = o.dginit;
-        bool have_dginit = !o.dginit_on_device;
-        *rc_hip = 0;
-        if (*stp <= 0.) return LB_INVALIDPARAMETERS;
-        if (have_dginit && 0 < dginit) return LB_INCREASEGRADIENT;
-        const double finit = *f;
-        double dgtest = ftol * dginit;
-        double width = max_step - min_step, prev_width = 2.0 * width;
-        LsPoint bx{0., finit, dginit}, by{0., finit, dginit};
-        for (;;) {
-            double stmin, stmax;
-            if (brackt) { stmin = std::min(bx.st, by.st); stmax = std::max(bx.st, by.st); }
-            else { stmin = bx.st; stmax = *stp + 4.0 * (*stp - bx.st); }
-            if (*stp < min_step) *stp = min_step;
-            if (max_step < *stp) *stp = max_step;
-            if ((brackt && ((*stp <= stmin || stmax <= *stp) || max_ls <= count + 1 || uinfo != 0)) ||
-                (brackt && (stmax - stmin <= xtol * stmax)))
-                *stp = bx.st;
-            v_step(dx, dxp, *stp, dd);
+        const MtParams params{1e-4, 0.9, 1e-16, 1e-20, 1e20, 5};     // plmdcaBackend.cpp:68-75 over lbfgs.cpp:116-121
+        // g.d of the direction: known on the host, or still on its way from the device's two-loop recursion -- then
+        // eval_scalars brings it into o.dginit with the scalars of the first evaluation
+        const bool deferred = o.dginit_on_device;
+        const int ls = mt_line_search(params, stp, f, &o.dginit, deferred, [&](double t, double* ft, double* dgt) {
+            v_step(dx, dxp, t, dd);
             DCA_ROUND_STAGE(32, dx, P);
-            if ((*rc_hip = publish_x())) return 0;            // sharded vectors: every rank needs the x its evaluation reads
-            if ((*rc_hip = evaluate_async(true))) return 0;
-            double dg_;
-            if ((*rc_hip = eval_scalars(f, &dg_, xx, gg))) return 0;
-            if (!have_dginit) {
-                have_dginit = true;
-                dginit = o.dginit;
-                if (0 < dginit) { o.evals -= 1; *f = finit; return LB_INCREASEGRADIENT; }    // the reference returns before evaluating (lbfgs.cpp:858-861); the caller restores x, g
-                dgtest = ftol * dginit;
-                bx.d = by.d = dginit;
-            }
-            const double ftest1 = finit + *stp * dgtest;
-            ++count;
-            if (brackt && ((*stp <= stmin || stmax <= *stp) || uinfo != 0)) return LB_ROUNDING_ERROR;
-            if (*stp == max_step && *f <= ftest1 && dg_ <= dgtest) return LB_MAXIMUMSTEP;
-            if (*stp == min_step && (ftest1 < *f || dgtest <= dg_)) return LB_MINIMUMSTEP;
-            if (brackt && (stmax - stmin) <= xtol * stmax) return LB_WIDTHTOOSMALL;
-            if (max_ls <= count) return LB_MAXIMUMLINESEARCH;
-            if (*f <= ftest1 && std::fabs(dg_) <= gtol * (-dginit)) return count;
-            if (stage1 && *f <= ftest1 && std::min(ftol, gtol) * dginit <= dg_) stage1 = false;
-            if (stage1 && ftest1 < *f && *f <= bx.f) {
-                LsPoint mx{bx.st, bx.f - bx.st * dgtest, bx.d - dgtest};
-                LsPoint my{by.st, by.f - by.st * dgtest, by.d - dgtest};
-                uinfo = mt_update(mx, my, *stp, *f - *stp * dgtest, dg_ - dgtest, stmin, stmax, brackt);
-                bx = LsPoint{mx.st, mx.f + mx.st * dgtest, mx.d + dgtest};
-                by = LsPoint{my.st, my.f + my.st * dgtest, my.d + dgtest};
-            } else {
-                uinfo = mt_update(bx, by, *stp, *f, dg_, stmin, stmax, brackt);
-            }
-            if (brackt) {
-                if (0.66 * prev_width <= std::fabs(by.st - bx.st)) *stp = bx.st + 0.5 * (by.st - bx.st);
-                prev_width = width;
-                width = std::fabs(by.st - bx.st);
-            }
-        }
+            DCA_TRY(publish_x());                 // sharded vectors: every rank needs the x its evaluation reads
+            DCA_TRY(evaluate_async(true));
+            return eval_scalars(ft, dgt, xx, gg);
+        }, rc_hip);
+        if (deferred && ls == LB_INCREASEGRADIENT) o.evals -= 1;     // the reference returns before evaluating (lbfgs.cpp:858-861); the caller restores x, g
+        return ls;
     }
 
     void lbfgs_end() override { o = decltype(o)(); }
