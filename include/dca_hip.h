@@ -458,7 +458,7 @@ int dca_di_from_fields(dca_ctx* ctx, const double* couplings, int layout, const 
 
 /* ------------------------------------------------------------------ ranking
  * Pair indices of the most recent score vector computed on this context (dca_plm_scores,
- * dca_plm_di_scores, dca_mf_scores, dca_mf_di_scores, dca_mf_run) in descending score order,
+ * dca_plm_di_scores, dca_mf_scores, dca_mf_di_scores, dca_mf_run, dca_ar_epistatic_scores) in descending score order,
  * equal scores in ascending pair order: the sorted(..., reverse=True) step of
  * compute_sorted_FN / _APC / DI (meanfield_dca.py:941, plmdca.py:479), done on the device copy. */
 int dca_scores_order(dca_ctx* ctx, int32_t* order_out, int capacity);
@@ -574,6 +574,31 @@ int dca_ar_log_probabilities(dca_ctx* ctx, const uint8_t* X, int n, double* logp
  * codes (host, model order).  Chain k's codes depend only on x, seed and first_chain + k.  DCA_ERR_ARG: n < 0, out NULL with
  * n > 0, L > 10240; n == 0 is DCA_OK.  Profiling tag "ar_sample". */
 int dca_ar_sample(dca_ctx* ctx, int n, uint64_t seed, uint64_t first_chain, uint8_t* out);
+/* Double-mutant epistasis of the wild type w (L codes < q, model order; host) under the current x.  With w^{k->a} the wild type
+ * with site k set to a (all q states, the gap included):
+ *   d_k(a)       = log P(w^{k->a}) - log P(w)                                                   single_out[k*q + a]
+ *   eps_kl(a, b) = log P(w^{k->a, l->b}) - log P(w^{k->a}) - log P(w^{l->b}) + log P(w),  k < l    eps_out[(pair*q + a)*q + b]
+ * in pair order (0,1),(0,2)...,(1,2)..., a the state of the EARLIER site k; the double-mutant effect is d_k(a) + d_l(b) +
+ * eps_kl(a, b).  No mutant sequence is formed: with cond_m the wild type's conditionals, p_m(c) = exp cond_m(c) and, for k < m,
+ * U^k_m(a, c) = exp(J_km(a, c) - J_km(w_k, c)), S_m(k, a) = sum_c p_m(c) U^k_m(a, c), V^k_m(a, c) = U^k_m(a, c) / S_m(k, a):
+ *   d_k(a)       = (cond_k(a) - cond_k(w_k)) + sum_{m>k} [(J_km(a, w_m) - J_km(w_k, w_m)) - log S_m(k, a)]   (m ascending)
+ *   eps_kl(a, b) = T - log prod_{m>l} r_m,  r_m = sum_c (p_m(c) V^k_m(a, c)) V^l_m(b, c)          (c ascending, fused multiply-adds;
+ *   T            = (J_kl(a, b) - J_kl(w_k, b)) - (J_kl(a, w_l) - J_kl(w_k, w_l))                   m ascending in the product)
+ * The product's exponent is split off into an integer every 4th factor and one logarithm is taken at the end, so 4 consecutive
+ * r_m may together span 2^+-1000.  The order of every sum depends on (L, q) alone: repeated calls, and calls with either or both
+ * outputs, give the same bits.  Entries with a = w_k or b = w_l are 0.0 exactly, and d_k(w_k) = 0.0.  Either output may be NULL,
+ * not both.  Device scratch: 2 L(L-1)/2 q^2 doubles (880 MB at L = 500, q = 21) from the context's pool; DCA_ERR_NOMEM when it
+ * is not there.  The alignment, the weights, x and g are not touched.  DCA_ERR_ARG: wildtype NULL, a code >= q, both outputs
+ * NULL; DCA_ERR_STATE before the first dca_ar_configure.  Profiling tag "ar_epistasis" (the wild-type pass: "ar_logits"). */
+int dca_ar_epistasis(dca_ctx* ctx, const uint8_t* wildtype, double* eps_out /* pairs*q*q, may be NULL */,
+                     double* single_out /* L*q, may be NULL */);
+/* Contact scores from that table: eps as a plm-layout vector (L*q zero fields, then the pair blocks) through the path of
+ * dca_plm_scores -- gap row and column dropped, the (q-1) x (q-1) block double-centred, Frobenius norm, APC-corrected with
+ * apc != 0 -- in pair order over the MODEL's sites (FN and APC do not change under transposition of a block or relabelling of
+ * the sites, so a caller with another site order relabels the pairs).  The score vector stays on the device for
+ * dca_scores_order, as after dca_plm_scores; like it, any L >= 2 is served.  Errors as dca_ar_epistasis (scores_out NULL:
+ * DCA_ERR_ARG); q > 21: DCA_ERR_ARG (the scoring kernel's limit). */
+int dca_ar_epistatic_scores(dca_ctx* ctx, const uint8_t* wildtype, int apc, double* scores_out /* pairs */);
 int dca_ar_release(dca_ctx* ctx);
 
 /* ------------------------------------------------------------------ comparing sequence sets with the alignment
@@ -617,7 +642,7 @@ int dca_alignment_statistics(dca_ctx* ctx, double* fi_out, double* fij_out);
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
- * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "ar_logits", "ar_grad", "ar_sample",
+ * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "ar_logits", "ar_grad", "ar_sample", "ar_epistasis",
  * "bm_stats", "ais", "hamming", "set_compare"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it

@@ -160,6 +160,8 @@ def lib():
         "dca_ar_log_probabilities": (i, [vp, vp, i, vp, vp, vp]),
         "dca_ar_sample": (i, [vp, i, C.c_uint64, C.c_uint64, vp]),
         "dca_ar_release": (i, [vp]),
+        "dca_ar_epistasis": (i, [vp, vp, vp, vp]),
+        "dca_ar_epistatic_scores": (i, [vp, vp, i, vp]),
         "dca_plm_bm_begin": (i, [vp, C.POINTER(BmArgs)]),
         "dca_plm_bm_iterate": (i, [vp, i, vp]),
         "dca_plm_bm_freqs": (i, [vp, i, vp, vp]),
@@ -215,6 +217,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_plm_sample", "dca_mf_sample", "dca_philox4x32_10",
            "dca_ar_configure", "dca_ar_num_params", "dca_ar_init_x", "dca_ar_set_x", "dca_ar_get_x", "dca_ar_gradient", "dca_ar_get_g",
            "dca_ar_fit", "dca_ar_log_probabilities", "dca_ar_sample", "dca_ar_release",
+           "dca_ar_epistasis", "dca_ar_epistatic_scores",
            "dca_plm_bm_begin", "dca_plm_bm_iterate", "dca_plm_bm_freqs", "dca_plm_bm_chains", "dca_plm_bm_end",
            "dca_plm_ais", "dca_mf_ais", "dca_ais_estimate",
            "dca_hamming_nearest", "dca_sequence_statistics", "dca_alignment_statistics",
@@ -783,6 +786,28 @@ class Context:
 
     def ar_release(self):
         check(self._l.dca_ar_release(self._h))
+
+    def _ar_wildtype(self, wildtype):
+        w = np.ascontiguousarray(wildtype, dtype=np.uint8).reshape(-1)
+        if w.size != self.L:
+            raise ValueError("the wild type must hold L = %d codes, not %d" % (self.L, w.size))
+        return w
+
+    def ar_epistasis(self, wildtype, eps=True, single=True):
+        """dca_ar_epistasis of the wild type (L codes, model order) -> (eps float64[pairs, q, q] in pair order, a at the earlier
+        site, or None; d float64[L, q] or None)."""
+        w = self._ar_wildtype(wildtype)
+        e = np.zeros((self.L * (self.L - 1) // 2, self.q, self.q), dtype=np.float64) if eps else None
+        d = np.zeros((self.L, self.q), dtype=np.float64) if single else None
+        check(self._l.dca_ar_epistasis(self._h, _ptr(w), _ptr(e) if eps else None, _ptr(d) if single else None))
+        return e, d
+
+    def ar_epistatic_scores(self, wildtype, apc=True):
+        """dca_ar_epistatic_scores -> float64[pairs] in pair order over the model's sites; scores_order() ranks them."""
+        w = self._ar_wildtype(wildtype)
+        out = np.zeros(self.L * (self.L - 1) // 2, dtype=np.float64)
+        check(self._l.dca_ar_epistatic_scores(self._h, _ptr(w), int(bool(apc)), _ptr(out)))
+        return out
 
     # ---- Boltzmann machine learning of x (boltzmann.hip): persistent chains on the device, records (eps_h, eps_J, pearson)
     def plm_bm_begin(self, chains, sweeps, equilibration_sweeps, seed=0, eta_h=0.0, eta_J=0.0, mu_h=0.0, mu_J=0.0,

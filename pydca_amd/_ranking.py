@@ -87,3 +87,12 @@ def ranked(scores, L, order=None):
     finally:
         if was_enabled:
             gc.enable()
+
+
+def mapped_site_pairs(sorted_dca_scores, seqbackmapper):
+    """Keeps the site pairs of a ranked list whose two MSA columns map to the reference sequence, renames them to reference
+    positions and sorts again (meanfield_dca.py:755-790, plmdca.py:527-562) -> (tuple of ((i, j), score), the mapping)."""
+    mapping_dict = seqbackmapper.map_to_reference_sequence()
+    mapped = [((mapping_dict[i], mapping_dict[j]), score) for (i, j), score in sorted_dca_scores
+              if i in mapping_dict and j in mapping_dict]
+    return tuple(sorted(mapped, key=lambda k: k[1], reverse=True)), mapping_dict

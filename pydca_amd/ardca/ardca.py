@@ -11,7 +11,8 @@ import os
 
 import numpy as np
 
-from .. import _compare, _lib, _potts
+from .. import _compare, _lib, _potts, _ranking
+from ..fasta_reader import fasta_reader
 
 logger = logging.getLogger(__name__)
 
@@ -59,6 +60,52 @@ def _number(name, v, low, integer=False):
     if not math.isfinite(f) or f < low or (integer and int(f) != f):
         raise ArDCAException('{} must be {} >= {}, not {!r}'.format(name, 'an integer' if integer else 'a finite number', low, v))
     return int(f) if integer else f
+
+
+def checked_pairs(pairs, L):
+    """pairs of compute_epistasis: a list of (i, j), i != j, 0-based file sites -> int64[P, 2]; ArDCAException otherwise."""
+    try:
+        arr = np.asarray(pairs)
+    except Exception:
+        raise ArDCAException('pairs must be a list of (i, j) site pairs, not {!r}'.format(pairs))
+    if arr.size == 0:
+        return np.zeros((0, 2), dtype=np.int64)
+    if arr.ndim != 2 or arr.shape[1] != 2 or arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise ArDCAException('pairs must be a list of (i, j) pairs of integer sites, not {!r}'.format(pairs))
+    arr = arr.astype(np.int64)
+    if arr.min() < 0 or arr.max() >= L:
+        raise ArDCAException('a site of pairs lies outside 0 .. {}'.format(L - 1))
+    same = np.nonzero(arr[:, 0] == arr[:, 1])[0]
+    if same.size:
+        raise ArDCAException('pair {} names site {} twice'.format(int(same[0]), int(arr[same[0], 0])))
+    return arr
+
+
+def model_pairs(site_order, pairs):
+    """File-site pairs (i, j) -> (index of the model's pair block, transposed?): the block of the model positions of i and j in
+    pair order, and whether the model places j before i (the block then has j's state first)."""
+    L = len(site_order)
+    inv = np.argsort(np.asarray(site_order, dtype=np.int64))
+    pi, pj = inv[pairs[:, 0]], inv[pairs[:, 1]]
+    k, l = np.minimum(pi, pj), np.maximum(pi, pj)
+    return L * (L - 1) // 2 - (L - k) * (L - k - 1) // 2 + (l - k - 1), pi > pj
+
+
+def file_pair_blocks(blocks_model, site_order, pairs):
+    """blocks_model float64[pairs of the model, q, q] (pair order over model positions, first index the earlier position) ->
+    float64[P, q, q] for the file-site pairs (i, j): first index the state of site i."""
+    idx, transposed = model_pairs(site_order, pairs)
+    out = np.array(blocks_model[idx], dtype=np.float64)
+    out[transposed] = np.transpose(out[transposed], (0, 2, 1))
+    return out
+
+
+def file_pair_scores(scores_model, site_order):
+    """A symmetric pair score in pair order over model positions -> the same in pair order over file sites."""
+    L = len(site_order)
+    iu, ju = np.triu_indices(L, k=1)
+    idx, _t = model_pairs(site_order, np.stack([iu, ju], axis=1))
+    return np.asarray(scores_model)[idx]
 
 
 class ArDCA(_compare.SequenceComparison):
@@ -279,3 +326,67 @@ class ArDCA(_compare.SequenceComparison):
         batch[idx, idx // q] = (idx % q).astype(np.uint8)
         logp = self._log_probabilities(batch)
         return (logp[:L * q] - logp[L * q]).reshape(L, q)
+
+    # ---- double mutants and contacts (ar_epistasis.hip)
+    def _wildtype(self, wildtype):
+        """-> uint8[L] codes in file order; None: the first record of the training file."""
+        if wildtype is None:
+            records = fasta_reader.get_alignment_from_fasta_file(self.__msa_file, same_length=False)
+            if not records:
+                raise ArDCAException('the training file {} holds no record'.format(self.__msa_file))
+            wildtype = str(records[0])
+        return _potts.wildtype_codes(wildtype, self.__biomolecule_int, self.__L, 0, ArDCAException)
+
+    def _all_pairs(self):
+        iu, ju = np.triu_indices(self.__L, k=1)
+        return np.stack([iu, ju], axis=1).astype(np.int64)
+
+    def _epistasis(self, wildtype, pairs, single):
+        w = self._wildtype(wildtype)
+        pairs = self._all_pairs() if pairs is None else checked_pairs(pairs, self.__L)
+        ctx = self._fitted_context()
+        logger.info('\n\tarDCA epistasis of the wild type, {} site pairs'.format(pairs.shape[0]))
+        eps, d = ctx.ar_epistasis(w[self.__order], single=single)
+        blocks = file_pair_blocks(eps, self.__order, pairs)
+        return (blocks, pairs, d[np.argsort(self.__order)]) if single else (blocks, pairs, None)
+
+    def compute_epistasis(self, wildtype=None, pairs=None):
+        """eps_ij(a, b) = log P(wt with i -> a, j -> b) - log P(wt with i -> a) - log P(wt with j -> b) + log P(wt): the
+        non-additive part of every double mutant of the wild type -> float64[P, q, q], a the state of site i (gap last); 0 where
+        a or b is the wild type's own state.  pairs: a list of (i, j), i != j, 0-based file sites; None: all i < j in pair order.
+        wildtype: an aligned string or a FASTA file with one record; None: the first record of the training file."""
+        return self._epistasis(wildtype, pairs, False)[0]
+
+    def compute_double_mutant_effects(self, wildtype=None, pairs=None):
+        """log P(wt with i -> a, j -> b) - log P(wt) = d_i(a) + d_j(b) + eps_ij(a, b) -> float64[P, q, q]; arguments as
+        compute_epistasis."""
+        eps, pairs, d = self._epistasis(wildtype, pairs, True)
+        return d[pairs[:, 0]][:, :, None] + d[pairs[:, 1]][:, None, :] + eps
+
+    def get_mapped_site_pairs_dca_scores(self, sorted_dca_scores, seqbackmapper):
+        """The ranked list on the reference sequence's positions, as PlmDCA.get_mapped_site_pairs_dca_scores."""
+        mapped, _mapping = _ranking.mapped_site_pairs(sorted_dca_scores, seqbackmapper)
+        logger.info('\n\tSite pairs mapped onto the reference sequence: {}'.format(len(mapped)))
+        return mapped
+
+    def _sorted_scores(self, wildtype, apc, seqbackmapper):
+        w = self._wildtype(wildtype)
+        ctx = self._fitted_context()
+        scores = ctx.ar_epistatic_scores(w[self.__order], apc=apc)
+        if np.array_equal(self.__order, np.arange(self.__L)):
+            ranked = _ranking.ranked(scores, self.__L, ctx.scores_order())
+        else:                                          # another site order: relabel, then rank the relabelled vector
+            ranked = _ranking.ranked(file_pair_scores(scores, self.__order), self.__L)
+        return ranked if seqbackmapper is None else self.get_mapped_site_pairs_dca_scores(ranked, seqbackmapper)
+
+    def compute_sorted_FN(self, wildtype=None, seqbackmapper=None):
+        """Contact scores [((i, j), score), ...], best first: the Frobenius norm of the double-centred epistasis block of every
+        site pair without its gap row and column (the scoring of PlmDCA.compute_sorted_FN applied to eps).  Sites in file
+        order, or reference positions with seqbackmapper."""
+        logger.info('\n\tarDCA epistatic scores (Frobenius norm), ranked')
+        return self._sorted_scores(wildtype, False, seqbackmapper)
+
+    def compute_sorted_FN_APC(self, wildtype=None, seqbackmapper=None):
+        """compute_sorted_FN with the average product correction."""
+        logger.info('\n\tarDCA epistatic scores with the average product correction, ranked')
+        return self._sorted_scores(wildtype, True, seqbackmapper)

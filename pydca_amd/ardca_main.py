@@ -1,5 +1,5 @@
-"""`ardca` command line: fit, compute_log_probabilities, compute_log_likelihood, sample_sequences, compute_mutation_effects
-and compare_sequences of the autoregressive model (ArDCA), with the argument names, output directory and file naming of the plmdca / mfdca
+"""`ardca` command line: fit, compute_log_probabilities, compute_log_likelihood, sample_sequences, compute_mutation_effects,
+compare_sequences, compute_fn and compute_epistasis of the autoregressive model (ArDCA), with the argument names, output directory and file naming of the plmdca / mfdca
 sub-commands: <output_dir>/ARDCA_<what>_<alignment base>.txt / .fa / .npy.  No pydca counterpart."""
 import logging
 import os
@@ -14,7 +14,7 @@ from .dca_utilities import dca_utilities
 
 logger = logging.getLogger(__name__)
 ARDCA_SUBCOMMANDS = ('fit', 'compute_log_probabilities', 'compute_log_likelihood', 'sample_sequences', 'compute_mutation_effects',
-                    'compare_sequences')
+                    'compare_sequences', 'compute_fn', 'compute_epistasis')
 _RULE = '#' + '=' * 70
 
 
@@ -72,7 +72,7 @@ def write_mutation_effects(path, dlogp, wildtype_letters, state_letters, metadat
 
 def execute_from_command_line(biomolecule, msa_file, the_command=None, seqid=None, lambda_h=None, lambda_J=None, max_iterations=None,
                               epsilon=None, order=None, output_dir=None, verbose=False, device=0, query_file=None, wildtype_file=None,
-                              num_sequences=None, seed=None):
+                              num_sequences=None, seed=None, apc=False, refseq_file=None):
     if verbose:
         logging.basicConfig(level=logging.INFO, format='%(levelname)s %(name)s: %(message)s')
     if the_command not in ARDCA_SUBCOMMANDS:
@@ -116,6 +116,28 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, seqid=Non
         out = path('samples', '.fa')
         write_samples(out, seqs, logp)
         return out
+    if the_command == 'compute_fn':
+        # ARDCA_fn[_apc]_<base>.txt in the score-file format of plmdca compute_fn; --wildtype_file: the sequence whose double
+        # mutants are scored (default: the first record of msa_file); --refseq_file: pairs on the reference's positions
+        seqbackmapper = None
+        if refseq_file:
+            from .sequence_backmapper.sequence_backmapper import SequenceBackmapper
+            seqbackmapper = SequenceBackmapper(msa_file=msa_file, refseq_file=refseq_file, biomolecule=instance.biomolecule)
+        if apc:
+            ranked = instance.compute_sorted_FN_APC(wildtype=wildtype_file, seqbackmapper=seqbackmapper)
+            score_type = 'ARDCA epistatic score (Frobenius norm), average product corrected (APC)'
+        else:
+            ranked = instance.compute_sorted_FN(wildtype=wildtype_file, seqbackmapper=seqbackmapper)
+            score_type = 'ARDCA epistatic score (Frobenius norm), non-APC (not average product corrected)'
+        out = path('fn_apc' if apc else 'fn', '.txt')
+        dca_utilities.write_sorted_dca_scores(out, ranked, metadata=meta, score_type=score_type)
+        return out
+    if the_command == 'compute_epistasis':
+        # float64[L(L-1)/2, q, q] each, all file-site pairs i < j in pair order, first state index at site i
+        eps_file, effects_file = path('epistasis', '.npy'), path('double_mutant_effects', '.npy')
+        np.save(eps_file, instance.compute_epistasis(wildtype=wildtype_file))
+        np.save(effects_file, instance.compute_double_mutant_effects(wildtype=wildtype_file))
+        return eps_file, effects_file
     if not wildtype_file:
         raise ardca.ArDCAException('compute_mutation_effects needs --wildtype_file')
     w = _potts.wildtype_codes(wildtype_file, bio, instance.sequences_len, 0, ardca.ArDCAException)
@@ -145,6 +167,12 @@ def build_parser():
             p.add_argument('--query_file', required=True, help='FASTA file of aligned sequences to compare with the alignment; no fit is run')
         if name == 'compute_mutation_effects':
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence')
+        if name in ('compute_fn', 'compute_epistasis'):
+            p.add_argument('--wildtype_file', help='FASTA file with one aligned sequence whose double mutants are scored '
+                                                   '(default: the first record of msa_file)')
+        if name == 'compute_fn':
+            p.add_argument('--apc', action='store_true', help='average product correction of the scores')
+            p.add_argument('--refseq_file', help='FASTA file of the reference sequence the site pairs are mapped onto')
         if name == 'sample_sequences':
             p.add_argument('--num_sequences', type=int, required=True, help='number of independent sequences to draw')
             p.add_argument('--seed', type=int, default=0, help='seed of the counter-based generator')
@@ -162,7 +190,8 @@ def run_ardca(argv=None):
         lambda_h=args.get('lambda_h'), lambda_J=args.get('lambda_J'), max_iterations=args.get('max_iterations'),
         epsilon=args.get('epsilon'), order=args.get('order'), output_dir=args.get('output_dir'), verbose=args.get('verbose'),
         device=args.get('device'), query_file=args.get('query_file'), wildtype_file=args.get('wildtype_file'),
-        num_sequences=args.get('num_sequences'), seed=args.get('seed'))
+        num_sequences=args.get('num_sequences'), seed=args.get('seed'), apc=bool(args.get('apc')),
+        refseq_file=args.get('refseq_file'))
 
 
 if __name__ == '__main__':

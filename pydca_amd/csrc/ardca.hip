@@ -737,6 +737,27 @@ struct ArEngine {
         return DCA_OK;
     }
 
+    // cond_l(b) of ONE sequence (host codes, model order) into dCond (device, L*q): the logits kernel with n = 1, so the values
+    // are bit for bit the cond of log_probabilities (the wild-type pass of ar_epistasis.hip)
+    int conditionals_of(const uint8_t* row, double* dCond)
+    {
+        const int S = kASeqBlock;
+        uint8_t *dRow = nullptr, *dQ = nullptr;
+        double* dS_ = nullptr;
+        hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRow), (size_t)L, false);
+        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dQ), (size_t)L * S, false);
+        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dS_), (size_t)L * S * sizeof(double), false);
+        if (e == hipSuccess) e = hipMemcpyAsync(dRow, row, (size_t)L, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(ar_sites_kernel, dim3(blocks_of((size_t)L * S)), dim3(256), 0, ctx->stream, dRow, (size_t)L, 1, L, S, dQ);
+            e = launch_logits(ctx, dx, L, q, dQ, 1, S, nullptr, dS_, nullptr, dCond);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        dca_dev_free(dRow); dca_dev_free(dQ); dca_dev_free(dS_);
+        if (e != hipSuccess) return fail(e, "conditionals");
+        return DCA_OK;
+    }
+
     int sample(int n, uint64_t seed, uint64_t first_chain, uint8_t* out)
     {
         const size_t lds = (size_t)64 * ceil_div(L, kSSlices);
@@ -766,6 +787,13 @@ struct ArEngine {
 };
 
 ArEngine* dca_make_ar_engine(dca_ctx* ctx) { return new ArEngine(ctx); }
+bool dca_ar_engine_model(ArEngine* e, const double** dx, int* L, int* q)
+{
+    if (!e || !e->dx) return false;
+    *dx = e->dx; *L = e->L; *q = e->q;
+    return true;
+}
+int dca_ar_engine_conditionals(ArEngine* e, const uint8_t* row, double* dCond) { return e->conditionals_of(row, dCond); }
 void dca_free_ar_engine(ArEngine* e) { delete e; }
 void dca_ar_engine_weights_changed(ArEngine* e) { if (e) e->configured = false; }
 

@@ -289,6 +289,10 @@ int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, c
 ArEngine* dca_make_ar_engine(dca_ctx* ctx);
 void dca_free_ar_engine(ArEngine*);
 void dca_ar_engine_weights_changed(ArEngine*);
+// for ar_epistasis.hip: the engine's device x and its (L, q) (false before the first configure), and cond_l(b) of one host row
+// (L codes, model order) into dCond (device, L*q) through the logits kernel
+bool dca_ar_engine_model(ArEngine*, const double** dx, int* L, int* q);
+int dca_ar_engine_conditionals(ArEngine*, const uint8_t* row, double* dCond);
 
 // ---- mf engine
 struct MfEngine;

@@ -234,19 +234,9 @@ class PlmDCA(_potts.PottsModel, _compare.SequenceComparison):
     def get_mapped_site_pairs_dca_scores(self, sorted_dca_scores, seqbackmapper):
         """Keeps the site pairs whose two MSA columns map to the reference sequence and renames
         them to reference positions (meanfield_dca.py:755-790, plmdca.py:527-562)."""
-        mapping_dict = seqbackmapper.map_to_reference_sequence()
-        self.__refseq_mapping_dict = mapping_dict
-        sorted_scores_mapped = list()
-        for pair, score in sorted_dca_scores:
-            try:
-                mapped_pair = mapping_dict[pair[0]], mapping_dict[pair[1]]
-            except KeyError:
-                pass
-            else:
-                sorted_scores_mapped.append((mapped_pair, score))
-        sorted_scores_mapped = sorted(sorted_scores_mapped, key=lambda k: k[1], reverse=True)
+        sorted_scores_mapped, self.__refseq_mapping_dict = _ranking.mapped_site_pairs(sorted_dca_scores, seqbackmapper)
         logger.info('\n\tSite pairs mapped onto the reference sequence: {}'.format(len(sorted_scores_mapped)))
-        return tuple(sorted_scores_mapped)
+        return sorted_scores_mapped
 
     def _maybe_mapped(self, ranked, seqbackmapper):
         return ranked if seqbackmapper is None else self.get_mapped_site_pairs_dca_scores(ranked, seqbackmapper)
