@@ -367,60 +367,6 @@ def test_lbfgs_float32_default_path_scores_close(L_, oracle_plm, oracle_mf):
     ctx.close()
 
 
-@pytest.mark.parametrize("env", [{"DCA_CHOLINV_LEAF16": "0"}, {"DCA_CHOLINV_LEAF16": "0", "DCA_CHOLINV_LEAF_MFMA": "0"},
-                                 {"DCA_CHOLINV_LEAF16": "0", "DCA_CHOLINV_LEAF_MFMA": "0", "DCA_CHOLINV_LEAF128": "0"},
-                                 {"DCA_CHOLINV_LEAF16": "0", "DCA_CHOLINV_LEAF128": "0"}, {"DCA_CHOLINV_LEAF16": "64"}, {"DCA_CHOLINV_LEAF16": "256"}])
-def test_spd_inverse_alternative_leaves(env):
-    """The recursion's other leaf kernels (the four-column MFMA leaf of rounds 2 - 5, the register-block leaf, 64-only recursion, the
-    16-column-step leaf up to 64 / 256 columns instead of 128; selected by environment variables that the library reads once,
-    hence a subprocess) give the same inverse to 1e-11."""
-    import subprocess
-    code = (
-        "import sys, numpy as np; sys.path.insert(0, %r)\n"
-        "from pydca_amd import _lib\n"
-        "worst = 0.0\n"
-        "for n in (64, 128, 192, 320, 500):\n"
-        "    rng = np.random.default_rng(n); B = rng.standard_normal((n, n + 8)); A = B @ B.T / n + 0.5 * np.diag(rng.random(n) + 0.5)\n"
-        "    ctx = _lib.Context(0, _lib.DCA_F64); inv = ctx.spd_inverse(A); ctx.close(); ref = np.linalg.inv(A)\n"
-        "    worst = max(worst, float(np.linalg.norm(inv - ref) / np.linalg.norm(ref))); assert np.array_equal(inv, inv.T)\n"
-        "print(worst)\n" % ROOT)
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
-    assert p.returncode == 0, p.stderr[-2000:]
-    assert float(p.stdout.strip().splitlines()[-1]) < 1e-11
-
-
-@pytest.mark.parametrize("env", [{"DCA_CHOLINV_PANEL": "128"}, {"DCA_CHOLINV_PANEL": "128", "DCA_CHOLINV_OVERLAP": "0"},
-                                 {"DCA_CHOLINV_PANEL": "256", "DCA_CHOLINV_SIDE_CAP": "7"}, {"DCA_CHOLINV_PANEL": "128", "DCA_CHOLINV_BULK_KW": "2"},
-                                 {"DCA_CHOLINV_PANEL": "128", "DCA_CHOLINV_STREAMK": "1", "DCA_CHOLINV_TRSM_SPLIT": "1"},
-                                 {"DCA_CHOLINV_PANEL": "256", "DCA_CHOLINV_STREAMK": "1", "DCA_CHOLINV_SIDE_CAP": "12"}])
-def test_spd_inverse_blocked_form_at_small_sizes(env):
-    """Round 5: the look-ahead factorisation + separate triangular-inverse tree (cholinv_blocked) is what runs for n >= 5000;
-    forced here onto small matrices (panels of 128 / 256 columns, split-k from 128 columns on, one stream, tiny launch caps,
-    the eight-wave bulk kernel, and the two opt-in forms that were measured slower and stay off: the stream-K bulk products
-    with their ordered fix-up, the panel's lower rows on the bulk stream) so that every branch of it -- ragged last panel,
-    split-k with its reduction, band splitting, the event chain -- is compared with LAPACK."""
-    import subprocess
-    code = (
-        "import sys, numpy as np; sys.path.insert(0, %r)\n"
-        "from pydca_amd import _lib\n"
-        "worst = 0.0\n"
-        "for n in (320, 448, 500, 1000, 1472, 2100):\n"
-        "    rng = np.random.default_rng(n); B = rng.standard_normal((n, n + 8)); A = B @ B.T / n + 0.5 * np.diag(rng.random(n) + 0.5)\n"
-        "    ctx = _lib.Context(0, _lib.DCA_F64); inv = ctx.spd_inverse(A); ctx.close(); ref = np.linalg.inv(A)\n"
-        "    worst = max(worst, float(np.linalg.norm(inv - ref) / np.linalg.norm(ref))); assert np.array_equal(inv, inv.T)\n"
-        "A[7, 7] = -1.0\n"
-        "ctx = _lib.Context(0, _lib.DCA_F64)\n"
-        "try:\n"
-        "    ctx.spd_inverse(A); raise SystemExit('an indefinite matrix was accepted')\n"
-        "except _lib.DcaBackendError as e:\n"
-        "    assert e.code == _lib.DCA_ERR_NOT_SPD, e\n"
-        "print(worst)\n" % ROOT)
-    full = dict(os.environ, DCA_SWEEP="0", DCA_CHOLINV_BLOCKED_MIN="0", DCA_CHOLINV_SPLITK_MIN="128", **env)
-    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=full)
-    assert p.returncode == 0, p.stderr[-2000:]
-    assert float(p.stdout.strip().splitlines()[-1]) < 1e-11
-
-
 def test_spd_inverse_default_form_at_n_5056(L_):
     """n = 5056: above the size from which dca_spd_inverse_device takes the block sweep by itself (default settings)."""
     n = 5056
@@ -437,18 +383,17 @@ def test_spd_inverse_default_form_at_n_5056(L_):
 SWEEP_SMALL = {"DCA_SWEEP_MIN": "256", "DCA_SWEEP_PANEL": "128"}
 
 
-@pytest.mark.parametrize("env", [{}, {"DCA_SWEEP_CAP": "8", "DCA_SWEEP_PRIO_CAP": "8"}, {"DCA_SWEEP_PER_CU": "1", "DCA_SWEEP_STAGES": "4"},
-                                 {"DCA_SWEEP_PER_CU": "1", "DCA_SWEEP_STAGES": "3", "DCA_SWEEP_CAP": "16"}, {"DCA_SWEEP_PANEL": "256"},
-                                 {"DCA_SWEEP_MASK": "240"}, {"DCA_SWEEP": "0", "DCA_CHOLINV_BLOCKED_MIN": "5000"},
-                                 {"DCA_SWEEP_FACTOR_MAX_N": "0"}, {"DCA_SWEEP_FACTOR_MAX_N": "0", "DCA_SWEEP_COPY": "0"}, {"DCA_SWEEP_COPY": "1"},
-                                 {"DCA_SWEEP_RESERVE": "4", "DCA_SWEEP_RESERVE_MAX_N": "100000"}])
+@pytest.mark.parametrize("env", [{}, {"DCA_SWEEP_CAP": "8", "DCA_SWEEP_PRIO_CAP": "8"}, {"DCA_SWEEP_PANEL": "256"}, {"DCA_SWEEP": "0"},
+                                 {"DCA_SWEEP_FACTOR_MAX_N": "0"}, {"DCA_SWEEP_PANEL": "256", "DCA_SWEEP_FACTOR_MAX_N": "0"},
+                                 {"DCA_SWEEP_CAP": "8", "DCA_SWEEP_PRIO_CAP": "8", "DCA_SWEEP_FACTOR_MAX_N": "0"},
+                                 {"DCA_SWEEP_PANEL": "256", "DCA_SWEEP_CAP": "8", "DCA_SWEEP_PRIO_CAP": "8"}])
 def test_spd_inverse_block_sweep_at_small_sizes(env):
-    """Round 6: the symmetric block sweep (cholinv_sweep) is what runs from n = 2560 on; forced here onto small matrices (panels of 128 /
+    """The symmetric block sweep (cholinv_sweep) is what runs from n = 2560 on; forced here onto small matrices (panels of 128 /
     256 columns -- ragged last panel, last tile row of 64, a 64-column last panel --, tiny workgroup caps so that the tile
-    hand-out wraps and steals across the XCD chunks, one workgroup per CU with three / four operand stages, CU-masked streams)
-    and compared with LAPACK; an indefinite matrix must come back as DCA_ERR_NOT_SPD with the pivot of the Cholesky
-    factorisation.  {DCA_SWEEP: 0} is the three-phase form on the same matrices; the sets after it: the next pivot block through
-    P instead of from X (what n >= 4500 takes), with / without the copy kernel, and CUs reserved for the chain by the update kernel."""
+    hand-out wraps and steals across the XCD chunks) and compared with LAPACK; an indefinite matrix must come back as
+    DCA_ERR_NOT_SPD with the pivot of the Cholesky factorisation.  {DCA_SWEEP: 0} is the fused recursion on the same matrices;
+    {DCA_SWEEP_FACTOR_MAX_N: 0}: the next pivot block through P instead of from X, after a copy (what n >= 4500 takes).  The last
+    three sets cross the two forms with the wide panels and the tiny caps: wide panels in the P form are what n >= 7000 takes."""
     import subprocess
     code = (
         "import sys, numpy as np; sys.path.insert(0, %r)\n"
@@ -619,10 +564,11 @@ def test_mf_singular_matrix_is_an_error(L_):
     ctx.close()
 
 
-@pytest.mark.parametrize("n", [1, 64, 100, 128, 129, 192, 200, 256, 320, 500, 1000])
+@pytest.mark.parametrize("n", [1, 64, 100, 128, 129, 192, 200, 256, 320, 448, 500, 1000, 1088, 1472, 2100, 2496])
 def test_spd_inverse_f64_mfma(L_, n):
     """Blocked Cholesky inverse on v_mfma_f64_16x16x4_f64 vs LAPACK; asymmetric-looking
-    test matrices (random SPD, no special structure)."""
+    test matrices (random SPD, no special structure).  Default settings: below n = 2560 this is the fused recursion, at
+    n = 2496 with its top-level product on the side stream."""
     rng = np.random.default_rng(n)
     B = rng.standard_normal((n, n + 8))
     A = B @ B.T / n + 0.5 * np.diag(rng.random(n) + 0.5)
@@ -631,6 +577,21 @@ def test_spd_inverse_f64_mfma(L_, n):
     ref = np.linalg.inv(A)
     assert rel_err(inv, ref) < 1e-11
     assert np.array_equal(inv, inv.T)
+    ctx.close()
+
+
+def test_spd_inverse_indefinite_matrix_is_reported(L_):
+    """Default settings, n = 2100 (the fused recursion): a matrix that is not positive definite comes back as DCA_ERR_NOT_SPD
+    with the first non-positive pivot of the Cholesky factorisation."""
+    n = 2100
+    rng = np.random.default_rng(n)
+    B = rng.standard_normal((n, n + 8))
+    A = B @ B.T / n + 0.5 * np.diag(rng.random(n) + 0.5)
+    A[7, 7] = -1.0
+    ctx = L_.Context(0, L_.DCA_F64)
+    with pytest.raises(L_.DcaBackendError) as ei:
+        ctx.spd_inverse(A)
+    assert ei.value.code == L_.DCA_ERR_NOT_SPD and "(pivot 8)" in str(ei.value), ei.value
     ctx.close()
 
 

@@ -43,10 +43,7 @@ int main()
     };
     timeit("leaf16<64>", [&](double* m) { hipLaunchKernelGGL(cholinv_leaf16_small_kernel<64>, dim3(1), dim3(512), leaf16_lds_bytes<64>(), st, m, n, 0, info); });
     timeit("leaf16<128>", [&](double* m) { hipLaunchKernelGGL(cholinv_leaf16_small_kernel<128>, dim3(1), dim3(512), leaf16_lds_bytes<128>(), st, m, n, 0, info); });
-    timeit("leaf16<192>", [&](double* m) { hipLaunchKernelGGL(cholinv_leaf16_kernel<192>, dim3(1), dim3(512), leaf16_lds_bytes<192>(), st, m, n, 0, info); });
-    timeit("leaf16<256>", [&](double* m) { hipLaunchKernelGGL(cholinv_leaf16_kernel<256>, dim3(1), dim3(512), leaf16_lds_bytes<256>(), st, m, n, 0, info); });
     for (int r = 0; r < reps; ++r) hipMemcpy(d + (size_t)r * n * n, h.data(), sizeof(double) * n * n, hipMemcpyHostToDevice);
-    timeit("old mfma leaf<128>", [&](double* m) { hipLaunchKernelGGL(cholinv_leaf_mfma_kernel<128>, dim3(1), dim3(DCA_LEAF_WAVES128 * 64), 0, st, m, n, 0, info); });
     if (DCA_LEAF16_ABLATE == 0) {
         double* out; hipMalloc(&out, 2048);
         const int iters = 2000;

@@ -31,7 +31,7 @@ int main(int argc, char** argv)
     auto run_leaves = [&]() {
         CHECK(hipMemcpy(dA, h.data(), h.size() * 8, hipMemcpyHostToDevice));
         CHECK(hipEventRecord(a0, sa));
-        for (int r = 0; r < leaves; ++r) hipLaunchKernelGGL(cholinv_leaf_mfma_kernel<128>, dim3(1), dim3(512), 0, sa, dA, ld, 0, dInfo);
+        for (int r = 0; r < leaves; ++r) hipLaunchKernelGGL(cholinv_leaf16_small_kernel<128>, dim3(1), dim3(512), leaf16_lds_bytes<128>(), sa, dA, ld, 0, dInfo);
         CHECK(hipEventRecord(a1, sa));
     };
     run_leaves(); CHECK(hipDeviceSynchronize());
@@ -56,7 +56,7 @@ int main(int argc, char** argv)
             for (int l = 0; l < launches; ++l) hipLaunchKernelGGL(gemm_nt_f64_dma_kernel<4>, dim3(gx, gy), dim3(256), (size_t)4 * 128 * 16 * 8, sb, g);
             CHECK(hipEventRecord(b1, sb));
             CHECK(hipEventRecord(a0, sa));
-            for (int r = 0; r < leaves; ++r) hipLaunchKernelGGL(cholinv_leaf_mfma_kernel<128>, dim3(1), dim3(512), 0, sa, dA, ld, 0, dInfo);
+            for (int r = 0; r < leaves; ++r) hipLaunchKernelGGL(cholinv_leaf16_small_kernel<128>, dim3(1), dim3(512), leaf16_lds_bytes<128>(), sa, dA, ld, 0, dInfo);
             CHECK(hipEventRecord(a1, sa));
             CHECK(hipDeviceSynchronize());
             float msa, msb2; CHECK(hipEventElapsedTime(&msa, a0, a1)); CHECK(hipEventElapsedTime(&msb2, b0, b1));

@@ -1,5 +1,5 @@
-// Round 6: the block sweep's update kernel alone (one REST launch of a middle panel, one PRIO launch) by operand stages and
-// workgroup cap.   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-result -I../../include [-DDCA_SWEEP_ABLATE=k] -o sweep_bench sweep_bench.hip
+// Round 6: the block sweep's update kernel alone (one REST launch of a middle panel, one PRIO launch) by workgroup cap
+// (the one-workgroup-per-CU forms with three / four operand stages it once compared are gone from cholinv.hip).   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-result -I../../include [-DDCA_SWEEP_ABLATE=k] -o sweep_bench sweep_bench.hip
 //   ./sweep_bench n w
 #include <unistd.h>
 #include <cmath>
@@ -41,24 +41,21 @@ int main(int argc, char** argv)
         g.nTiles = mode == 0 ? 8 * bands * bands + 2 * bands : g.prN * nR + g.dgN * (g.dgN + 1) / 2;
         const double tiles = mode == 0 ? nR * (nR + 1) / 2.0 - g.dgN * (g.dgN + 1) / 2.0 : g.nTiles;
         const double flop = tiles * 2.0 * 128 * 128 * w;
-        for (int perCu = 1; perCu <= 2; ++perCu)
-        for (int stages = 2; stages <= (perCu == 2 ? 2 : 4); stages += 2)
-            for (int cap : {248, 256, 496, 512, 100000}) {
-                if (perCu == 1 && cap > 256 && cap < 100000) continue;
-                float best = 1e9;
-                const int G = std::min(cap, (g.nTiles + 7) / 8 * 8);
-                for (int rep = 0; rep < 4; ++rep) {
-                    hipMemsetAsync(ctr, 0, 64, st);
-                    hipEventRecord(e0, st);
-                    sweep_update_launch(st, G, stages, perCu, g);
-                    hipEventRecord(e1, st);
-                    hipEventSynchronize(e1);
-                    float ms; hipEventElapsedTime(&ms, e0, e1);
-                    if (ms < best) best = ms;
-                }
-                printf("n=%d w=%d %s tiles=%.0f perCu=%d stages=%d G=%5d  %8.1f us  %5.1f TF  (%.1f us per round)\n", n, w, mode == 0 ? "REST" : "PRIO", tiles, perCu, stages, G,
-                       best * 1e3, flop / (best * 1e-3) / 1e12, best * 1e3 / ceil(tiles / G));
+        for (int cap : {248, 256, 496, 512, 100000}) {
+            float best = 1e9;
+            const int G = std::min(cap, (g.nTiles + 7) / 8 * 8);
+            for (int rep = 0; rep < 4; ++rep) {
+                hipMemsetAsync(ctr, 0, 64, st);
+                hipEventRecord(e0, st);
+                sweep_update_launch(st, G, g);
+                hipEventRecord(e1, st);
+                hipEventSynchronize(e1);
+                float ms; hipEventElapsedTime(&ms, e0, e1);
+                if (ms < best) best = ms;
             }
+            printf("n=%d w=%d %s tiles=%.0f G=%5d  %8.1f us  %5.1f TF  (%.1f us per round)\n", n, w, mode == 0 ? "REST" : "PRIO", tiles, G,
+                   best * 1e3, flop / (best * 1e-3) / 1e12, best * 1e3 / ceil(tiles / G));
+        }
     }
     if (hipGetLastError() != hipSuccess) printf("launch error\n");
     return 0;

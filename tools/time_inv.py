@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time the SPD inverse (csrc/cholinv.hip) alone on a random SPD matrix: device time of the whole inverse, of the
-recursion / factorisation part and of the final X^T X, from the library's own HIP events.  Environment knobs of
-cholinv.hip (DCA_CHOLINV_*) are read once per process, so one process per variant.
+recursion / sweep part and of the final X^T X (fused recursion only: n < 2560), from the library's own HIP events.  The
+environment knobs of cholinv.hip (DCA_SWEEP*, DCA_CHOLINV_TRACE) are read once per process, so one process per variant.
 
     python tools/time_inv.py --n 10048 --reps 4 [--check]"""
 import argparse
