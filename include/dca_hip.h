@@ -596,8 +596,8 @@ int dca_ar_epistasis(dca_ctx* ctx, const uint8_t* wildtype, double* eps_out /* p
  * dca_plm_scores -- gap row and column dropped, the (q-1) x (q-1) block double-centred, Frobenius norm, APC-corrected with
  * apc != 0 -- in pair order over the MODEL's sites (FN and APC do not change under transposition of a block or relabelling of
  * the sites, so a caller with another site order relabels the pairs).  The score vector stays on the device for
- * dca_scores_order, as after dca_plm_scores; like it, any L >= 2 is served.  Errors as dca_ar_epistasis (scores_out NULL:
- * DCA_ERR_ARG); q > 21: DCA_ERR_ARG (the scoring kernel's limit). */
+ * dca_scores_order, as after dca_plm_scores; like it, any L >= 2 and every q of dca_set_msa is served.  Errors as
+ * dca_ar_epistasis (scores_out NULL: DCA_ERR_ARG). */
 int dca_ar_epistatic_scores(dca_ctx* ctx, const uint8_t* wildtype, int apc, double* scores_out /* pairs */);
 int dca_ar_release(dca_ctx* ctx);
 

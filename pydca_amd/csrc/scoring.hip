@@ -13,10 +13,14 @@ template <typename S>
 __global__ __launch_bounds__(64)
 void fn_kernel(const S* __restrict__ src, int kind, int L, int q, int ld, double* __restrict__ fn)
 {
-    __shared__ double blk[20 * 20];
-    __shared__ double rowm[20], colm[20];
-    __shared__ double tot;
+    // dynamic LDS, (q-1)^2 + 2 (q-1) + 1 doubles: the block, its row and column means, its mean -- sized by the alphabet, so
+    // that every q dca_set_msa accepts (up to 32) is served at the occupancy of its own block size
+    extern __shared__ __attribute__((aligned(16))) unsigned char dca_smem[];
     const int qm = q - 1;
+    double* blk = reinterpret_cast<double*>(dca_smem);
+    double* rowm = blk + qm * qm;
+    double* colm = rowm + qm;
+    double& tot = colm[qm];
     // decode (i,j) from blockIdx: rows of the upper triangle
     const size_t p = blockIdx.x;
     int i = 0;
@@ -247,13 +251,14 @@ void pair_blocks_kernel(const S* __restrict__ src, int kind, const int* __restri
 
 int dca_fn_scores(dca_ctx* ctx, const void* src, int src_kind, int dtype, int L, int q, int ld, int apc, double* dOut)
 {
-    if (q - 1 > 20) { dca_set_error("q too large for the scoring kernel"); return DCA_ERR_ARG; }
+    if (q > 32) { dca_set_error("q too large for the scoring kernel"); return DCA_ERR_ARG; }
     const size_t npairs = (size_t)L * (L - 1) / 2;
+    const size_t lds = (size_t)((q - 1) * (q - 1) + 2 * (q - 1) + 1) * sizeof(double);
     ScopedKernelClock kc(ctx, "scores");
     if (dtype == DCA_F32)
-        hipLaunchKernelGGL(fn_kernel<float>, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, static_cast<const float*>(src), src_kind, L, q, ld, dOut);
+        hipLaunchKernelGGL(fn_kernel<float>, dim3((unsigned)npairs), dim3(64), lds, ctx->stream, static_cast<const float*>(src), src_kind, L, q, ld, dOut);
     else
-        hipLaunchKernelGGL(fn_kernel<double>, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, static_cast<const double*>(src), src_kind, L, q, ld, dOut);
+        hipLaunchKernelGGL(fn_kernel<double>, dim3((unsigned)npairs), dim3(64), lds, ctx->stream, static_cast<const double*>(src), src_kind, L, q, ld, dOut);
     if (apc) {
         double* dAv = nullptr;
         HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dAv), (size_t)(L + 1) * sizeof(double)));
