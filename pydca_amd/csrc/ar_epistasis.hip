@@ -22,7 +22,7 @@
 // product.  Instead of one logarithm per (pair, state pair, m) the kernel multiplies the r_m and splits the exponent of the
 // running product off into an integer every 4th step (so 4 consecutive r_m may span 2^+-1000 together before anything
 // overflows); one logarithm at the end: eps = T - (log(mantissa product) + exponent sum * ln 2).  No atomics, no scratch.
-#include "dca_internal.h"
+#include "site_conditionals.h"
 
 #include <algorithm>
 #include <cmath>
@@ -218,8 +218,6 @@ void epi_main_kernel(const double* __restrict__ x, const uint8_t* __restrict__ w
     }
 }
 
-inline int qm_of(int q) { return q <= 8 ? 8 : q <= 24 ? 24 : 32; }
-
 template <int QM>
 hipError_t launch_main(dca_ctx* ctx, const double* x, const uint8_t* w, const double* V, const int2* tiles, int ntiles,
                        int L, int q, double* eps)
@@ -279,11 +277,9 @@ int epistasis_device(dca_ctx* ctx, const double* dx, int L, int q, const uint8_t
         hipLaunchKernelGGL(epi_single_kernel, dim3(lqBlocks), dim3(256), 0, ctx->stream, B.dCond, B.dTerm, B.dW, L, q, B.dD);
         e = hipGetLastError();
         if (e == hipSuccess) {
-            switch (qm_of(q)) {
-            case 8: e = launch_main<8>(ctx, dx, B.dW, B.dV, B.dTiles, (int)tiles.size(), L, q, B.dVec + Lq); break;
-            case 24: e = launch_main<24>(ctx, dx, B.dW, B.dV, B.dTiles, (int)tiles.size(), L, q, B.dVec + Lq); break;
-            default: e = launch_main<32>(ctx, dx, B.dW, B.dV, B.dTiles, (int)tiles.size(), L, q, B.dVec + Lq); break;
-            }
+            e = with_qm(q, [&](auto qm) {
+                return launch_main<decltype(qm)::value>(ctx, dx, B.dW, B.dV, B.dTiles, (int)tiles.size(), L, q, B.dVec + Lq);
+            });
         }
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // the host copies of the wild type and the tiles are read until here

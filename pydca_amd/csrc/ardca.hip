@@ -5,9 +5,10 @@
 //
 // Objective (include/dca_hip.h): f(x) = -sum_n W_n sum_l log P(s_nl | s_n,<l) + lambda_h sum h^2 + lambda_J sum J^2, W_n = w_n / sum w.
 // One evaluation runs the sequences through in passes (bounded device scratch); per pass:
-//   ar_sites_kernel   site-major copy of the pass's codes, QT[l * NpS + n]
-//   ar_logits_kernel  ("ar_logits") u_l, log-softmax, the site values log P(s_nl | .) and the residual R_nl(b) = W_n (P_nl(b) - [s_nl = b])
-//   ar_finish_kernel  log P(s_n) = sum_l site (ascending l); ar_wsum_kernel: F_pass = sum_n W_n log P(s_n) (fixed tree)
+//   dca_rows_to_sites site-major copy of the pass's codes, QT[l * NpS + n]
+//   ar_logits_kernel  ("ar_logits") u_l, log-softmax, the site values log P(s_nl | .) and the residual R_nl(b) = W_n (P_nl(b) - [s_nl = b]):
+//                     site_conditionals.h's body (which states the summation order: h_l first, then k ascending) with the policy below
+//   dca_site_finish   log P(s_n) = sum_l site (ascending l); ar_wsum_kernel: F_pass = sum_n W_n log P(s_n) (fixed tree)
 //   ar_field_kernel / ar_grad_kernel ("ar_grad")  G_h[l][b] = sum_n R_nl(b), G_kl[a][b] = sum_n [s_nk = a] R_nl(b), ascending n
 // and the pass results are added in ascending pass order; then g += 2 lambda x and fx = -(sum of F_pass) + lambda_h |h|^2 + lambda_J |J|^2.
 // No atomics anywhere: every element is summed in an order fixed by (N, L, q, pass size), so repeated calls give the same bits.
@@ -18,7 +19,7 @@
 //
 // Sampler ("ar_sample"): chain c visits sites 0 .. L-1 once and draws s_l with sample.hip's rule at beta = 1 from
 // U = Philox(seed; chain, 0, site, 3).  DESIGN.md section 16 has the geometry and the measured numbers.
-#include "dca_internal.h"
+#include "site_conditionals.h"
 #include "more_thuente.h"
 #include "vec_kernels.h"
 
@@ -29,11 +30,6 @@
 
 namespace {
 
-constexpr int kAThreads = 256;                     // logits: 4 waves
-constexpr int kAPerLane = 2;                       // queries per lane
-constexpr int kASeqBlock = kAThreads * kAPerLane;  // queries per logits workgroup
-constexpr int kAMaxCJ = 16;                        // blocks per chunk at most
-constexpr size_t kAChunkBudget = 16 * 1024;        // LDS per J chunk buffer (two of them)
 constexpr size_t kAPassBudget = 1ull << 30;        // device scratch of one pass
 constexpr int kGTile = 64;                         // sequences per staged tile of the coupling gradient
 constexpr size_t kGBlockBudget = 56 * 1024;        // LDS of the gradient blocks of one workgroup
@@ -42,171 +38,41 @@ constexpr int kSSlices = 4;                        // sampler: lanes per chain (
 constexpr int kSChainsPerWave = 64 / kSSlices;
 constexpr int kDotBlocks = 256;
 
-// site-major copy of n rows (row stride ld): QT[s * NpS + k], zero past n
-__global__ void ar_sites_kernel(const uint8_t* __restrict__ rows, size_t ld, int n, int L, int NpS, uint8_t* __restrict__ QT)
-{
-    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (t >= (size_t)L * NpS) return;
-    const int s = (int)(t / NpS), k = (int)(t % NpS);
-    QT[t] = k < n ? rows[(size_t)k * ld + s] : 0;
-}
-
+// site l of the autoregressive model: the earlier sites k < l; the block of the pair (k, l) holds J_kl(a, b) as the term needs
+// it, so nothing is transposed.  With R (L x NpS x q) and W (the pass's normalised weights) the epilogue writes the residual
+// R_nl(b) = W_n (P_nl(b) - [s_nl = b]).
 template <int QM>
-constexpr int chunk_blocks() { return (int)(kAChunkBudget / (QM * QM * sizeof(double))) < kAMaxCJ ? (int)(kAChunkBudget / (QM * QM * sizeof(double))) : kAMaxCJ; }
+struct ArPolicy {
+    const double* x;
+    int L, q, l, NpS;
+    const double* W;
+    double* R;
+    __device__ __forceinline__ int neighbours() const { return l; }
+    __device__ __forceinline__ bool skip(int) const { return false; }
+    __device__ __forceinline__ double load(int k, int a, int b) const { return x[(size_t)L * q + pair_index(L, k, l) * (size_t)(q * q) + (a * q + b)]; }
+    __device__ __forceinline__ int lds_pos(int, int a, int b) const { return a * QM + b; }
+    __device__ __forceinline__ double field(int b) const { return x[(size_t)l * q + b]; }
+    __device__ __forceinline__ void epilogue(int n, const double* u, double m, double lz, int sl) const
+    {
+        if (!R) return;
+        const double w = W[n];
+        double* r = R + ((size_t)l * NpS + n) * q;
+#pragma unroll
+        for (int b = 0; b < QM; ++b)
+            if (b < q) r[b] = w * (exp((u[b] - m) - lz) - (b == sl ? 1.0 : 0.0));
+    }
+};
 
-// grid (ceil(nq / 512), L): blockIdx.y = L - 1 - l, so the sites with the most terms are dispatched first.  LDS: two J chunk
-// buffers (CJ blocks of q x QM doubles: the block of the pair (k, l) as stored, rows padded to QM), then two code buffers
-// (CJ x 512 bytes).  QT: site-major codes, NpS a multiple of 512 and >= gridDim.x * 512.  site: L x NpS.  With W (the pass's
-// normalised weights) R (L x NpS x q) receives W_n (P_nl(b) - [s_nl = b]); with cond (nq x L x q, host layout) the conditionals.
+// grid (ceil(nq / 512), L): blockIdx.y = L - 1 - l, so the sites with the most terms are dispatched first.  LDS
+// site_lds<double, QM>(q).  QT, site and cond as site_conditional_body takes them; R and W as the policy does.
 template <int QM>
-__global__ __launch_bounds__(kAThreads)
+__global__ __launch_bounds__(kSiteThreads)
 void ar_logits_kernel(const double* __restrict__ x, int L, int q, const uint8_t* __restrict__ QT, int nq, int NpS,
                       const double* __restrict__ W, double* __restrict__ site, double* __restrict__ R, double* __restrict__ cond)
 {
-    constexpr int CJ = chunk_blocks<QM>();
-    constexpr int KPB = (QM * QM + kAThreads - 1) / kAThreads;
-    constexpr int codeBytes = CJ * kASeqBlock;
-    constexpr int CPT = (codeBytes / 16 + kAThreads - 1) / kAThreads;   // 16-byte code pieces per thread
-    static_assert(CPT <= 2, "at most two code pieces per thread");
-    extern __shared__ __attribute__((aligned(16))) unsigned char ar_smem[];
-    const int blk = q * QM;
-    const int bufVals = CJ * blk;
-    double* bufJ = reinterpret_cast<double*>(ar_smem);
-    uint8_t* bufC = ar_smem + (size_t)2 * bufVals * sizeof(double);
-    const int tid = threadIdx.x;
     const int l = L - 1 - (int)blockIdx.y;
-    const int seq0 = blockIdx.x * kASeqBlock;
-    const int qq = q * q;
-    const int steps = (l + CJ - 1) / CJ;
-
-    // this thread's block elements e = tid + kk * 256 < q * q: (a, b) = (e / q, e % q), contiguous in the source
-    int kA[KPB], kB[KPB];
-#pragma unroll
-    for (int kk = 0; kk < KPB; ++kk) {
-        const int e = tid + kk * kAThreads;
-        kA[kk] = e < qq ? e / q : -1;
-        kB[kk] = e < qq ? e - (e / q) * q : 0;
-    }
-    for (int e = tid; e < 2 * bufVals; e += kAThreads) bufJ[e] = 0.0;      // the row padding stays zero
-
-    double val[CJ][KPB];
-    uint4 cv0 = {}, cv1 = {};
-    auto load = [&](int t) {
-        const int k0 = t * CJ;
-#pragma unroll
-        for (int jj = 0; jj < CJ; ++jj) {
-            const int k = k0 + jj;
-            if (k >= l) continue;
-            const double* blkSrc = x + (size_t)L * q + pair_index(L, k, l) * (size_t)qq;
-#pragma unroll
-            for (int kk = 0; kk < KPB; ++kk)
-                if (kA[kk] >= 0) val[jj][kk] = blkSrc[kA[kk] * q + kB[kk]];
-        }
-        if (tid / 32 < CJ && k0 + tid / 32 < l) cv0 = *reinterpret_cast<const uint4*>(QT + (size_t)(k0 + tid / 32) * NpS + seq0 + (tid & 31) * 16);
-        if constexpr (CPT > 1) {
-            const int e = tid + kAThreads;
-            if (e / 32 < CJ && k0 + e / 32 < l) cv1 = *reinterpret_cast<const uint4*>(QT + (size_t)(k0 + e / 32) * NpS + seq0 + (e & 31) * 16);
-        }
-    };
-    auto store = [&](int t) {
-        const int k0 = t * CJ;
-        double* bj = bufJ + (t & 1) * bufVals;
-        uint8_t* bc = bufC + (t & 1) * codeBytes;
-#pragma unroll
-        for (int jj = 0; jj < CJ; ++jj) {
-            if (k0 + jj >= l) continue;
-#pragma unroll
-            for (int kk = 0; kk < KPB; ++kk)
-                if (kA[kk] >= 0) bj[jj * blk + kA[kk] * QM + kB[kk]] = val[jj][kk];
-        }
-        if (tid / 32 < CJ && k0 + tid / 32 < l) *reinterpret_cast<uint4*>(bc + (tid / 32) * kASeqBlock + (tid & 31) * 16) = cv0;
-        if constexpr (CPT > 1) {
-            const int e = tid + kAThreads;
-            if (e / 32 < CJ && k0 + e / 32 < l) *reinterpret_cast<uint4*>(bc + (e / 32) * kASeqBlock + (e & 31) * 16) = cv1;
-        }
-    };
-
-    double u[kAPerLane][QM];
-#pragma unroll
-    for (int b = 0; b < QM; ++b) {
-        const double h = b < q ? x[(size_t)l * q + b] : 0.0;
-#pragma unroll
-        for (int p = 0; p < kAPerLane; ++p) u[p][b] = h;
-    }
-
-    __syncthreads();
-    if (steps > 0) {
-        load(0);
-        store(0);
-    }
-    __syncthreads();
-
-    for (int t = 0; t < steps; ++t) {
-        const int k0 = t * CJ;
-        if (t + 1 < steps) load(t + 1);
-        const double* cur = bufJ + (t & 1) * bufVals;
-        const uint8_t* cc = bufC + (t & 1) * codeBytes;
-#pragma unroll 1
-        for (int jj = 0; jj < CJ; ++jj) {
-            if (k0 + jj >= l) break;
-#pragma unroll
-            for (int p = 0; p < kAPerLane; ++p) {
-                const double* row = cur + jj * blk + (int)cc[jj * kASeqBlock + p * kAThreads + tid] * QM;
-#pragma unroll
-                for (int b = 0; b < QM; b += 2) {
-                    const double2 v = *reinterpret_cast<const double2*>(row + b);
-                    u[p][b] += v.x; u[p][b + 1] += v.y;
-                }
-            }
-        }
-        if (t + 1 < steps) store(t + 1);
-        __syncthreads();
-    }
-
-#pragma unroll
-    for (int p = 0; p < kAPerLane; ++p) {
-        const int n = seq0 + p * kAThreads + tid;
-        if (n >= nq) continue;
-        const int sl = QT[(size_t)l * NpS + n];
-        double m = u[p][0];
-#pragma unroll
-        for (int b = 1; b < QM; ++b) if (b < q) m = fmax(m, u[p][b]);
-        double Z = 0.0, us = u[p][0];
-#pragma unroll
-        for (int b = 0; b < QM; ++b) {
-            if (b < q) Z += exp(u[p][b] - m);
-            if (b == sl) us = u[p][b];
-        }
-        const double lz = log(Z);
-        site[(size_t)l * NpS + n] = (us - m) - lz;
-        if (R) {
-            const double w = W[n];
-            double* r = R + ((size_t)l * NpS + n) * q;
-#pragma unroll
-            for (int b = 0; b < QM; ++b)
-                if (b < q) r[b] = w * (exp((u[p][b] - m) - lz) - (b == sl ? 1.0 : 0.0));
-        }
-        if (cond) {
-            double* out = cond + ((size_t)n * L + l) * q;
-#pragma unroll
-            for (int b = 0; b < QM; ++b) if (b < q) out[b] = (u[p][b] - m) - lz;
-        }
-    }
-}
-
-// logp[n] = sum_l site[l][n] (ascending l); rows (nq x L) or NULL: the site values in the host layout
-__global__ __launch_bounds__(256)
-void ar_finish_kernel(const double* __restrict__ site, int L, int nq, int NpS, double* __restrict__ logp, double* __restrict__ rows)
-{
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= nq) return;
-    double s = 0.0;
-    for (int l = 0; l < L; ++l) {
-        const double v = site[(size_t)l * NpS + n];
-        s += v;
-        if (rows) rows[(size_t)n * L + l] = v;
-    }
-    logp[n] = s;
+    const ArPolicy<QM> P{x, L, q, l, NpS, W, R};
+    site_conditional_body<double, QM>(P, l, blockIdx.x * kSiteSeqBlock, L, q, QT, nq, NpS, site, cond);
 }
 
 // out[0] = sum_n W_n logp_n: thread t sums n = t, t + 256, ... ascending, then a fixed tree over the 256 partials
@@ -387,50 +253,23 @@ void ar_sample_kernel(const double* __restrict__ x, int L, int q, int n, uint64_
     }
 }
 
-inline int qm_of(int q) { return q <= 8 ? 8 : q <= 24 ? 24 : 32; }
-
-template <int QM>
-size_t logits_lds(int q)
-{
-    constexpr int CJ = chunk_blocks<QM>();
-    return 2 * (size_t)CJ * q * QM * sizeof(double) + 2 * (size_t)CJ * kASeqBlock;
-}
-
-template <int QM>
-hipError_t launch_logits_qm(dca_ctx* ctx, const double* x, int L, int q, const uint8_t* QT, int nq, int NpS, const double* W,
-                            double* site, double* R, double* cond)
-{
-    auto kern = ar_logits_kernel<QM>;
-    const size_t lds = logits_lds<QM>(q);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ceil_div(nq, kASeqBlock), L), dim3(kAThreads), lds, ctx->stream, x, L, q, QT, nq, NpS, W, site, R, cond);
-    return hipGetLastError();
-}
-
+// the logits kernel on the context's stream (callers clock it as "ar_logits")
 hipError_t launch_logits(dca_ctx* ctx, const double* x, int L, int q, const uint8_t* QT, int nq, int NpS, const double* W,
                          double* site, double* R, double* cond)
 {
-    ScopedKernelClock kc(ctx, "ar_logits");
-    switch (qm_of(q)) {
-    case 8: return launch_logits_qm<8>(ctx, x, L, q, QT, nq, NpS, W, site, R, cond);
-    case 24: return launch_logits_qm<24>(ctx, x, L, q, QT, nq, NpS, W, site, R, cond);
-    default: return launch_logits_qm<32>(ctx, x, L, q, QT, nq, NpS, W, site, R, cond);
-    }
+    return with_qm(q, [&](auto qm) {
+        auto kern = ar_logits_kernel<decltype(qm)::value>;
+        const size_t lds = site_lds<double, decltype(qm)::value>(q);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(ceil_div(nq, kSiteSeqBlock), L), dim3(kSiteThreads), lds, ctx->stream, x, L, q, QT, nq, NpS, W, site, R, cond);
+        return hipGetLastError();
+    });
 }
 
 int grad_chunk(int q)
 {
     return std::max(1, std::min({64, (int)(kGBlockBudget / ((size_t)q * q * sizeof(double))), kGMaxThreads / q}));
-}
-
-// sequences per pass: device scratch within kAPassBudget; DCA_AR_PASS (a positive count) caps it
-int ar_pass_size(int n, size_t perSeq)
-{
-    size_t cap = std::max((size_t)kASeqBlock, kAPassBudget / perSeq / kASeqBlock * kASeqBlock);
-    const char* env = getenv("DCA_AR_PASS");
-    if (env && atol(env) > 0) cap = std::min(cap, (size_t)atol(env));
-    return (int)std::min(cap, (size_t)std::max(n, 1));
 }
 
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
@@ -505,8 +344,8 @@ struct ArEngine {
         HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dW), (size_t)N * sizeof(double)));
         HIP_TRY(hipMemcpy(dW, w.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
         free_pass();
-        pass = ar_pass_size(N, (size_t)L * (1 + sizeof(double) + (size_t)q * sizeof(double)) + sizeof(double));
-        NpS = (int)round_up((size_t)pass, kASeqBlock);
+        pass = site_pass_size(N, (size_t)L * (1 + sizeof(double) + (size_t)q * sizeof(double)) + sizeof(double), kAPassBudget, "DCA_AR_PASS", 1);
+        NpS = (int)round_up((size_t)pass, kSiteSeqBlock);
         npass = ceil_div(N, pass);
         HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dQT), (size_t)L * NpS, false));
         HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dSite), (size_t)L * NpS * sizeof(double), false));
@@ -550,11 +389,13 @@ struct ArEngine {
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(ar_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds);
         for (int p = 0; p < npass && e == hipSuccess; ++p) {
             const int first = p * pass, nq = std::min(pass, N - first);
-            hipLaunchKernelGGL(ar_sites_kernel, dim3(blocks_of((size_t)L * NpS)), dim3(256), 0, ctx->stream, ctx->dX + (size_t)first * ctx->Ls,
-                               (size_t)ctx->Ls, nq, L, NpS, dQT);
-            e = launch_logits(ctx, dx, L, q, dQT, nq, NpS, dW + first, dSite, dR, nullptr);
+            e = dca_rows_to_sites(ctx, ctx->dX + (size_t)first * ctx->Ls, (size_t)ctx->Ls, nq, L, NpS, dQT);
+            if (e == hipSuccess) {
+                ScopedKernelClock kc(ctx, "ar_logits");
+                e = launch_logits(ctx, dx, L, q, dQT, nq, NpS, dW + first, dSite, dR, nullptr);
+            }
+            if (e == hipSuccess) e = dca_site_finish(ctx, dSite, L, nq, NpS, dLogp, nullptr);
             if (e != hipSuccess) break;
-            hipLaunchKernelGGL(ar_finish_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, dSite, L, nq, NpS, dLogp, nullptr);
             hipLaunchKernelGGL(ar_wsum_kernel, dim3(1), dim3(256), 0, ctx->stream, dLogp, dW + first, nq, dPassF + p);
             {
                 ScopedKernelClock kc(ctx, "ar_grad");
@@ -703,58 +544,22 @@ struct ArEngine {
 
     int log_probabilities(const uint8_t* X, int n, double* logp_out, double* site_out, double* cond_out)
     {
-        const size_t perSeq = (size_t)L * (2 + sizeof(double)) + sizeof(double) + (site_out ? (size_t)L * sizeof(double) : 0) +
-                              (cond_out ? (size_t)L * q * sizeof(double) : 0);
-        const int cap = ar_pass_size(n, perSeq);
-        const int S = (int)round_up((size_t)cap, kASeqBlock);
-        uint8_t *dRows = nullptr, *dQ = nullptr;
-        double *dS_ = nullptr, *dLp = nullptr, *dRowsOut = nullptr, *dCond = nullptr;
-        hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)cap * L, false);
-        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dQ), (size_t)L * S, false);
-        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dS_), (size_t)L * S * sizeof(double), false);
-        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dLp), (size_t)S * sizeof(double), false);
-        if (e == hipSuccess && site_out) e = dca_dev_malloc(reinterpret_cast<void**>(&dRowsOut), (size_t)cap * L * sizeof(double), false);
-        if (e == hipSuccess && cond_out) e = dca_dev_malloc(reinterpret_cast<void**>(&dCond), (size_t)cap * L * q * sizeof(double), false);
-        for (int first = 0; first < n && e == hipSuccess; first += cap) {
-            const int nq = std::min(cap, n - first);
-            e = hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream);
-            if (e != hipSuccess) break;
-            hipLaunchKernelGGL(ar_sites_kernel, dim3(blocks_of((size_t)L * S)), dim3(256), 0, ctx->stream, dRows, (size_t)L, nq, L, S, dQ);
-            e = launch_logits(ctx, dx, L, q, dQ, nq, S, nullptr, dS_, nullptr, dCond);
-            if (e != hipSuccess) break;
-            hipLaunchKernelGGL(ar_finish_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, dS_, L, nq, S, dLp, dRowsOut);
-            e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(logp_out + first, dLp, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess && site_out)
-                e = hipMemcpyAsync(site_out + (size_t)first * L, dRowsOut, (size_t)nq * L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess && cond_out)
-                e = hipMemcpyAsync(cond_out + (size_t)first * L * q, dCond, (size_t)nq * L * q * sizeof(double), hipMemcpyDeviceToHost,
-                                   ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        }
-        dca_dev_free(dRows); dca_dev_free(dQ); dca_dev_free(dS_); dca_dev_free(dLp); dca_dev_free(dRowsOut); dca_dev_free(dCond);
+        const SitePasses sp{kAPassBudget, "DCA_AR_PASS", 1, "ar_logits"};
+        const hipError_t e = dca_site_passes(ctx, sp, L, q, X, n, logp_out, site_out, cond_out, [&](const uint8_t* dQT, int nq, int NqS, double* dSite, double* dCond) {
+            return launch_logits(ctx, dx, L, q, dQT, nq, NqS, nullptr, dSite, nullptr, dCond);
+        });
         if (e != hipSuccess) return fail(e, "log-probabilities");
         return DCA_OK;
     }
 
-    // cond_l(b) of ONE sequence (host codes, model order) into dCond (device, L*q): the logits kernel with n = 1, so the values
-    // are bit for bit the cond of log_probabilities (the wild-type pass of ar_epistasis.hip)
+    // cond_l(b) of ONE sequence (host codes, model order) into dCond (device, L*q): log_probabilities with n = 1, so the values
+    // are bit for bit its cond (the wild-type pass of ar_epistasis.hip)
     int conditionals_of(const uint8_t* row, double* dCond)
     {
-        const int S = kASeqBlock;
-        uint8_t *dRow = nullptr, *dQ = nullptr;
-        double* dS_ = nullptr;
-        hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRow), (size_t)L, false);
-        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dQ), (size_t)L * S, false);
-        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dS_), (size_t)L * S * sizeof(double), false);
-        if (e == hipSuccess) e = hipMemcpyAsync(dRow, row, (size_t)L, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(ar_sites_kernel, dim3(blocks_of((size_t)L * S)), dim3(256), 0, ctx->stream, dRow, (size_t)L, 1, L, S, dQ);
-            e = launch_logits(ctx, dx, L, q, dQ, 1, S, nullptr, dS_, nullptr, dCond);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        dca_dev_free(dRow); dca_dev_free(dQ); dca_dev_free(dS_);
-        if (e != hipSuccess) return fail(e, "conditionals");
+        double logp = 0.0;
+        std::vector<double> cond((size_t)L * q);
+        DCA_TRY(log_probabilities(row, 1, &logp, nullptr, cond.data()));
+        HIP_TRY(hipMemcpy(dCond, cond.data(), cond.size() * sizeof(double), hipMemcpyHostToDevice));
         return DCA_OK;
     }
 
@@ -772,11 +577,7 @@ struct ArEngine {
                 hipLaunchKernelGGL(kern, dim3(ceil_div(n, kSChainsPerWave)), dim3(64), lds, ctx->stream, dx, L, q, n, seed, first_chain, dOutRows);
                 return hipGetLastError();
             };
-            switch (qm_of(q)) {
-            case 8: e = go(ar_sample_kernel<8>); break;
-            case 24: e = go(ar_sample_kernel<24>); break;
-            default: e = go(ar_sample_kernel<32>); break;
-            }
+            e = with_qm(q, [&](auto qm) { return go(ar_sample_kernel<decltype(qm)::value>); });
         }
         if (e == hipSuccess) e = hipMemcpyAsync(out, dOutRows, (size_t)n * L, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -882,9 +683,7 @@ int dca_ar_log_probabilities(dca_ctx* ctx, const uint8_t* X, int n, double* logp
     if (n < 0 || (n > 0 && (!X || !logp))) { dca_set_error("dca_ar_log_probabilities: bad arguments"); return DCA_ERR_ARG; }
     DCA_TRY(ar_need_engine(ctx, false));
     if (n == 0) return DCA_OK;
-    const int L = ctx->ar->L, q = ctx->ar->q;
-    for (size_t k = 0; k < (size_t)n * L; ++k)
-        if (X[k] >= q) { dca_set_error("code %d >= q at element %zu", (int)X[k], k); return DCA_ERR_ARG; }
+    DCA_TRY(dca_check_codes(X, (size_t)n * ctx->ar->L, ctx->ar->q, ""));
     return ctx->ar->log_probabilities(X, n, logp, site, cond);
 }
 

@@ -179,7 +179,7 @@ int energies_t(dca_ctx* ctx, const PottsView<S>& pv, const uint8_t* X, int n, do
         const int nq = std::min(cap, n - first);
         e = hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) break;
-        e = dca_rows_to_sites(ctx, dRows, nq, L, NqS, dQT);
+        e = dca_rows_to_sites(ctx, dRows, (size_t)L, nq, L, NqS, dQT);
         if (e != hipSuccess) break;
         {
             ScopedKernelClock kc(ctx, "energies");

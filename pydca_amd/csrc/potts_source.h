@@ -61,8 +61,9 @@ auto with_source_type(const PottsSource& ps, F&& f)
     return f(PottsView<double>(ps));
 }
 
-// sample.hip: rows (n x L device bytes) <-> site-major codes st[s * nS + c] (zero past n), on ctx->stream
-hipError_t dca_rows_to_sites(dca_ctx* ctx, const uint8_t* dRows, int n, int L, int nS, uint8_t* dSites);
+// sample.hip: rows (n x L device bytes; row stride ld going in, L coming out) <-> site-major codes st[s * nS + c] (zero past n),
+// on ctx->stream
+hipError_t dca_rows_to_sites(dca_ctx* ctx, const uint8_t* dRows, size_t ld, int n, int L, int nS, uint8_t* dSites);
 hipError_t dca_sites_to_rows(dca_ctx* ctx, const uint8_t* dSites, int n, int L, int nS, uint8_t* dRows);
 
 // energy.hip: DCA_ERR_ARG with "<what>code %d >= q at element %zu" for the first host code >= q

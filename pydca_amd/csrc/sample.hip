@@ -21,7 +21,7 @@
 // the global site-major state buffer.  One launch is one sweep; no atomics, no inter-workgroup communication.  The state
 // buffer lives in a DcaChains (dca_internal.h): dca_potts_sample makes one per call, a Boltzmann-learning run (boltzmann.hip)
 // keeps its own on the device for the whole run.
-#include "dca_internal.h"
+#include "site_conditionals.h"
 
 #include <cmath>
 
@@ -33,12 +33,12 @@ constexpr int kSResidentL = 512;                  // chain codes in LDS up to 32
 constexpr size_t kSChunkBudget = 40 * 1024;       // LDS per J chunk buffer (two of them)
 
 // rows (n x L) <-> site-major state (st[s * nS + c], nS a multiple of 64; chains past n start at code 0)
-__global__ void rows_to_sites_kernel(const uint8_t* __restrict__ rows, int n, int L, int nS, uint8_t* __restrict__ st)
+__global__ void rows_to_sites_kernel(const uint8_t* __restrict__ rows, size_t ld, int n, int L, int nS, uint8_t* __restrict__ st)
 {
     const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (t >= (size_t)L * nS) return;
     const int s = (int)(t / nS), c = (int)(t % nS);
-    st[t] = c < n ? rows[(size_t)c * L + s] : 0;
+    st[t] = c < n ? rows[(size_t)c * ld + s] : 0;
 }
 
 __global__ void sites_to_rows_kernel(const uint8_t* __restrict__ st, int n, int L, int nS, uint8_t* __restrict__ rows)
@@ -204,7 +204,7 @@ struct SampleGeom { int QM, CJ; bool res; size_t lds; };
 SampleGeom sample_geometry(int L, int q, size_t elem)
 {
     SampleGeom g{};
-    g.QM = q <= 8 ? 8 : q <= 24 ? 24 : 32;
+    g.QM = qm_of(q);
     const size_t blkBytes = (size_t)q * g.QM * elem;
     const int R = elem == 4 ? 32 : 16;
     int cj = std::min((int)(kSThreads * R / (q * q)), (int)(kSChunkBudget / blkBytes));
@@ -239,11 +239,7 @@ hipError_t dispatch_res(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& 
 template <typename S, bool INTERP>
 hipError_t dispatch_qm(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
-    switch (sg.QM) {
-    case 8: return dispatch_res<S, 8, INTERP>(ctx, sg, pv, a);
-    case 24: return dispatch_res<S, 24, INTERP>(ctx, sg, pv, a);
-    default: return dispatch_res<S, 32, INTERP>(ctx, sg, pv, a);
-    }
+    return with_qm(pv.q, [&](auto qm) { return dispatch_res<S, decltype(qm)::value, INTERP>(ctx, sg, pv, a); });
 }
 
 // h0 NULL: the plain sweep under beta; otherwise the interpolated one (INTERP above)
@@ -256,10 +252,10 @@ hipError_t dispatch_sweep(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>
 
 }  // namespace
 
-hipError_t dca_rows_to_sites(dca_ctx* ctx, const uint8_t* dRows, int n, int L, int nS, uint8_t* dSites)
+hipError_t dca_rows_to_sites(dca_ctx* ctx, const uint8_t* dRows, size_t ld, int n, int L, int nS, uint8_t* dSites)
 {
     const size_t total = (size_t)L * nS;
-    hipLaunchKernelGGL(rows_to_sites_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dRows, n, L, nS, dSites);
+    hipLaunchKernelGGL(rows_to_sites_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dRows, ld, n, L, nS, dSites);
     return hipGetLastError();
 }
 
@@ -283,7 +279,7 @@ int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t 
         if (initial) {
             e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)n * L, false);
             if (e == hipSuccess) e = hipMemcpyAsync(dRows, initial, (size_t)n * L, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = dca_rows_to_sites(ctx, dRows, n, L, ch->nS, ch->dState);
+            if (e == hipSuccess) e = dca_rows_to_sites(ctx, dRows, (size_t)L, n, L, ch->nS, ch->dState);
         } else {
             hipLaunchKernelGGL(initial_state_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, n, L, q, ch->nS, seed,
                                first_chain, ch->dState);

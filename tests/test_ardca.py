@@ -8,6 +8,7 @@ import pytest
 
 from conftest import data_file
 from test_ardca_host import log_probabilities_ref, conditionals_ref, objective_ref, random_alignment, random_model, sample_ref
+from test_pseudo_likelihood_host import mf_model
 from pydca_amd import _lib, _potts, ardca_main
 from pydca_amd.ardca.ardca import ArDCA
 
@@ -112,6 +113,47 @@ def test_log_probabilities_match_numpy_and_are_batch_invariant(L, q, monkeypatch
     assert np.array_equal(ctx.ar_log_probabilities(Q[5:6]), logp[5:6])
     monkeypatch.setenv("DCA_AR_PASS", "50")
     assert np.array_equal(ctx.ar_log_probabilities(Q), logp)
+
+
+# (2, 5): site 0 has no chunk at all; (17, 8): QM = 8, 16 blocks per chunk and one block into a second chunk; (19, 9): the first
+# q of QM = 24; (8, 24): q = QM, no padding column; (7, 25): the first q of QM = 32, 2 blocks per chunk; (5, 32): q = QM = 32.
+# 600 queries cross the 256-lane and the 512-query block boundary.
+@pytest.mark.parametrize("L,q", [(2, 5), (17, 8), (19, 9), (8, 24), (7, 25), (5, 32)])
+def test_log_probabilities_at_chunk_and_padding_edges(L, q):
+    ctx = ar_context(random_alignment(16, L, q, L * q), q)
+    x = random_model(L, q, L + q)
+    ctx.ar_set_x(x)
+    Q = random_alignment(600, L, q, 17)
+    logp, site, cond = ctx.ar_log_probabilities(Q, per_site=True, conditionals=True)
+    lp_ref, site_ref = log_probabilities_ref(x, Q, L, q)
+    assert rel(logp, lp_ref) <= 1e-12 and rel(site, site_ref) <= 1e-12
+    assert rel(cond, conditionals_ref(x, Q, L, q)) <= 1e-12
+    assert np.array_equal(np.cumsum(site, 1)[:, -1], logp)                         # ascending sum of the site values, bit for bit
+    assert np.array_equal(site, cond[np.arange(600)[:, None], np.arange(L)[None, :], Q.astype(np.int64)])
+
+
+@pytest.mark.parametrize("L,q", [(9, 5), (7, 21), (5, 30)])
+def test_last_site_conditionals_equal_the_pseudo_likelihood_ones(L, q):
+    """At the last site the arDCA and the Potts conditionals are the same sum, term for term and in the same order: h first,
+    then the blocks (k, L-1) for k ascending, read as J(s_k, .).  Both kernels run one body, so the bits agree.  The plm engine
+    holds models of q = 5 and q = 21 only; at q = 30 the Potts model is the mean-field one of a random alignment, and arDCA
+    gets the same numbers in the plm layout (zero on the gap state, as the mean-field source reads it)."""
+    ctx = ar_context(random_alignment(64, L, q, 18), q)
+    if q in (5, 21):
+        x = np.random.default_rng(L * q).normal(0, 0.3, L * q + L * (L - 1) // 2 * q * q)
+        ctx.plm_configure(1.0, 1.0)
+        ctx.plm_set_x(x)
+        entry = ctx.plm_pseudo_likelihood
+    else:
+        ctx.mf_corr_mat(0.5, want=False)
+        h, Jp = mf_model(ctx.mf_couplings(), ctx.mf_fields(), L, q)
+        x = np.concatenate([h.ravel(), Jp.ravel()])
+        entry = ctx.mf_pseudo_likelihood
+    ctx.ar_set_x(x)
+    Q = random_alignment(600, L, q, 19)
+    _pll, cond_pll = entry(Q, conditionals=True)
+    _lp, cond_ar = ctx.ar_log_probabilities(Q, conditionals=True)
+    assert np.array_equal(cond_pll[:, L - 1, :], cond_ar[:, L - 1, :])
 
 
 @pytest.mark.parametrize("L,q", [(4, 5), (3, 21)])

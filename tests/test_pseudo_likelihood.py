@@ -182,18 +182,28 @@ def test_bitwise_invariance_positions_repeats_and_passes(monkeypatch):
 
 
 # ---------------------------------------------------------------- 5. shapes
+# ... and the edges of the accumulator count QM (8 for q <= 8, 24 for q <= 24, else 32) and of its chunks: (17, 8) 16 blocks per
+# chunk and one into a second chunk, (19, 9) the first q of QM = 24, (8, 24) q = QM, (7, 25) the first q of QM = 32, (5, 32)
+# q = QM = 32.  The plm engine holds models of q = 5 and q = 21 only, so these five reach the site kernel through the
+# mean-field source, which is float64: no entry of the library feeds it a float32 model of another q.
 @pytest.mark.parametrize("L,q,prec", [(2, 5, _lib.DCA_F32), (2, 21, _lib.DCA_F64), (7, 21, _lib.DCA_F32), (67, 5, _lib.DCA_F64),
-                                      (700, 5, _lib.DCA_F32)])
+                                      (700, 5, _lib.DCA_F32), (17, 8, _lib.DCA_F64), (19, 9, _lib.DCA_F64), (8, 24, _lib.DCA_F64),
+                                      (7, 25, _lib.DCA_F64), (5, 32, _lib.DCA_F64)])
 def test_edge_shapes(L, q, prec):
     rng = np.random.default_rng(L * q)
-    Xt = rng.integers(0, q, size=(16, L), dtype=np.uint8)
-    ctx, x = plm_context(Xt, q, prec, L)
-    h, Jp = plm_model(x, L, q)
+    if q in (5, 21):
+        ctx, x = plm_context(rng.integers(0, q, size=(16, L), dtype=np.uint8), q, prec, L)
+        h, Jp = plm_model(x, L, q)
+        entry = ctx.plm_pseudo_likelihood
+    else:
+        ctx, J, fields = mf_context(rng.integers(0, q, size=(64, L), dtype=np.uint8), q)
+        h, Jp = mf_model(J, fields, L, q)
+        entry = ctx.mf_pseudo_likelihood
     Q = rng.integers(0, q, size=(600, L), dtype=np.uint8)
-    pll, site, cond = ctx.plm_pseudo_likelihood(Q, per_site=True, conditionals=True)
+    pll, site, cond = entry(Q, per_site=True, conditionals=True)
     idx = np.arange(0, 600, 7 if L > 100 else 1)
     check_against_ref((pll[idx], site[idx], cond[idx]), h, Jp, Q[idx])
-    assert ctx.plm_pseudo_likelihood(Q[:0]).shape == (0,)
+    assert entry(Q[:0]).shape == (0,)
     ctx.close()
 
 
