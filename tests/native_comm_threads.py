@@ -14,10 +14,35 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import lbfgs_step_reference as R  # noqa: E402
 from conftest import golden  # noqa: E402
 from pydca_amd import _lib, parallel  # noqa: E402
 
 FAKE = os.path.join(ROOT, "tests", "fake_rccl", "libfake_rccl.so")
+
+
+def lbfgs_steps(s, x0, dtype, rank, starts):
+    """R.K_STEPS single L-BFGS iterations from x0 on a context of the column-strip decomposition, read back after each
+    (plm_get_x / plm_get_g are collective there: every rank calls them); rank 0 audits every element of every step
+    (tests/lbfgs_step_reference.py) -- the audit does not care how the vectors are partitioned, `starts` only names the
+    rank and loop of the walk a bad element belongs to."""
+    s.plm_set_x(x0.astype(dtype))
+    s.plm_lbfgs_begin(R.K_STEPS)
+    st = s.plm_lbfgs_iterate(0)
+    xs, gs, steps, xn, gn, early = [s.plm_get_x(dtype)], [s.plm_get_g(dtype)], [], [st.xnorm], [st.gnorm], []
+    for k in range(1, R.K_STEPS + 1):
+        early.append(bool(st.finished))
+        st = s.plm_lbfgs_iterate(1)
+        xs.append(s.plm_get_x(dtype))
+        gs.append(s.plm_get_g(dtype))
+        steps.append(st.step)
+        xn.append(st.xnorm)
+        gn.append(st.gnorm)
+    if rank != 0:
+        return None
+    if any(early) or st.iterations != R.K_STEPS:
+        return dict(failures=["stopped early: status %d after %d iterations" % (st.status, st.iterations)], ratios=[])
+    return R.audit(xs, gs, steps, dtype, xn, gn, starts=starts).as_dict()
 
 
 def main():
@@ -49,6 +74,14 @@ def main():
     full32.close()
     M = golden("mf_toy_protein")
     XM = (M["X"] - 1).astype(np.uint8)
+    # column strips: rank r > 0 starts its vectors at L q + pairs_before q^2 -- any residue modulo the 16-byte pack, so the
+    # vector kernels run the misaligned head of their walk (1 to 3 elements in float32)
+    starts = R.strip_starts(X.shape[1], q, world)
+    residues = sorted({v % 4 for v in starts})
+    if world in (2, 8):                       # at world 3 every strip of RF71 happens to start on a 16-byte boundary
+        assert any(residues), (starts, residues)
+    if world == 8:
+        assert 1 in residues and 3 in residues, (starts, residues)
 
     uid_w, uid_p1, uid_p2, uid_p3, uid_m, uid_p4, uid_p5, uid_p6 = (_lib.comm_unique_id(FAKE) for _ in range(8))
     out = [None] * world
@@ -113,6 +146,7 @@ def main():
                     fx_err=abs(fx - fx_ref) / abs(fx_ref), g_err=float(np.linalg.norm(g - g_ref) / np.linalg.norm(g_ref)),
                     status=[st.status, st.iterations, st.evaluations], fx_end_err=abs(st.fx - st_ref.fx) / abs(st_ref.fx),
                     x_err=float(np.linalg.norm(x - x_ref) / np.linalg.norm(x_ref)), x_sum=float(x.sum()), score_sum=float(sc.sum()))
+                res["lbfgs_step_f64"] = lbfgs_steps(s, x0, np.float64, rank, starts)
                 s.close()
                 s = _lib.Context(0, _lib.DCA_F32)
                 s.set_msa(X, q)
@@ -123,6 +157,7 @@ def main():
                 fx = s.plm_gradient()
                 g = s.plm_get_g(np.float64)
                 res["mode4_f32"] = dict(fx_err=abs(fx - fx32_ref) / abs(fx32_ref), g_err=float(np.linalg.norm(g - g32_ref) / np.linalg.norm(g32_ref)))
+                res["lbfgs_step_f32"] = lbfgs_steps(s, x0, np.float32, rank, starts)
                 s.close()
             # mfDCA pair counts summed through the communicator
             m = parallel.make_sharded_mf_context(_lib, XM, int(M["q"]), M["w"], rank, world, 0)
@@ -146,7 +181,8 @@ def main():
         t.start()
     for t in threads:
         t.join(timeout=240)
-    print(json.dumps({"world": world, "reference_status": [st_ref.status, st_ref.iterations, st_ref.evaluations], "ranks": out}), flush=True)
+    print(json.dumps({"world": world, "reference_status": [st_ref.status, st_ref.iterations, st_ref.evaluations],
+                      "strip_starts": starts, "ranks": out}), flush=True)
     os._exit(0)                       # a rank that failed leaves its peers inside a barrier
 
 

@@ -644,6 +644,15 @@ def test_native_exchange_path_with_several_ranks(world):
         assert r["mode4_f32"]["fx_err"] <= 1e-6 and r["mode4_f32"]["g_err"] < 1e-5, r["mode4_f32"]      # float32: the window changes the slab split
         assert r["mf_err"] < 1e-9
         assert r["mf_stale_counts_dropped"] and r["mf_fi_err"] < 1e-13, r      # reduction switched on after a query; re-weighted afterwards
+    # lbfgs_step: eight single iterations under column strips, every element of every step audited by rank 0 against the
+    # high-precision direction (tests/lbfgs_step_reference.py).  The strips start at any residue modulo the 16-byte pack, so
+    # this is where the misaligned head of the vector kernels' walk runs: 2 elements at world 2, 1 and 3 at world 8 (float32)
+    assert world == 3 or any(v % 4 for v in res["strip_starts"]), res["strip_starts"]      # world 3: every start a multiple of 4
+    for key in ("lbfgs_step_f32", "lbfgs_step_f64"):
+        a = res["ranks"][0][key]
+        print("\n[lbfgs-step] world %d %s: %s" % (world, key, {k: v for k, v in a.items() if k != "failures"}))
+        assert not a["failures"], (key, a["failures"])
+        assert len(a["ratios"]) == 8 and max(a["ratios"]) <= 1.0, (key, a)
 
 
 @pytest.mark.parametrize("mode", ["vectors", "allreduce", "selflaunch"])
