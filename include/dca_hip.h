@@ -638,12 +638,48 @@ int dca_sequence_statistics(dca_ctx* ctx, const uint8_t* Q, int nq, double* fi_o
  * pairs*q*q in pair order; either may be NULL, not both) -- the x that dca_sequence_statistics compares with, bit for bit. */
 int dca_alignment_statistics(dca_ctx* ctx, double* fi_out, double* fij_out);
 
+/* Three-site connected correlations, the statistic no pairwise fit has seen:
+ *   c_ijk(a,b,c) = f_ijk(a,b,c) - f_ij(a,b) f_k(c) - f_ik(a,c) f_j(b) - f_jk(b,c) f_i(a) + 2 f_i(a) f_j(b) f_k(c)
+ * All three-site work is in integers.  Sequence n carries the weight wq_n = llrint(w_n * 2^40) for the alignment (Q == NULL; w_n
+ * the context's double weights, the ones dca_alignment_statistics uses) and wq_n = 1 for a query set; the denominator is
+ * M = sum_n wq_n (nq for a set).  Every count -- of a triple, and of the one- and two-site marginals that enter c_ijk -- is the
+ * uint64 sum of wq over the matching sequences, a frequency is (double)count / (double)M, and c_ijk is formed in double, without
+ * contraction, in exactly the order written, left to right, the last term as 2.0 * f_i * f_j * f_k.  So c_ijk sums to zero over
+ * any of its three state indices up to rounding, and nothing depends on the launch geometry, the order of any atomic (all are
+ * integer) or the pass split.  For a set f_i and f_ij are bit-equal to dca_sequence_statistics.  For the alignment the quantised
+ * weights are a different, fully specified weighting: its f_i and f_ij differ from dca_alignment_statistics by at most
+ * 2 N 2^-41 / Meff.  An alignment of more than 2^23 sequences, or a weight outside [0, 1] (dca_set_weights; the weights of
+ * dca_compute_weights are 1 / count), is DCA_ERR_ARG: the sums stay below 2^63.
+ *
+ * dca_three_site_values: elements = T rows (i, j, k, a, b, c), i < j < k < L, states < q, in the context's column order; a row
+ * may repeat.  Q == NULL: the context's alignment under its quantised weights; else nq x L host codes with unit weights, uploaded
+ * in passes of at most DCA_NN_PASS queries (the variable of dca_hamming_nearest; integers make the split invisible).
+ * count_out (uint64[T]), denom_out (uint64*), f3_out, c3_out (double[T]) may each be NULL, not all.
+ *
+ * dca_three_site_scan: the K elements of largest |c_ijk(a,b,c)| over ALL site triples i < j < k and all states (states equal to
+ * skip_state left out of a, b and c; -1: none), of the alignment (Q == NULL) or of a set.  Sorted by |c| descending, ties by
+ * ascending (i, j, k, a, b, c).  *found = min(K, number of eligible elements); elements_out holds K rows of 6, c3_out and f3_out
+ * (either may be NULL) K values.  The scan tiles the later sites (j, k) in TB x TB blocks, TB the largest of 8, 4, 2 with
+ * TB^2 q^2 <= 7168 (q = 5: 8, q = 21: 4, q = 32: 2); the result does not depend on it.  Exact, with device memory O(K) beyond the
+ * pair table: a histogram pass over the high bits of |c|, at most one refinement of the bin that holds the K-th value, and an
+ * append pass whose buffer the histogram sized.  If more than 16 K + 2^20 elements still tie with the K-th value (for instance
+ * K reaches into exact zeros of a large alignment) the call is DCA_ERR_ARG with a message instead of allocating without bound
+ * (DCA_THREE_SITE_CAP, a positive count read per call, replaces that cap).
+ *
+ * DCA_ERR_STATE: no alignment; weights missing with Q == NULL.  DCA_ERR_ARG: L < 3, K < 1, T < 1, nq < 1 with Q, an index out of
+ * order or out of range, a code >= q, a NULL context.  Profiling tags "three_site_scan" (one launch per pass), "three_site_values".
+ * No reference counterpart. */
+int dca_three_site_values(dca_ctx* ctx, const uint8_t* Q, int nq, const int32_t* elements, int T,
+                          uint64_t* count_out, uint64_t* denom_out, double* f3_out, double* c3_out);
+int dca_three_site_scan(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int skip_state,
+                        int32_t* elements_out, double* c3_out, double* f3_out, int* found);
+
 /* ------------------------------------------------------------------ timing
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
  * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "ar_logits", "ar_grad", "ar_sample", "ar_epistasis",
- * "bm_stats", "ais", "hamming", "set_compare"). */
+ * "bm_stats", "ais", "hamming", "set_compare", "three_site_scan", "three_site_values"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it
  * instead of two per stage (an event record costs the stream ~5 us: 14 per plmDCA iteration are 5 % of config C's step, 0.4 % of

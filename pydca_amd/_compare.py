@@ -1,9 +1,10 @@
-"""Comparing sequence sets with the alignment: Hamming distances to the nearest natural sequence and the
-agreement of one- and two-site frequencies and connected correlations.  Model-free -- the methods need the alignment and its
+"""Comparing sequence sets with the alignment (DESIGN.md sections 17 and 20): Hamming distances to the nearest natural sequence,
+the agreement of one- and two-site frequencies and connected correlations and, beyond what a pairwise fit has seen, of the
+strongest three-site connected correlations.  Model-free -- the methods need the alignment and its
 sequence weights, never fitted parameters -- so one mixin serves PlmDCA, MeanFieldDCA and ArDCA, before or after a fit."""
 import numpy as np
 
-from . import _potts
+from . import _lib, _potts
 
 
 def distance_summary(dist):
@@ -29,6 +30,38 @@ def pairs_to_order(fij, order):
     swap = a > b
     out[swap] = np.transpose(out[swap], (0, 2, 1))
     return out
+
+
+def _relabel_elements(elements, site_map):
+    el = np.asarray(elements)
+    sites = np.asarray(site_map)[el[:, :3]]
+    o = np.argsort(sites, axis=1, kind='stable')
+    out = np.empty(el.shape, dtype=np.int32)
+    out[:, :3] = np.take_along_axis(sites, o, axis=1)
+    out[:, 3:] = np.take_along_axis(el[:, 3:], o, axis=1)
+    return out
+
+
+def elements_from_order(elements, order):
+    """Three-site elements (i, j, k, a, b, c) over the columns of a permuted alignment (position j holds file site order[j]) ->
+    the same elements over the file's sites: every site relabelled, then the three (site, state) pairs sorted by site, so
+    i < j < k again and every state follows its site.  The rows keep their order."""
+    return _relabel_elements(elements, np.asarray(order))
+
+
+def elements_to_order(elements, order):
+    """The inverse of elements_from_order: elements over the file's sites -> over the permuted alignment's columns."""
+    return _relabel_elements(elements, np.argsort(np.asarray(order)))
+
+
+def centred_fit(x, y):
+    """(pearson, slope, max |x - y|) of two vectors with the analytic mean 0, as dca_set_comparison defines them: Sxx = sum x^2,
+    Syy, Sxy; pearson = Sxy / sqrt(Sxx Syy) (0 when Sxx Syy <= 0), slope = Sxy / Sxx (0 when Sxx == 0).  In double."""
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    sxx, syy, sxy = float(np.dot(x, x)), float(np.dot(y, y)), float(np.dot(x, y))
+    vv = sxx * syy
+    return (float(sxy / np.sqrt(vv)) if vv > 0.0 else 0.0, sxy / sxx if sxx > 0.0 else 0.0,
+            float(np.max(np.abs(x - y))) if x.size else 0.0)
 
 
 def _picked(dist, index, hist, return_index, return_histogram):
@@ -94,15 +127,72 @@ class SequenceComparison:
         Q = self._compare_codes(sequences, 'compute_set_diversity')
         return self._compare_context().hamming_nearest(None, Q, True)
 
-    def compare_with_alignment(self, sequences, return_frequencies=False):
+    def _three_site_count(self, name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise self._compare_exc('{} must be an integer, not {!r}'.format(name, v))
+        return int(v)
+
+    def _three_site_skip(self, include_gaps, name='include_gaps'):
+        # the encoders of both residue tables give the gap the last code, q - 1
+        return -1 if _flag(name, include_gaps, self._compare_exc) else self._compare_dims()[2] - 1
+
+    def _three_site_scan(self, ctx, K, Q, skip):
+        el, c3, f3 = ctx.three_site_scan(K, Q, skip)
+        order = self._compare_order()
+        return (el if order is None else elements_from_order(el, order)), c3, f3
+
+    def _three_site_elements(self, elements):
+        _bio, L, q = self._compare_dims()
+        try:
+            return _lib.three_site_elements(elements, L, q)
+        except ValueError as e:
+            raise self._compare_exc(str(e))
+
+    def compute_top_three_site_correlations(self, num_top=10000, sequences=None, include_gaps=True):
+        """The num_top strongest three-site connected correlations c_ijk(a, b, c) = f_ijk - f_ij f_k - f_ik f_j - f_jk f_i +
+        2 f_i f_j f_k, found by scanning ALL site triples and states, of the alignment under its sequence weights (sequences None)
+        or of a sequence set (a FASTA path or a list of aligned strings; unit weights) -> dict: elements int32[K, 6], rows
+        (i, j, k, a, b, c) with the sites in file order and i < j < k; c3 and f3 float64[K].  Sorted by |c3| descending; equal
+        values in ascending order of the row as the context holds it (for ArDCA that is the model's site order, so ties may
+        come in another order than from PlmDCA).  K = min(num_top, number of elements).  include_gaps=False leaves every
+        element that names the gap state out.  Counts are integers: the alignment's weights enter as llrint(w 2^40)."""
+        K = self._three_site_count('num_top', num_top)
+        if K < 1:
+            raise self._compare_exc('num_top must be >= 1, not {}'.format(K))
+        skip = self._three_site_skip(include_gaps)
+        self._compare_one_gpu('compute_top_three_site_correlations')
+        if self._compare_dims()[1] < 3:
+            raise self._compare_exc('three-site correlations need at least three sites')
+        Q = None if sequences is None else self._compare_codes(sequences, 'compute_top_three_site_correlations')
+        el, c3, f3 = self._three_site_scan(self._compare_context(), K, Q, skip)
+        return {'elements': el, 'c3': c3, 'f3': f3}
+
+    def compute_three_site_correlations(self, elements, sequences=None):
+        """(f3, c3), float64[T] each, at the listed elements: int[T, 6] rows (i, j, k, a, b, c), sites in file order with
+        i < j < k, states as the encoder codes them -- of the alignment under its weights (sequences None) or of a set."""
+        el = self._three_site_elements(elements)
+        self._compare_one_gpu('compute_three_site_correlations')
+        Q = None if sequences is None else self._compare_codes(sequences, 'compute_three_site_correlations')
+        order = self._compare_order()
+        _count, _denom, f3, c3 = self._compare_context().three_site_values(el if order is None else elements_to_order(el, order), Q)
+        return f3, c3
+
+    def compare_with_alignment(self, sequences, return_frequencies=False, three_site=0, three_site_include_gaps=True):
         """Do the sequences reproduce the alignment's statistics?  -> dict: pearson_fi / pearson_fij / pearson_cij, slope_* and
         max_abs_diff_* of the set's one-site frequencies, two-site frequencies and connected correlations c_ij(a, b) = f_ij(a, b)
         - f_i(a) f_j(b) against the alignment's under its sequence weights (no pseudocount; x = alignment, y = set; all states,
         gap included); num_sequences; nearest_distance (int32[n], compute_distances_to_alignment) with nearest_distance_mean /
         _median / _min and fraction_identical (distance 0); alignment_self_distance_mean / _median / _min
         (compute_alignment_self_distances).  return_frequencies adds fi (L x q) and fij (pairs x q x q, pair order) of the set,
-        sites in file order."""
+        sites in file order.  three_site = K > 0 adds the check on a statistic the fit never saw: the alignment's K strongest
+        three-site connected correlations (compute_top_three_site_correlations, with three_site_include_gaps) against the set's
+        values at the same elements -- pearson_cijk, slope_cijk, max_abs_diff_cijk (same definitions, analytic mean 0) and
+        three_site_terms, the number of elements compared."""
         rf = _flag('return_frequencies', return_frequencies, self._compare_exc)
+        K3 = self._three_site_count('three_site', three_site)
+        if K3 < 0:
+            raise self._compare_exc('three_site must be >= 0, not {}'.format(K3))
+        skip3 = self._three_site_skip(three_site_include_gaps, 'three_site_include_gaps')
         self._compare_one_gpu('compare_with_alignment')
         Q = self._compare_codes(sequences, 'compare_with_alignment')
         ctx = self._compare_context()
@@ -117,6 +207,11 @@ class SequenceComparison:
         out['nearest_distance_mean'], out['nearest_distance_median'], out['nearest_distance_min'] = distance_summary(d)
         out['fraction_identical'] = float(np.mean(d == 0))
         out['alignment_self_distance_mean'], out['alignment_self_distance_median'], out['alignment_self_distance_min'] = distance_summary(s)
+        if K3 > 0:
+            el, x3, _f3 = ctx.three_site_scan(K3, None, skip3)         # the context's column order serves both calls
+            y3 = ctx.three_site_values(el, Q)[3] if el.shape[0] else np.zeros(0)
+            out['pearson_cijk'], out['slope_cijk'], out['max_abs_diff_cijk'] = centred_fit(x3, y3)
+            out['three_site_terms'] = int(el.shape[0])
         if rf:
             order = self._compare_order()
             if order is not None:
@@ -127,14 +222,15 @@ class SequenceComparison:
         return out
 
 
-def run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type):
+def run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type, three_site=0, three_site_include_gaps=True):
     """compare_sequences of the plmdca, mfdca and ardca command lines -> the path of <output_dir>/<prefix>_sequence_comparison_
     <alignment base>.txt (dca_utilities.write_sequence_comparison).  No fit is run."""
     from .dca_utilities import dca_utilities
     if not query_file:
         raise exc_type('compare_sequences needs --query_file')
     dca_utilities.create_directories(output_dir)
-    summary = instance.compare_with_alignment(query_file)
+    extra = dict(three_site=int(three_site), three_site_include_gaps=bool(three_site_include_gaps)) if three_site else {}
+    summary = instance.compare_with_alignment(query_file, **extra)
     dist, index, hist = instance.compute_distances_to_alignment(query_file, return_index=True, return_histogram=True)
     _d, self_hist = instance.compute_alignment_self_distances(return_histogram=True)
     path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_sequence_comparison_', postfix='.txt')

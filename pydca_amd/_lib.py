@@ -170,6 +170,8 @@ def lib():
         "dca_hamming_nearest": (i, [vp, vp, i, vp, i, i, vp, vp, vp]),
         "dca_sequence_statistics": (i, [vp, vp, i, vp, vp, C.POINTER(SetComparison)]),
         "dca_alignment_statistics": (i, [vp, vp, vp]),
+        "dca_three_site_values": (i, [vp, vp, i, vp, i, vp, vp, vp, vp]),
+        "dca_three_site_scan": (i, [vp, vp, i, i, i, vp, vp, vp, C.POINTER(i)]),
         "dca_plm_ais": (i, [vp, C.POINTER(AisArgs), vp, C.POINTER(d), vp]),
         "dca_mf_ais": (i, [vp, C.POINTER(AisArgs), vp, C.POINTER(d), vp]),
         "dca_ais_estimate": (i, [vp, i, d, C.POINTER(d), C.POINTER(d), C.POINTER(d)]),
@@ -221,10 +223,36 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_plm_bm_begin", "dca_plm_bm_iterate", "dca_plm_bm_freqs", "dca_plm_bm_chains", "dca_plm_bm_end",
            "dca_plm_ais", "dca_mf_ais", "dca_ais_estimate",
            "dca_hamming_nearest", "dca_sequence_statistics", "dca_alignment_statistics",
+           "dca_three_site_values", "dca_three_site_scan",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
            "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
            "dca_reset_kernel_times", "dca_plm_run", "plmdcaBackend", "freeFieldsAndCouplings"]
+
+
+def three_site_elements(elements, L, q):
+    """elements of the three-site entries -> int32[T, 6], rows (i, j, k, a, b, c) checked as dca_three_site_values checks them
+    (0 <= i < j < k < L, states in 0 .. q-1); ValueError otherwise.  Needs no device."""
+    try:
+        raw = np.asarray(elements)
+    except Exception:
+        raise ValueError("elements must be an integer array of shape (T, 6)")
+    if raw.dtype == object or raw.ndim != 2 or raw.shape[1] != 6 or not (np.issubdtype(raw.dtype, np.integer) or raw.dtype == np.bool_):
+        raise ValueError("elements must be an integer array of shape (T, 6) with rows (i, j, k, a, b, c), not %s of shape %s"
+                         % (raw.dtype, raw.shape))
+    if raw.shape[0] < 1:
+        raise ValueError("elements must hold at least one row")
+    big = raw.astype(np.int64)
+    s, st = big[:, :3], big[:, 3:]
+    bad = (s[:, 0] < 0) | (s[:, 0] >= s[:, 1]) | (s[:, 1] >= s[:, 2]) | (s[:, 2] >= L)
+    if bad.any():
+        k = int(np.argmax(bad))
+        raise ValueError("element %d names the sites %s; they must satisfy 0 <= i < j < k < %d" % (k, tuple(int(v) for v in s[k]), L))
+    bad = ((st < 0) | (st >= q)).any(axis=1)
+    if bad.any():
+        k = int(np.argmax(bad))
+        raise ValueError("element %d names the states %s; states are 0 .. %d" % (k, tuple(int(v) for v in st[k]), q - 1))
+    return np.ascontiguousarray(big, dtype=np.int32)
 
 
 def ais_schedule(temperatures, betas=None):
@@ -879,6 +907,33 @@ class Context:
         fij = np.zeros((self.L * (self.L - 1) // 2, self.q, self.q), dtype=np.float64)
         check(self._l.dca_alignment_statistics(self._h, _ptr(fi), _ptr(fij)))
         return fi, fij
+
+    # ---- three-site connected correlations (three_site.hip): integer counts, quantised alignment weights (include/dca_hip.h)
+    def three_site_values(self, elements, Q=None):
+        """elements: int32[T, 6] rows (i, j, k, a, b, c) in the context's column order; Q: uint8[nq, L] or None (the alignment
+        under its weights) -> (uint64[T] counts, int denominator, float64[T] f3, float64[T] c3)"""
+        el = np.ascontiguousarray(elements, dtype=np.int32).reshape(-1, 6)      # the library checks the rows
+        q_ = None if Q is None else np.ascontiguousarray(Q, dtype=np.uint8).reshape(-1, self.L)
+        T = el.shape[0]
+        count, denom = np.zeros(T, dtype=np.uint64), C.c_uint64(0)
+        f3, c3 = np.zeros(T, dtype=np.float64), np.zeros(T, dtype=np.float64)
+        check(self._l.dca_three_site_values(self._h, None if q_ is None else _ptr(q_), 0 if q_ is None else int(q_.shape[0]),
+                                            _ptr(el) if T else None, int(T), _ptr(count) if T else None, C.byref(denom),
+                                            _ptr(f3) if T else None, _ptr(c3) if T else None))
+        return count, int(denom.value), f3, c3
+
+    def three_site_scan(self, K, Q=None, skip_state=-1):
+        """The K elements of largest |c_ijk(a, b, c)| of the alignment (Q None) or of the set Q, |c| descending, ties by ascending
+        (i, j, k, a, b, c) -> (int32[found, 6], float64[found] c3, float64[found] f3)"""
+        q_ = None if Q is None else np.ascontiguousarray(Q, dtype=np.uint8).reshape(-1, self.L)
+        K = int(K)
+        el = np.zeros((max(K, 1), 6), dtype=np.int32)
+        c3, f3 = np.zeros(max(K, 1), dtype=np.float64), np.zeros(max(K, 1), dtype=np.float64)
+        found = C.c_int(0)
+        check(self._l.dca_three_site_scan(self._h, None if q_ is None else _ptr(q_), 0 if q_ is None else int(q_.shape[0]), K,
+                                          int(skip_state), _ptr(el), _ptr(c3), _ptr(f3), C.byref(found)))
+        n = found.value
+        return el[:n].copy(), c3[:n].copy(), f3[:n].copy()
 
     # ---- log Z by annealed importance sampling (ais.hip) -> (float64[n] log weights, log Z0, uint8[n, L] final chains or None)
     def _ais(self, fn, chains, temperatures, sweeps_per_temperature, seed, first_chain, betas, base_fields, return_chains):

@@ -318,7 +318,7 @@ def run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, opts):
 
 
 def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata, biomolecule, table, exc_type,
-                   query_file=None, wildtype_file=None, sampling=None, ais=None):
+                   query_file=None, wildtype_file=None, sampling=None, ais=None, three_site=0, three_site_no_gaps=False):
     """compute_energies / compute_mutation_effects / sample_sequences / compute_pseudo_log_likelihood / compare_sequences of the
     plmdca and mfdca command lines -> the path of the file written: <output_dir>/<prefix>_energies_<alignment base>.txt,
     <prefix>_mutation_effects_<alignment base>.txt, <prefix>_samples_<alignment base>.fa,
@@ -329,7 +329,8 @@ def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata
         return run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, ais)
     if the_command == 'compare_sequences':
         from . import _compare
-        return _compare.run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type)
+        return _compare.run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type, three_site=int(three_site or 0),
+                                    three_site_include_gaps=not three_site_no_gaps)
     dca_utilities.create_directories(output_dir)
     if the_command == 'sample_sequences':
         opts = dict(sampling or {})

@@ -72,7 +72,8 @@ def write_mutation_effects(path, dlogp, wildtype_letters, state_letters, metadat
 
 def execute_from_command_line(biomolecule, msa_file, the_command=None, seqid=None, lambda_h=None, lambda_J=None, max_iterations=None,
                               epsilon=None, order=None, output_dir=None, verbose=False, device=0, query_file=None, wildtype_file=None,
-                              num_sequences=None, seed=None, apc=False, refseq_file=None):
+                              num_sequences=None, seed=None, apc=False, refseq_file=None, three_site=0,
+                              three_site_no_gaps=False):
     if verbose:
         logging.basicConfig(level=logging.INFO, format='%(levelname)s %(name)s: %(message)s')
     if the_command not in ARDCA_SUBCOMMANDS:
@@ -96,7 +97,8 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, seqid=Non
     meta = ardca_param_metadata(instance)
     if the_command == 'compare_sequences':
         from . import _compare
-        return _compare.run_compare(instance, 'ARDCA', msa_file, output_dir, meta, query_file, ardca.ArDCAException)
+        return _compare.run_compare(instance, 'ARDCA', msa_file, output_dir, meta, query_file, ardca.ArDCAException,
+                                    three_site=int(three_site or 0), three_site_include_gaps=not three_site_no_gaps)
     if the_command == 'compute_log_probabilities':
         logp = instance.compute_sequence_log_probabilities(query_file)
         out = path('log_probabilities', '.txt')
@@ -165,6 +167,10 @@ def build_parser():
             p.add_argument('--query_file', help='FASTA file of aligned query sequences (default: the records of msa_file)')
         if name == 'compare_sequences':
             p.add_argument('--query_file', required=True, help='FASTA file of aligned sequences to compare with the alignment; no fit is run')
+            p.add_argument('--three_site', type=int, default=0, help='K > 0: also compare the alignment\'s K strongest three-site '
+                           'connected correlations, found by a scan of all triples, with the set\'s')
+            p.add_argument('--three_site_no_gaps', action='store_true', help='leave elements that name the gap state out of '
+                           '--three_site')
         if name == 'compute_mutation_effects':
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence')
         if name in ('compute_fn', 'compute_epistasis'):
@@ -191,7 +197,8 @@ def run_ardca(argv=None):
         epsilon=args.get('epsilon'), order=args.get('order'), output_dir=args.get('output_dir'), verbose=args.get('verbose'),
         device=args.get('device'), query_file=args.get('query_file'), wildtype_file=args.get('wildtype_file'),
         num_sequences=args.get('num_sequences'), seed=args.get('seed'), apc=bool(args.get('apc')),
-        refseq_file=args.get('refseq_file'))
+        refseq_file=args.get('refseq_file'), three_site=args.get('three_site') or 0,
+        three_site_no_gaps=bool(args.get('three_site_no_gaps')))
 
 
 if __name__ == '__main__':

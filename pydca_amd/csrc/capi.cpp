@@ -601,6 +601,34 @@ int dca_alignment_statistics(dca_ctx* ctx, double* fi_out, double* fij_out)
     return dca_set_statistics_impl(ctx, nullptr, 0, fi_out, fij_out, nullptr);
 }
 
+static int three_site_state(dca_ctx* ctx, const char* who, const uint8_t* Q, int nq)
+{
+    if (!ctx->dX) { dca_set_error("%s: dca_set_msa first", who); return DCA_ERR_STATE; }
+    if (ctx->L < 3) { dca_set_error("%s: three-site correlations need an alignment of at least three sites, not %d", who, ctx->L); return DCA_ERR_ARG; }
+    if (Q && nq < 1) { dca_set_error("%s: nq %d < 1", who, nq); return DCA_ERR_ARG; }
+    if (!Q && !ctx->have_weights) { dca_set_error("%s: dca_compute_weights or dca_set_weights first (Q is NULL: the alignment under its weights)", who); return DCA_ERR_STATE; }
+    return DCA_OK;
+}
+int dca_three_site_values(dca_ctx* ctx, const uint8_t* Q, int nq, const int32_t* elements, int T, uint64_t* count_out,
+                          uint64_t* denom_out, double* f3_out, double* c3_out)
+{
+    CHECK_CTX(ctx);
+    if (!elements || T < 1) { dca_set_error("dca_three_site_values: elements is NULL or T %d < 1", T); return DCA_ERR_ARG; }
+    if (!count_out && !denom_out && !f3_out && !c3_out) { dca_set_error("dca_three_site_values: every output is NULL"); return DCA_ERR_ARG; }
+    DCA_TRY(three_site_state(ctx, "dca_three_site_values", Q, nq));
+    return dca_three_site_values_impl(ctx, Q, nq, elements, T, count_out, denom_out, f3_out, c3_out);
+}
+int dca_three_site_scan(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int skip_state, int32_t* elements_out, double* c3_out,
+                        double* f3_out, int* found)
+{
+    CHECK_CTX(ctx);
+    if (K < 1) { dca_set_error("dca_three_site_scan: K %d < 1", K); return DCA_ERR_ARG; }
+    if (!elements_out || !found) { dca_set_error("dca_three_site_scan: elements_out or found is NULL"); return DCA_ERR_ARG; }
+    DCA_TRY(three_site_state(ctx, "dca_three_site_scan", Q, nq));
+    if (skip_state < -1 || skip_state >= ctx->q) { dca_set_error("dca_three_site_scan: skip_state %d is neither -1 nor a state < %d", skip_state, ctx->q); return DCA_ERR_ARG; }
+    return dca_three_site_scan_impl(ctx, Q, nq, K, skip_state, elements_out, c3_out, f3_out, found);
+}
+
 int dca_plm_di_scores(dca_ctx* ctx, const double* reg_fi, int apc, double* out)
 {
     CHECK_CTX(ctx);

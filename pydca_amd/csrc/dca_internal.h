@@ -282,6 +282,14 @@ int dca_hamming_nearest_impl(dca_ctx* ctx, const uint8_t* Q, int nq, const uint8
                              int32_t* index_out, uint64_t* hist_out);
 int dca_set_statistics_impl(dca_ctx* ctx, const uint8_t* Q, int nq, double* fi_out, double* fij_out, dca_set_comparison* cmp_out);
 
+// ---- three_site.hip : three-site connected correlations of the alignment (Q == NULL, quantised weights) or of a set, at listed
+// elements and as a scan for the K strongest (dca_three_site_values, dca_three_site_scan; arguments checked in capi.cpp except
+// the elements and the codes)
+int dca_three_site_values_impl(dca_ctx* ctx, const uint8_t* Q, int nq, const int32_t* elements, int T, uint64_t* count_out,
+                               uint64_t* denom_out, double* f3_out, double* c3_out);
+int dca_three_site_scan_impl(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int skip_state, int32_t* elements_out, double* c3_out,
+                             double* f3_out, int* found);
+
 int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, const double* reg_fi, int L, int q,
                             double* fields_out, double* di_out, const double* fields_in = nullptr);
 
