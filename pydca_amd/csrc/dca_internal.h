@@ -149,11 +149,6 @@ int dca_comm_native(dca_ctx* ctx, int op, void* buf, size_t count, int dtype, bo
 int dca_comm_native_reduce(dca_ctx* ctx, void* vec, size_t count, int dtype, double* scalar_dev);
 int dca_comm_native_sum_u32(dca_ctx* ctx, uint32_t* buf, size_t count);
 
-// ---- reductions.hip : deterministic device reductions
-// out[slot] = sum(partials[0..n)) ; single block, fixed tree
-int dca_reduce_partials(dca_ctx* ctx, const double* dPartials, int n, double* dOut);
-int dca_sum_doubles(dca_ctx* ctx, const double* dVals, int n, double* dOut);  // two-stage
-
 // ---- plm engine
 struct PlmEngineBase {
     virtual ~PlmEngineBase() {}

@@ -97,4 +97,40 @@ __global__ void vec_step_kernel(T* __restrict__ x, const T* __restrict__ xp, T s
         { const T v = stpv * d[i]; x[i] = xp[i] + v; })
 }
 
+// ------------------------------------------------------------------ double-double sums (plm_stages.h, lbfgs_kernels.h)
+// The objective is summed in double-double (error-free TwoSum): N*L terms in whatever order the kernels meet them
+// would otherwise leave ~1e-13 of rounding noise in fx, the line search interpolates on DIFFERENCES of fx, and over 100
+// iterations of an optimisation that does not converge that noise grew to 6e-4 in the scores at config E
+// (profiles/r03_e_sensitivity_cap100_plain_sums.json).  An (almost) exact sum does not depend on the order: chunked scan, serial
+// chain, any sharding and the float64 oracle (Neumaier sums) then see the same fx to the last bit or two.
+__device__ __forceinline__ void dd_add(double& hi, double& lo, double v)
+{
+    const double s = hi + v;
+    const double bb = s - hi;
+    lo += (hi - (s - bb)) + (v - bb);
+    hi = s;
+}
+__device__ __forceinline__ void dd_add2(double& hi, double& lo, double vh, double vl) { dd_add(hi, lo, vh); lo += vl; }
+__device__ __forceinline__ void dd_wave_reduce(double& hi, double& lo)       // fixed tree over the 64 lanes; lane 0 holds the sum
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        const double vh = __shfl_down(hi, off), vl = __shfl_down(lo, off);
+        dd_add2(hi, lo, vh, vl);
+    }
+}
+
+__device__ __forceinline__ void dd_block_reduce(double& hi, double& lo, double* redHi, double* redLo)      // result in thread 0
+{
+    redHi[threadIdx.x] = hi;
+    redLo[threadIdx.x] = lo;
+    __syncthreads();
+    for (int st = blockDim.x / 2; st > 0; st >>= 1) {
+        if ((int)threadIdx.x < st) dd_add2(redHi[threadIdx.x], redLo[threadIdx.x], redHi[threadIdx.x + st], redLo[threadIdx.x + st]);
+        __syncthreads();
+    }
+    hi = redHi[0];
+    lo = redLo[0];
+    __syncthreads();
+}
+
 }  // namespace
