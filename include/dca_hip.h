@@ -50,6 +50,9 @@ const char* dca_version(void);
 /* Device blocks of 1 MiB and more are kept in a process-wide cache when a context releases them and are handed to
  * later contexts (DCA_POOL_MAX_BYTES, default 64 GiB per process).  This returns them to the driver; result: bytes released. */
 size_t dca_release_cached_memory(void);
+/* Device blocks the library has allocated and not yet released, of any size, over all contexts of the process (a block in
+ * the cache above is not in use). */
+size_t dca_device_blocks_in_use(void);
 
 /* ------------------------------------------------------------------ drop-in FFI
  * Same symbols, signatures and meaning as the reference's ctypes boundary

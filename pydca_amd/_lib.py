@@ -90,6 +90,7 @@ def lib():
         "dca_version": (C.c_char_p, []),
         "dca_device_count": (i, []),
         "dca_release_cached_memory": (sz, []),
+        "dca_device_blocks_in_use": (sz, []),
         "dca_read_msa": (i, [C.c_char_p, i, i, vp, i, C.POINTER(i)]),
         "dca_count_msa_lines": (i, [C.c_char_p]),
         "dca_fasta_shape": (i, [C.c_char_p, C.POINTER(i), C.POINTER(i)]),
@@ -208,7 +209,7 @@ def lib():
 
 EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_partial_counts", "dca_set_weight_counts", "dca_comm_unique_id",
            "dca_comm_init", "dca_comm_destroy", "dca_comm_abort", "dca_comm_info", "dca_plm_set_native_comm", "dca_mf_set_native_comm",
-           "dca_last_error", "dca_version", "dca_device_count", "dca_release_cached_memory", "dca_read_msa", "dca_count_msa_lines", "dca_read_msa_alloc", "dca_mf_set_row_window", "dca_comm_allgather_host", "dca_fasta_shape", "dca_read_fasta", "dca_read_fasta_alloc", "dca_host_free", "dca_create",
+           "dca_last_error", "dca_version", "dca_device_count", "dca_release_cached_memory", "dca_device_blocks_in_use", "dca_read_msa", "dca_count_msa_lines", "dca_read_msa_alloc", "dca_mf_set_row_window", "dca_comm_allgather_host", "dca_fasta_shape", "dca_read_fasta", "dca_read_fasta_alloc", "dca_host_free", "dca_create",
            "dca_destroy", "dca_set_msa", "dca_compute_weights", "dca_set_weights", "dca_get_weights",
            "dca_get_weight_counts", "dca_get_meff", "dca_plm_configure", "dca_plm_configure_strips", "dca_plm_num_params", "dca_plm_init_x",
            "dca_plm_set_x", "dca_plm_get_x", "dca_plm_release", "dca_plm_gradient", "dca_plm_get_g", "dca_plm_set_reduce_hook", "dca_mf_set_reduce_hook", "dca_di_from_arrays", "dca_di_from_fields", "dca_plm_set_vector_sharding",
@@ -334,6 +335,11 @@ def comm_unique_id(rccl_path=None):
 def release_cached_memory():
     """Return the library's cached device blocks (>= 1 MiB, kept across contexts) to the driver -> bytes released."""
     return int(lib().dca_release_cached_memory())
+
+
+def device_blocks_in_use():
+    """Device blocks the library has allocated and not yet released, over all contexts of the process."""
+    return int(lib().dca_device_blocks_in_use())
 
 
 def check(rc):

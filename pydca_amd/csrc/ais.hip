@@ -134,38 +134,28 @@ int dca_potts_ais(dca_ctx* ctx, const PottsSource& ps, const dca_ais_args* args,
     DcaChains ch;
     ch.n = n; ch.L = L; ch.nS = (int)round_up((size_t)n, kAisStride);
     const int G = dca_energy_slab_count(ps);
-    double *dH0 = nullptr, *dLogW = nullptr, *dSlabs = nullptr;
+    DevBuf<double> dH0, dLogW, dSlabs;
     const size_t sites = (size_t)L * ch.nS;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&ch.dState), sites, false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dH0), h0.size() * sizeof(double), false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dLogW), (size_t)ch.nS * sizeof(double), false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dSlabs), (size_t)G * ch.nS * sizeof(double), false);
-    if (e == hipSuccess) e = hipMemcpyAsync(dH0, h0.data(), h0.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dLogW, 0, (size_t)ch.nS * sizeof(double), ctx->stream);
-    if (e == hipSuccess) {
+    HIP_TRY_AS(ch.dState.alloc(sites, false), "ais");
+    HIP_TRY_AS(dH0.alloc(h0.size(), false), "ais");
+    HIP_TRY_AS(dLogW.alloc((size_t)ch.nS, false), "ais");
+    HIP_TRY_AS(dSlabs.alloc((size_t)G * ch.nS, false), "ais");
+    HIP_TRY_AS(hipMemcpyAsync(dH0, h0.data(), h0.size() * sizeof(double), hipMemcpyHostToDevice, ctx->stream), "ais");
+    HIP_TRY_AS(hipMemsetAsync(dLogW, 0, (size_t)ch.nS * sizeof(double), ctx->stream), "ais");
+    {
         ScopedKernelClock kc(ctx, "ais");
-        hipLaunchKernelGGL(ais_start_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, dH0, n, L, q, ch.nS,
-                           args->seed, args->first_chain, ch.dState);
-        e = hipGetLastError();
+        hipLaunchKernelGGL(ais_start_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, dH0.get(), n, L, q, ch.nS,
+                           args->seed, args->first_chain, ch.dState.get());
+        HIP_TRY_AS(hipGetLastError(), "ais");
     }
-    int rc = e == hipSuccess ? DCA_OK : DCA_ERR_HIP;
-    for (int k = 1; k <= K && rc == DCA_OK; ++k) {
-        e = weight_step(ctx, ps, ch, dSlabs, G, dH0, beta[k] - beta[k - 1], dLogW);
-        if (e != hipSuccess) { rc = DCA_ERR_HIP; break; }
+    for (int k = 1; k <= K; ++k) {
+        HIP_TRY_AS(weight_step(ctx, ps, ch, dSlabs, G, dH0, beta[k] - beta[k - 1], dLogW), "ais");
         if (k < K && s > 0)
-            rc = dca_chains_sweeps(ctx, ch, ps, s, args->seed, args->first_chain, (uint64_t)(k - 1) * (uint64_t)s, 1.0, dH0, beta[k]);
+            DCA_TRY(dca_chains_sweeps(ctx, ch, ps, s, args->seed, args->first_chain, (uint64_t)(k - 1) * (uint64_t)s, 1.0, dH0, beta[k]));
     }
-    if (rc == DCA_OK) {
-        e = hipMemcpyAsync(log_weights_out, dLogW, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = DCA_ERR_HIP;
-    }
-    if (rc == DCA_OK && chains_out) rc = dca_chains_read(ctx, ch, chains_out);
-    if (rc == DCA_ERR_HIP && e != hipSuccess) dca_set_error("ais: %s", hipGetErrorString(e));
-    hipStreamSynchronize(ctx->stream);
-    dca_dev_free(dH0); dca_dev_free(dLogW); dca_dev_free(dSlabs);
-    dca_chains_free(&ch);
-    return rc;
+    HIP_TRY_AS(hipMemcpyAsync(log_weights_out, dLogW, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "ais");
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), "ais");
+    return chains_out ? dca_chains_read(ctx, ch, chains_out) : DCA_OK;
 }
 
 // log Z0 = sum_i (m_i + log sum_a exp(h0_i(a) - m_i)), ascending i and a

@@ -243,10 +243,9 @@ std::vector<int2> epistasis_tiles(int L, int q)
 }
 
 struct EpiBuffers {
-    uint8_t* dW = nullptr;
-    double *dCond = nullptr, *dPm = nullptr, *dSpm = nullptr, *dTerm = nullptr, *dV = nullptr, *dD = nullptr, *dVec = nullptr;
-    int2* dTiles = nullptr;
-    ~EpiBuffers() { for (void* p : {(void*)dW, (void*)dCond, (void*)dPm, (void*)dSpm, (void*)dTerm, (void*)dV, (void*)dD, (void*)dVec, (void*)dTiles}) dca_dev_free(p); }
+    DevBuf<uint8_t> dW;
+    DevBuf<double> dCond, dPm, dSpm, dTerm, dV, dD, dVec;
+    DevBuf<int2> dTiles;
 };
 
 // B.dVec <- L q zeros, then eps in pair order (the plm layout scoring.hip reads); B.dD <- d.  Everything stays on the device.
@@ -254,12 +253,10 @@ int epistasis_device(dca_ctx* ctx, const double* dx, int L, int q, const uint8_t
 {
     const size_t Lq = (size_t)L * q, pairs = (size_t)L * (L - 1) / 2, qq = (size_t)q * q;
     const std::vector<int2> tiles = epistasis_tiles(L, q);
-    auto need = [&](void** p, size_t bytes) { return dca_dev_malloc(p, bytes, false) == hipSuccess; };
-    if (!need(reinterpret_cast<void**>(&B.dW), (size_t)L) || !need(reinterpret_cast<void**>(&B.dCond), Lq * sizeof(double)) ||
-        !need(reinterpret_cast<void**>(&B.dPm), Lq * sizeof(double)) || !need(reinterpret_cast<void**>(&B.dSpm), Lq * sizeof(double)) || !need(reinterpret_cast<void**>(&B.dD), Lq * sizeof(double)) ||
-        !need(reinterpret_cast<void**>(&B.dTerm), pairs * q * sizeof(double)) || !need(reinterpret_cast<void**>(&B.dV), pairs * qq * sizeof(double)) ||
-        !need(reinterpret_cast<void**>(&B.dVec), (Lq + pairs * qq) * sizeof(double)) ||
-        !need(reinterpret_cast<void**>(&B.dTiles), tiles.size() * sizeof(int2))) {
+    if (B.dW.alloc((size_t)L, false) != hipSuccess || B.dCond.alloc(Lq, false) != hipSuccess || B.dPm.alloc(Lq, false) != hipSuccess ||
+        B.dSpm.alloc(Lq, false) != hipSuccess || B.dD.alloc(Lq, false) != hipSuccess || B.dTerm.alloc(pairs * q, false) != hipSuccess ||
+        B.dV.alloc(pairs * qq, false) != hipSuccess || B.dVec.alloc(Lq + pairs * qq, false) != hipSuccess ||
+        B.dTiles.alloc(tiles.size(), false) != hipSuccess) {
         (void)hipGetLastError();
         dca_set_error("arDCA epistasis: out of device memory (%.0f MB for L = %d, q = %d)", (2.0 * pairs * qq + pairs * q) * 8e-6, L, q);
         return DCA_ERR_NOMEM;
@@ -268,22 +265,21 @@ int epistasis_device(dca_ctx* ctx, const double* dx, int L, int q, const uint8_t
     HIP_TRY(hipMemcpyAsync(B.dW, wildtype, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(B.dTiles, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(B.dVec, 0, Lq * sizeof(double), ctx->stream));
-    hipError_t e = hipSuccess;
+    static const char* who = "arDCA epistasis";
     {
         ScopedKernelClock kc(ctx, "ar_epistasis");
         const unsigned lqBlocks = (unsigned)((Lq + 255) / 256);
-        hipLaunchKernelGGL(epi_prob_kernel, dim3(lqBlocks), dim3(256), 0, ctx->stream, B.dCond, (int)Lq, B.dPm, B.dSpm);
-        hipLaunchKernelGGL(epi_pairs_kernel, dim3(L - 1, L - 1), dim3(256), 0, ctx->stream, dx, B.dW, B.dPm, B.dSpm, L, q, B.dV, B.dTerm);
-        hipLaunchKernelGGL(epi_single_kernel, dim3(lqBlocks), dim3(256), 0, ctx->stream, B.dCond, B.dTerm, B.dW, L, q, B.dD);
-        e = hipGetLastError();
-        if (e == hipSuccess) {
-            e = with_qm(q, [&](auto qm) {
-                return launch_main<decltype(qm)::value>(ctx, dx, B.dW, B.dV, B.dTiles, (int)tiles.size(), L, q, B.dVec + Lq);
-            });
-        }
+        hipLaunchKernelGGL(epi_prob_kernel, dim3(lqBlocks), dim3(256), 0, ctx->stream, B.dCond.get(), (int)Lq, B.dPm.get(), B.dSpm.get());
+        hipLaunchKernelGGL(epi_pairs_kernel, dim3(L - 1, L - 1), dim3(256), 0, ctx->stream, dx, B.dW.get(), B.dPm.get(), B.dSpm.get(), L, q,
+                           B.dV.get(), B.dTerm.get());
+        hipLaunchKernelGGL(epi_single_kernel, dim3(lqBlocks), dim3(256), 0, ctx->stream, B.dCond.get(), B.dTerm.get(), B.dW.get(), L, q,
+                           B.dD.get());
+        HIP_TRY_AS(hipGetLastError(), who);
+        HIP_TRY_AS(with_qm(q, [&](auto qm) {
+            return launch_main<decltype(qm)::value>(ctx, dx, B.dW, B.dV, B.dTiles, (int)tiles.size(), L, q, B.dVec + Lq);
+        }), who);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);     // the host copies of the wild type and the tiles are read until here
-    if (e != hipSuccess) { dca_set_error("arDCA epistasis: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);     // the host copies of the wild type and the tiles are read until here
     return DCA_OK;
 }
 
@@ -328,20 +324,9 @@ int dca_ar_epistatic_scores(dca_ctx* ctx, const uint8_t* wildtype, int apc, doub
     EpiBuffers B;
     DCA_TRY(epistasis_device(ctx, dx, L, q, wildtype, B));
     const size_t npairs = (size_t)L * (L - 1) / 2;
-    double* dScores = nullptr;
-    if (dca_dev_malloc(reinterpret_cast<void**>(&dScores), npairs * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        dca_set_error("dca_ar_epistatic_scores: out of device memory");
-        return DCA_ERR_NOMEM;
-    }
-    int rc = dca_fn_scores(ctx, B.dVec, 0, DCA_F64, L, q, 0, apc, dScores);
-    if (rc == DCA_OK) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(scores_out, dScores, npairs * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { dca_set_error("copy scores: %s", hipGetErrorString(e)); rc = DCA_ERR_HIP; }
-    }
-    dca_dev_free(dScores);
-    return rc;
+    return dca_download_doubles(ctx, npairs, scores_out, "copy scores",
+                                [&](double* dScores) { return dca_fn_scores(ctx, B.dVec, 0, DCA_F64, L, q, 0, apc, dScores); },
+                                "dca_ar_epistatic_scores");
 }
 
 }  // extern "C"

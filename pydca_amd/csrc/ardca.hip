@@ -282,29 +282,19 @@ struct ArEngine {
     size_t P = 0;
     bool configured = false;
     double lh = 0.0, lJ = 0.0;
-    double *dx = nullptr, *dg = nullptr, *dW = nullptr;
+    DevBuf<double> dx, dg, dW;
     // passes of the fit
     int pass = 0, NpS = 0, npass = 0;
-    uint8_t* dQT = nullptr;
-    double *dSite = nullptr, *dR = nullptr, *dLogp = nullptr, *dPassF = nullptr;
+    DevBuf<uint8_t> dQT;
+    DevBuf<double> dSite, dR, dLogp, dPassF;
     // scalars: dot partials, results
-    double *dPart = nullptr, *dOut = nullptr;
+    DevBuf<double> dPart, dOut;
     // optimiser
-    double *dxp = nullptr, *dgp = nullptr, *dd = nullptr, *dS[5] = {}, *dY[5] = {};
+    DevBuf<double> dxp, dgp, dd, dS[5], dY[5];
     int evals = 0;
 
     explicit ArEngine(dca_ctx* c) : ctx(c) {}
-    ~ArEngine()
-    {
-        free_pass();
-        for (double* p : {dx, dg, dW, dPart, dOut, dxp, dgp, dd}) dca_dev_free(p);
-        for (int i = 0; i < 5; ++i) { dca_dev_free(dS[i]); dca_dev_free(dY[i]); }
-    }
-    void free_pass()
-    {
-        dca_dev_free(dQT); dca_dev_free(dSite); dca_dev_free(dR); dca_dev_free(dLogp); dca_dev_free(dPassF);
-        dQT = nullptr; dSite = dR = dLogp = dPassF = nullptr;
-    }
+    void free_pass() { dQT.reset(); dSite.reset(); dR.reset(); dLogp.reset(); dPassF.reset(); }
 
     int fail(hipError_t e, const char* what)
     {
@@ -316,15 +306,15 @@ struct ArEngine {
     int ensure_x()
     {
         if (dx && L == ctx->L && q == ctx->q) return DCA_OK;
-        dca_dev_free(dx); dca_dev_free(dg); dx = dg = nullptr;
+        dx.reset(); dg.reset();
         L = ctx->L; q = ctx->q;
         P = dca_plm_num_params(L, q);
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dx), P * sizeof(double)));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dg), P * sizeof(double)));
+        HIP_TRY(dx.alloc(P));
+        HIP_TRY(dg.alloc(P));
         HIP_TRY(hipMemsetAsync(dx, 0, P * sizeof(double), ctx->stream));
         HIP_TRY(hipMemsetAsync(dg, 0, P * sizeof(double), ctx->stream));
-        if (!dPart) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dPart), kDotBlocks * sizeof(double)));
-        if (!dOut) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dOut), 16 * sizeof(double)));
+        if (!dPart) HIP_TRY(dPart.alloc(kDotBlocks));
+        if (!dOut) HIP_TRY(dOut.alloc(16));
         return DCA_OK;
     }
 
@@ -340,18 +330,17 @@ struct ArEngine {
         const double meff = ctx->meff;
         if (!(meff > 0.0)) { dca_set_error("arDCA: the weights sum to %g", meff); return DCA_ERR_ARG; }
         for (double& v : w) v = v / meff;
-        dca_dev_free(dW); dW = nullptr;
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dW), (size_t)N * sizeof(double)));
+        HIP_TRY(dW.alloc((size_t)N));
         HIP_TRY(hipMemcpy(dW, w.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
         free_pass();
         pass = site_pass_size(N, (size_t)L * (1 + sizeof(double) + (size_t)q * sizeof(double)) + sizeof(double), kAPassBudget, "DCA_AR_PASS", 1);
         NpS = (int)round_up((size_t)pass, kSiteSeqBlock);
         npass = ceil_div(N, pass);
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dQT), (size_t)L * NpS, false));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dSite), (size_t)L * NpS * sizeof(double), false));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dR), (size_t)L * NpS * q * sizeof(double), false));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dLogp), (size_t)NpS * sizeof(double), false));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dPassF), (size_t)npass * sizeof(double), false));
+        HIP_TRY(dQT.alloc((size_t)L * NpS, false));
+        HIP_TRY(dSite.alloc((size_t)L * NpS, false));
+        HIP_TRY(dR.alloc((size_t)L * NpS * q, false));
+        HIP_TRY(dLogp.alloc((size_t)NpS, false));
+        HIP_TRY(dPassF.alloc((size_t)npass, false));
         configured = true;
         return DCA_OK;
     }
@@ -459,10 +448,10 @@ struct ArEngine {
         constexpr int M = 5;
         const auto t0 = std::chrono::steady_clock::now();
         if (!dxp) {
-            for (double** p : {&dxp, &dgp, &dd}) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(p), P * sizeof(double)));
+            for (DevBuf<double>* b : {&dxp, &dgp, &dd}) HIP_TRY(b->alloc(P));
             for (int i = 0; i < M; ++i) {
-                HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dS[i]), P * sizeof(double)));
-                HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dY[i]), P * sizeof(double)));
+                HIP_TRY(dS[i].alloc(P));
+                HIP_TRY(dY[i].alloc(P));
             }
         }
         evals = 0;
@@ -477,16 +466,16 @@ struct ArEngine {
         for (;;) {
             if (std::sqrt(gg) <= epsilon * std::max(1.0, std::sqrt(xx))) { status = DCA_AR_CONVERGED; break; }
             if (k >= max_iterations) { status = DCA_AR_MAX_ITERATIONS; break; }
-            std::swap(dx, dxp);
-            std::swap(dg, dgp);
+            dx.swap(dxp);
+            dg.swap(dgp);
             const double fprev = fx, ggprev = gg, xxprev = xx;
             // the search rejects 0 < dginit, as the reference's does, and would take a zero slope; none reaches it: dginit
             // is -gg, where gg = 0 has converged above (epsilon >= 0), or the g.d that the reset below found < 0
             const int ls = line_search(&step, &fx, dginit, &gg, &xx, &rc);
             if (rc) return rc;
             if (ls < 0) {                                     // back to the last accepted point
-                std::swap(dx, dxp);
-                std::swap(dg, dgp);
+                dx.swap(dxp);
+                dg.swap(dgp);
                 fx = fprev; gg = ggprev; xx = xxprev;
                 status = DCA_AR_LINE_SEARCH_FAILED;
                 break;
@@ -567,22 +556,21 @@ struct ArEngine {
     {
         const size_t lds = (size_t)64 * ceil_div(L, kSSlices);
         if (lds > 160 * 1024) { dca_set_error("arDCA sample: L = %d exceeds the sampler's %d sites", L, 160 * 1024 / 64 * kSSlices); return DCA_ERR_ARG; }
-        uint8_t* dOutRows = nullptr;
-        hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dOutRows), (size_t)n * L, false);
-        if (e == hipSuccess) {
+        static const char* who = "arDCA sample";
+        DevBuf<uint8_t> dOutRows;
+        HIP_TRY_AS(dOutRows.alloc((size_t)n * L, false), who);
+        {
             ScopedKernelClock kc(ctx, "ar_sample");
             auto go = [&](auto kern) {
-                hipError_t r = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                if (r != hipSuccess) return r;
-                hipLaunchKernelGGL(kern, dim3(ceil_div(n, kSChainsPerWave)), dim3(64), lds, ctx->stream, dx, L, q, n, seed, first_chain, dOutRows);
+                HIP_PASS(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL(kern, dim3(ceil_div(n, kSChainsPerWave)), dim3(64), lds, ctx->stream, dx.get(), L, q, n, seed, first_chain,
+                                   dOutRows.get());
                 return hipGetLastError();
             };
-            e = with_qm(q, [&](auto qm) { return go(ar_sample_kernel<decltype(qm)::value>); });
+            HIP_TRY_AS(with_qm(q, [&](auto qm) { return go(ar_sample_kernel<decltype(qm)::value>); }), who);
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(out, dOutRows, (size_t)n * L, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        dca_dev_free(dOutRows);
-        if (e != hipSuccess) return fail(e, "sample");
+        HIP_TRY_AS(hipMemcpyAsync(out, dOutRows, (size_t)n * L, hipMemcpyDeviceToHost, ctx->stream), who);
+        HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
         return DCA_OK;
     }
 };

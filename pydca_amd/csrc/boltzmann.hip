@@ -14,6 +14,7 @@
 #include "dca_internal.h"
 
 #include <cmath>
+#include <memory>
 
 namespace {
 
@@ -166,13 +167,8 @@ struct BmRun {
     double eta_h = 0, eta_J = 0, mu_h = 0, mu_J = 0;
     long long t = 0;                       // iterations since begin
     DcaChains ch;
-    double *dFi = nullptr, *dFij = nullptr, *dGi = nullptr, *dEps = nullptr, *dSlab = nullptr, *dRec = nullptr;
+    DevBuf<double> dFi, dFij, dGi, dEps, dSlab, dRec;
     int tb = 0, nb = 0, tiles = 0, recCap = 0;
-    ~BmRun()
-    {
-        dca_chains_free(&ch);
-        dca_dev_free(dFi); dca_dev_free(dFij); dca_dev_free(dGi); dca_dev_free(dEps); dca_dev_free(dSlab); dca_dev_free(dRec);
-    }
 };
 
 namespace {
@@ -181,59 +177,53 @@ namespace {
 int bm_tile(int q) { return q <= 8 ? 16 : q <= 24 ? 4 : 2; }
 
 template <typename S, int TB, bool UPDATE>
-hipError_t launch_pairs_tb(dca_ctx* ctx, BmRun* r, S* x, double* gij)
+hipError_t launch_pairs_tb(dca_ctx* ctx, const BmRun* r, const DcaChains& ch, S* x, double* gi, double* gij)
 {
     auto kern = bm_pairs_kernel<S, TB, UPDATE>;
     const size_t lds = (size_t)TB * TB * r->q * r->q * sizeof(uint32_t);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(r->nb, r->nb), dim3(kBmThreads), lds, ctx->stream, r->ch.dState, r->ch.nS, r->ch.n, r->L, r->q, r->nb,
-                       r->dFi, r->dFij, r->dGi, x, r->eta_J, r->mu_J, r->dSlab, gij);
+    hipLaunchKernelGGL(kern, dim3(r->nb, r->nb), dim3(kBmThreads), lds, ctx->stream, ch.dState.get(), ch.nS, ch.n, r->L, r->q, r->nb,
+                       r->dFi.get(), r->dFij.get(), gi, x, r->eta_J, r->mu_J, r->dSlab.get(), gij);
     return hipGetLastError();
 }
 
 template <typename S, bool UPDATE>
-hipError_t launch_pairs(dca_ctx* ctx, BmRun* r, S* x, double* gij)
+hipError_t launch_pairs(dca_ctx* ctx, const BmRun* r, const DcaChains& ch, S* x, double* gi, double* gij)
 {
     switch (r->tb) {
-    case 16: return launch_pairs_tb<S, 16, UPDATE>(ctx, r, x, gij);
-    case 4: return launch_pairs_tb<S, 4, UPDATE>(ctx, r, x, gij);
-    default: return launch_pairs_tb<S, 2, UPDATE>(ctx, r, x, gij);
+    case 16: return launch_pairs_tb<S, 16, UPDATE>(ctx, r, ch, x, gi, gij);
+    case 4: return launch_pairs_tb<S, 4, UPDATE>(ctx, r, ch, x, gi, gij);
+    default: return launch_pairs_tb<S, 2, UPDATE>(ctx, r, ch, x, gi, gij);
     }
 }
 
-// the statistics of the current chains; UPDATE: with the update of x and the record written to dRec[slot]
+// the statistics of the chains ch into gi (and gij); UPDATE: with the update of x and the record written to dRec[slot]
 template <typename S, bool UPDATE>
-hipError_t bm_stats(dca_ctx* ctx, BmRun* r, S* x, int slot, double* gij)
+hipError_t bm_stats(dca_ctx* ctx, const BmRun* r, const DcaChains& ch, S* x, int slot, double* gi, double* gij)
 {
     ScopedKernelClock kc(ctx, "bm_stats");
-    hipLaunchKernelGGL((bm_fields_kernel<S, UPDATE>), dim3(r->L), dim3(kBmThreads), 0, ctx->stream, r->ch.dState, r->ch.nS, r->ch.n, r->q,
-                       r->dFi, r->dGi, x, r->eta_h, r->mu_h, r->dEps);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = launch_pairs<S, UPDATE>(ctx, r, x, gij);
-    if (e == hipSuccess && UPDATE) {
+    hipLaunchKernelGGL((bm_fields_kernel<S, UPDATE>), dim3(r->L), dim3(kBmThreads), 0, ctx->stream, ch.dState.get(), ch.nS, ch.n, r->q,
+                       r->dFi.get(), gi, x, r->eta_h, r->mu_h, r->dEps.get());
+    HIP_PASS(hipGetLastError());
+    HIP_PASS((launch_pairs<S, UPDATE>(ctx, r, ch, x, gi, gij)));
+    if (UPDATE) {
         const double M = (double)((size_t)r->L * (r->L - 1) / 2) * (double)(r->q * r->q);
-        hipLaunchKernelGGL(bm_record_kernel, dim3(1), dim3(kBmThreads), 0, ctx->stream, r->dSlab, r->tiles, r->dEps, r->L, M,
+        hipLaunchKernelGGL(bm_record_kernel, dim3(1), dim3(kBmThreads), 0, ctx->stream, r->dSlab.get(), r->tiles, r->dEps.get(), r->L, M,
                            r->dRec + (size_t)3 * slot);
-        e = hipGetLastError();
     }
-    return e;
+    return hipGetLastError();
 }
 
 }  // namespace
 
 hipError_t dca_bm_count_chains(dca_ctx* ctx, const DcaChains& ch, int q, double* dGi, double* dGij)
 {
-    BmRun r;                               // a view of the caller's chains and buffers for the launchers above; it owns nothing
+    BmRun r;                               // the geometry for the launchers above; it owns nothing
     r.L = ch.L; r.q = q;
     r.tb = bm_tile(q);
     r.nb = ceil_div(ch.L, r.tb);
-    r.ch = ch;
-    r.dGi = dGi;
-    const hipError_t e = bm_stats<float, false>(ctx, &r, nullptr, 0, dGij);
-    r.ch = DcaChains();
-    r.dGi = nullptr;
-    return e;
+    return bm_stats<float, false>(ctx, &r, ch, nullptr, 0, dGi, dGij);
 }
 
 namespace {
@@ -264,7 +254,7 @@ int dca_bm_begin_impl(dca_ctx* ctx, void* dx, int dtype, const dca_bm_args* a)
         return DCA_ERR_ARG;
     }
     if (a->initial) DCA_TRY(dca_check_codes(a->initial, (size_t)a->chains * L, q, "dca_plm_bm_begin: initial "));
-    BmRun* r = new BmRun();
+    std::unique_ptr<BmRun> r(new BmRun());
     r->L = L; r->q = q; r->dtype = dtype;
     r->k = a->sweeps; r->E = a->equilibration_sweeps; r->seed = a->seed;
     r->eta_h = a->eta_h; r->eta_J = a->eta_J; r->mu_h = a->mu_h; r->mu_J = a->mu_J;
@@ -272,27 +262,22 @@ int dca_bm_begin_impl(dca_ctx* ctx, void* dx, int dtype, const dca_bm_args* a)
     r->nb = ceil_div(L, r->tb);
     r->tiles = r->nb * (r->nb + 1) / 2;
     const size_t Lq = (size_t)L * q, pairs = (size_t)L * (L - 1) / 2;
-    auto fail = [&](int rc) { delete r; return rc; };
-    if (dca_dev_malloc(reinterpret_cast<void**>(&r->dFi), Lq * sizeof(double), false) != hipSuccess ||
-        dca_dev_malloc(reinterpret_cast<void**>(&r->dFij), pairs * q * q * sizeof(double), false) != hipSuccess ||
-        dca_dev_malloc(reinterpret_cast<void**>(&r->dGi), Lq * sizeof(double)) != hipSuccess ||
-        dca_dev_malloc(reinterpret_cast<void**>(&r->dEps), (size_t)L * sizeof(double)) != hipSuccess ||
-        dca_dev_malloc(reinterpret_cast<void**>(&r->dSlab), (size_t)r->tiles * kBmSums * sizeof(double)) != hipSuccess) {
+    if (r->dFi.alloc(Lq, false) != hipSuccess || r->dFij.alloc(pairs * q * q, false) != hipSuccess || r->dGi.alloc(Lq) != hipSuccess ||
+        r->dEps.alloc((size_t)L) != hipSuccess || r->dSlab.alloc((size_t)r->tiles * kBmSums) != hipSuccess) {
         dca_set_error("dca_plm_bm_begin: out of device memory");
-        return fail(DCA_ERR_NOMEM);
+        return DCA_ERR_NOMEM;
     }
     // data statistics from the mf engine's weighted counts: a private engine, so the context's own mf state stays as it is
     {
         MfEngine* m = dca_make_mf_engine(ctx);
         const int rc = dca_mf_engine_bm_freqs(m, a->pseudocount, r->dFi, r->dFij);
         dca_free_mf_engine(m);
-        if (rc != DCA_OK) return fail(rc);
+        DCA_TRY(rc);
     }
-    int rc = dca_chains_start(ctx, &r->ch, a->chains, L, q, a->seed, 0, a->initial);
-    if (rc == DCA_OK) rc = dca_chains_sweeps(ctx, r->ch, bm_model(r, dx), r->E, r->seed, 0, 0, 1.0);
-    if (rc == DCA_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) { dca_set_error("dca_plm_bm_begin: stream failed"); rc = DCA_ERR_HIP; }
-    if (rc != DCA_OK) return fail(rc);
-    ctx->bm = r;
+    DCA_TRY(dca_chains_start(ctx, &r->ch, a->chains, L, q, a->seed, 0, a->initial));
+    DCA_TRY(dca_chains_sweeps(ctx, r->ch, bm_model(r.get(), dx), r->E, r->seed, 0, 0, 1.0));
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) { dca_set_error("dca_plm_bm_begin: stream failed"); return DCA_ERR_HIP; }
+    ctx->bm = r.release();
     return DCA_OK;
 }
 
@@ -303,15 +288,15 @@ int dca_bm_iterate_impl(dca_ctx* ctx, void* dx, int iterations, dca_bm_record* r
     if (iterations < 0) { dca_set_error("dca_plm_bm_iterate: iterations %d < 0", iterations); return DCA_ERR_ARG; }
     if (iterations == 0) return DCA_OK;
     if (iterations > r->recCap) {
-        dca_dev_free(r->dRec); r->dRec = nullptr; r->recCap = 0;
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&r->dRec), (size_t)iterations * 3 * sizeof(double)));
+        r->recCap = 0;
+        HIP_TRY(r->dRec.alloc((size_t)iterations * 3));
         r->recCap = iterations;
     }
     for (int it = 0; it < iterations; ++it) {
         const uint64_t first = (uint64_t)r->E + (uint64_t)r->t * (uint64_t)r->k;
         DCA_TRY(dca_chains_sweeps(ctx, r->ch, bm_model(r, dx), r->k, r->seed, 0, first, 1.0));
-        const hipError_t e = r->dtype == DCA_F32 ? bm_stats<float, true>(ctx, r, static_cast<float*>(dx), it, nullptr)
-                                                 : bm_stats<double, true>(ctx, r, static_cast<double*>(dx), it, nullptr);
+        const hipError_t e = r->dtype == DCA_F32 ? bm_stats<float, true>(ctx, r, r->ch, static_cast<float*>(dx), it, r->dGi, nullptr)
+                                                 : bm_stats<double, true>(ctx, r, r->ch, static_cast<double*>(dx), it, r->dGi, nullptr);
         if (e != hipSuccess) { dca_set_error("dca_plm_bm_iterate: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
         ++r->t;
     }
@@ -334,14 +319,14 @@ int dca_bm_freqs_impl(dca_ctx* ctx, int which, double* fi_out, double* fij_out)
     }
     if (r->t == 0) { dca_set_error("dca_plm_bm_freqs: no iteration has run yet"); return DCA_ERR_STATE; }
     // the chains are those of the last iteration's statistics (its sweeps came before them): count them again, x untouched
-    double* dG = nullptr;
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dG), std::max<size_t>(nij, 1) * sizeof(double), false));
-    hipError_t e = r->dtype == DCA_F32 ? bm_stats<float, false>(ctx, r, nullptr, 0, dG) : bm_stats<double, false>(ctx, r, nullptr, 0, dG);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess && fi_out) e = hipMemcpy(fi_out, r->dGi, Lq * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && fij_out) e = hipMemcpy(fij_out, dG, nij * sizeof(double), hipMemcpyDeviceToHost);
-    dca_dev_free(dG);
-    if (e != hipSuccess) { dca_set_error("dca_plm_bm_freqs: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    static const char* who = "dca_plm_bm_freqs";
+    DevBuf<double> dG;
+    HIP_TRY(dG.alloc(std::max<size_t>(nij, 1), false));
+    HIP_TRY_AS((r->dtype == DCA_F32 ? bm_stats<float, false>(ctx, r, r->ch, nullptr, 0, r->dGi, dG)
+                                    : bm_stats<double, false>(ctx, r, r->ch, nullptr, 0, r->dGi, dG)), who);
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
+    if (fi_out) HIP_TRY_AS(hipMemcpy(fi_out, r->dGi, Lq * sizeof(double), hipMemcpyDeviceToHost), who);
+    if (fij_out) HIP_TRY_AS(hipMemcpy(fij_out, dG, nij * sizeof(double), hipMemcpyDeviceToHost), who);
     return DCA_OK;
 }
 

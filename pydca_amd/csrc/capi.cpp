@@ -45,12 +45,21 @@ struct DevPool {
 };
 DevPool& pool() { static DevPool* p = new DevPool(); return *p; }   // never destroyed: the HIP runtime may be gone at exit
 constexpr size_t kPoolMinBytes = (size_t)1 << 20;
+std::atomic<size_t> g_blocksInUse{0};      // handed out by dca_dev_malloc, not yet given to dca_dev_free (dca_device_blocks_in_use)
+hipError_t pool_malloc(void** out, size_t bytes, bool zero_recycled);
 }  // namespace
 
 hipError_t dca_dev_malloc(void** out, size_t bytes, bool zero_recycled)
 {
     *out = nullptr;
-    if (bytes < kPoolMinBytes) return hipMalloc(out, bytes);
+    const hipError_t e = bytes < kPoolMinBytes ? hipMalloc(out, bytes) : pool_malloc(out, bytes, zero_recycled);
+    if (e == hipSuccess) g_blocksInUse.fetch_add(1, std::memory_order_relaxed);
+    return e;
+}
+
+namespace {
+hipError_t pool_malloc(void** out, size_t bytes, bool zero_recycled)
+{
     int dev = 0;
     hipGetDevice(&dev);
     DevPool& P = pool();
@@ -92,10 +101,12 @@ hipError_t dca_dev_malloc(void** out, size_t bytes, bool zero_recycled)
     P.live[*out] = DevBlock{*out, bytes, dev};
     return hipSuccess;
 }
+}  // namespace
 
 hipError_t dca_dev_free(void* p)
 {
     if (!p) return hipSuccess;
+    g_blocksInUse.fetch_sub(1, std::memory_order_relaxed);
     DevPool& P = pool();
     DevBlock b{nullptr, 0, 0};
     {
@@ -170,6 +181,8 @@ size_t dca_release_cached_memory(void)
     return n;
 }
 
+size_t dca_device_blocks_in_use(void) { return g_blocksInUse.load(std::memory_order_relaxed); }
+
 int dca_device_count(void)
 {
     int n = 0;
@@ -218,8 +231,8 @@ int dca_create(dca_ctx** out, int device, int precision)
     ctx->device = device;
     ctx->precision = precision;
     hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&ctx->dScal), 64 * sizeof(double));
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&ctx->hScal), 64 * sizeof(double), hipHostMallocDefault);
+    if (e == hipSuccess) e = dca_dev_alloc(&ctx->dScal, 64);
+    if (e == hipSuccess) e = hipHostMalloc(&ctx->hScal, 64 * sizeof(double), hipHostMallocDefault);
     if (e != hipSuccess) {                       // nothing half-built is handed out or left behind
         dca_set_error("dca_create: %s", hipGetErrorString(e));
         dca_destroy(ctx);
@@ -249,14 +262,13 @@ const uint8_t* dca_host_msa(dca_ctx* ctx)
 {
     if (ctx->hX.empty() && ctx->dX) {
         ctx->hX.resize((size_t)ctx->N * ctx->L);
-        uint8_t* dTmp = nullptr;
-        hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dTmp), ctx->hX.size());
+        DevBuf<uint8_t> dTmp;
+        hipError_t e = dTmp.alloc(ctx->hX.size());
         if (e == hipSuccess) {
             hipLaunchKernelGGL(unpad_rows_kernel, dim3((unsigned)((ctx->hX.size() + 255) / 256)), dim3(256), 0, ctx->stream,
-                               ctx->dX, dTmp, ctx->N, ctx->L, ctx->Ls);
+                               ctx->dX, dTmp.get(), ctx->N, ctx->L, ctx->Ls);
             e = hipStreamSynchronize(ctx->stream);
             if (e == hipSuccess) e = hipMemcpy(ctx->hX.data(), dTmp, ctx->hX.size(), hipMemcpyDeviceToHost);
-            dca_dev_free(dTmp);
         }
         if (e != hipSuccess) {
             ctx->hX.clear();
@@ -271,7 +283,7 @@ int dca_remember_scores(dca_ctx* ctx, const double* dScores, int n)
 {
     if (ctx->nLastScores != n) {
         dca_dev_free(ctx->dLastScores); ctx->dLastScores = nullptr; ctx->nLastScores = 0;
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&ctx->dLastScores), (size_t)n * sizeof(double)));
+        HIP_TRY(dca_dev_alloc(&ctx->dLastScores, (size_t)n));
         ctx->nLastScores = n;
     }
     HIP_TRY(hipMemcpyAsync(ctx->dLastScores, dScores, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -304,22 +316,22 @@ int dca_set_msa(dca_ctx* ctx, const uint8_t* X, int N, int L, int q)
     const int Ls = (int)round_up((size_t)L, 128);
     ctx->hX.clear();                                       // host copy is made on demand (dca_host_msa)
     // one contiguous copy + a repack kernel (a pitched hipMemcpy2D of narrow rows takes seconds)
-    uint8_t* dTmp = nullptr;
-    unsigned* dMax = nullptr;
+    DevBuf<uint8_t> dTmp;
+    DevBuf<unsigned> dMax;
     unsigned maxCode = 0;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&ctx->dX), (size_t)N * Ls);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dTmp), (size_t)N * L);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dMax), sizeof(unsigned));
+    hipError_t e = dca_dev_alloc(&ctx->dX, (size_t)N * Ls);
+    if (e == hipSuccess) e = dTmp.alloc((size_t)N * L);
+    if (e == hipSuccess) e = dMax.alloc(1);
     if (e == hipSuccess) e = hipMemsetAsync(dMax, 0, sizeof(unsigned), ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(dTmp, X, (size_t)N * L, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const size_t total = (size_t)N * Ls;
-        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dTmp, ctx->dX, N, L, Ls, dMax);
+        hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->stream, dTmp.get(), ctx->dX, N, L, Ls, dMax.get());
         e = hipMemcpyAsync(&maxCode, dMax, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     }
-    dca_dev_free(dTmp);
-    dca_dev_free(dMax);
+    dTmp.reset();
+    dMax.reset();
     if (e == hipSuccess && maxCode >= (unsigned)q) {      // the slow search only runs on failure
         size_t k = 0;
         while (X[k] < q) ++k;
@@ -327,8 +339,8 @@ int dca_set_msa(dca_ctx* ctx, const uint8_t* X, int N, int L, int q)
         dca_set_error("dca_set_msa: code %d >= q at element %zu", (int)X[k], k);
         return DCA_ERR_ARG;
     }
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&ctx->dCounts), (size_t)N * sizeof(uint32_t));
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&ctx->dWd), (size_t)N * sizeof(double));
+    if (e == hipSuccess) e = dca_dev_alloc(&ctx->dCounts, (size_t)N);
+    if (e == hipSuccess) e = dca_dev_alloc(&ctx->dWd, (size_t)N);
     if (e != hipSuccess) {
         free_msa(ctx);
         dca_set_error("uploading the alignment: %s", hipGetErrorString(e));
@@ -648,16 +660,9 @@ static int need_mf(dca_ctx* ctx)
 }
 // the mean-field model for the dca_potts_* calls; its device fields live until the call's stream work has drained
 struct MfPotts {
-    dca_ctx* ctx = nullptr;
     PottsSource ps{};
-    double* dH = nullptr;
-    int get(dca_ctx* c) { ctx = c; return dca_mf_engine_potts_source(c->mf, &ps, &dH); }
-    ~MfPotts()
-    {
-        if (!dH) return;
-        hipStreamSynchronize(ctx->stream);
-        dca_dev_free(dH);
-    }
+    DevBuf<double> dH;
+    int get(dca_ctx* c) { return dca_mf_engine_potts_source(c->mf, &ps, &dH); }
 };
 int dca_mf_single_site_freqs(dca_ctx* ctx, double* fi_out) { CHECK_CTX(ctx); DCA_TRY(need_mf(ctx)); return dca_mf_engine_site_freqs(ctx->mf, fi_out); }
 int dca_mf_pair_site_freqs(dca_ctx* ctx, double* fij_out) { CHECK_CTX(ctx); DCA_TRY(need_mf(ctx)); return dca_mf_engine_pair_freqs(ctx->mf, fij_out); }
@@ -750,17 +755,15 @@ int dca_comm_allgather_host(dca_ctx* ctx, const double* mine, int n, double* all
     if (!mine || !all || n <= 0) return DCA_ERR_ARG;
     if (!ctx->comm) { dca_set_error("no communicator: dca_comm_init first"); return DCA_ERR_STATE; }
     const size_t total = (size_t)n * ctx->comm_world;
-    double* d = nullptr;
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&d), total * sizeof(double)));
-    int rc = DCA_OK;
+    DevBuf<double> d;
+    HIP_TRY(d.alloc(total));
     // every rank contributes its values at its own offset of a zero vector: the sum IS the gathered vector (only sums are bound)
     if (hipMemsetAsync(d, 0, total * sizeof(double), ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(d + (size_t)n * ctx->comm_rank, mine, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = DCA_ERR_HIP;
-    if (rc == DCA_OK) rc = dca_comm_native(ctx, DCA_COMM_ALL_REDUCE, d, total, DCA_F64);
-    if (rc == DCA_OK && (hipMemcpyAsync(all, d, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-                         hipStreamSynchronize(ctx->stream) != hipSuccess)) rc = DCA_ERR_HIP;
-    dca_dev_free(d);
-    return rc;
+        hipMemcpyAsync(d + (size_t)n * ctx->comm_rank, mine, (size_t)n * sizeof(double), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return DCA_ERR_HIP;
+    DCA_TRY(dca_comm_native(ctx, DCA_COMM_ALL_REDUCE, d, total, DCA_F64));
+    if (hipMemcpyAsync(all, d, total * sizeof(double), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess) return DCA_ERR_HIP;
+    return DCA_OK;
 }
 int dca_mf_set_reduce_hook(dca_ctx* ctx, dca_reduce_hook hook, void* user)
 {
@@ -852,21 +855,17 @@ int dca_spd_inverse(dca_ctx* ctx, const double* A, int n, double* Ainv_out)
         for (int c = 0; c < r; ++c) padded[(size_t)c * np + r] = A[(size_t)r * n + c];
     }
     for (int r = n; r < np; ++r) padded[(size_t)r * np + r] = 1.0;
-    double *dA = nullptr, *dWork = nullptr;
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dA), padded.size() * sizeof(double)));
-    if (dca_dev_malloc(reinterpret_cast<void**>(&dWork), 2 * padded.size() * sizeof(double)) != hipSuccess) { dca_dev_free(dA); dca_set_error("out of device memory"); return DCA_ERR_NOMEM; }
+    DevBuf<double> dA, dWork;
+    HIP_TRY(dA.alloc(padded.size()));
+    if (dWork.alloc(2 * padded.size()) != hipSuccess) { dca_set_error("out of device memory"); return DCA_ERR_NOMEM; }
     int info = 0;
-    int rc = DCA_OK;
-    if (hipMemcpy(dA, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) rc = DCA_ERR_HIP;
+    if (hipMemcpy(dA, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return DCA_ERR_HIP;
     double* dInv = nullptr;
-    if (rc == DCA_OK) rc = dca_spd_inverse_device(ctx, dA, np, dWork, &info, 1.0, &dInv);
-    if (rc == DCA_OK && info != 0) { dca_set_error("matrix is not positive definite (pivot %d)", info); rc = DCA_ERR_NOT_SPD; }
-    if (rc == DCA_OK) {
-        if (hipMemcpy(padded.data(), dInv, padded.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) rc = DCA_ERR_HIP;
-        else for (int r = 0; r < n; ++r) memcpy(Ainv_out + (size_t)r * n, padded.data() + (size_t)r * np, (size_t)n * sizeof(double));
-    }
-    dca_dev_free(dA); dca_dev_free(dWork);
-    return rc;
+    DCA_TRY(dca_spd_inverse_device(ctx, dA, np, dWork, &info, 1.0, &dInv));
+    if (info != 0) { dca_set_error("matrix is not positive definite (pivot %d)", info); return DCA_ERR_NOT_SPD; }
+    if (hipMemcpy(padded.data(), dInv, padded.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return DCA_ERR_HIP;
+    for (int r = 0; r < n; ++r) memcpy(Ainv_out + (size_t)r * n, padded.data() + (size_t)r * np, (size_t)n * sizeof(double));
+    return DCA_OK;
 }
 
 // ------------------------------------------------------------------ timing

@@ -1537,8 +1537,8 @@ int dca_spd_inverse_device(dca_ctx* ctx, double* dA, int n, double* dWork, int* 
     if (n % 64 != 0 || n <= 0) { dca_set_error("dca_spd_inverse_device: n must be a positive multiple of 64"); return DCA_ERR_ARG; }
     DCA_TRY(gemm_kernels_prepare(ctx->device));
     ScopedKernelClock kc(ctx, "mf_inverse");
-    int* dInfo = nullptr;
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dInfo), sizeof(int)));
+    DevBuf<int> dInfo;
+    HIP_TRY(dInfo.alloc(1));
     HIP_TRY(hipMemsetAsync(dInfo, 0, sizeof(int), ctx->stream));
     Arena ws{dWork, (size_t)n * n};
     int rc;
@@ -1573,10 +1573,8 @@ int dca_spd_inverse_device(dca_ctx* ctx, double* dA, int n, double* dWork, int* 
         *result = out;
     }
     int info = 0;
-    hipError_t e = hipMemcpyAsync(&info, dInfo, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dca_dev_free(dInfo);
-    if (e != hipSuccess) { dca_set_error("cholinv: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    HIP_TRY_AS(hipMemcpyAsync(&info, dInfo, sizeof(int), hipMemcpyDeviceToHost, ctx->stream), "cholinv");
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), "cholinv");
     if (info_out) *info_out = info;
     return rc;
 }

@@ -26,21 +26,41 @@ void dca_set_error(const char* fmt, ...);
         }                                                                               \
     } while (0)
 
+// the message and code of a named entry: "<who>: <hipGetErrorString>", DCA_ERR_HIP; with nomem, hipErrorOutOfMemory becomes
+// "<who>: out of device memory", DCA_ERR_NOMEM
+#define HIP_TRY_AS_(expr, who, nomem)                                                                                     \
+    do {                                                                                                                  \
+        hipError_t _e = (expr);                                                                                           \
+        if ((nomem) && _e == hipErrorOutOfMemory) { dca_set_error("%s: out of device memory", who); return DCA_ERR_NOMEM; } \
+        if (_e != hipSuccess) { dca_set_error("%s: %s", who, hipGetErrorString(_e)); return DCA_ERR_HIP; }                 \
+    } while (0)
+#define HIP_TRY_AS(expr, who) HIP_TRY_AS_(expr, who, false)
+#define HIP_TRY_AS_NOMEM(expr, who) HIP_TRY_AS_(expr, who, true)
+
+#define HIP_PASS(expr) /* in a function that returns hipError_t */ \
+    do {                                                           \
+        hipError_t _e = (expr);                                    \
+        if (_e != hipSuccess) return _e;                           \
+    } while (0)
+
 #define DCA_TRY(expr)                  \
     do {                               \
         int _rc = (expr);              \
         if (_rc != DCA_OK) return _rc; \
     } while (0)
 
-// ---- capi.cpp : device allocations.  Blocks of at least 1 MiB go back to a process-wide, per-device cache
-// when they are freed and later requests of a similar size are served from it (zero-filled), because
-// hipMalloc / hipFree of GB-sized blocks costs tens of milliseconds per call on some hosts -- more than
-// the whole mfDCA chain.  dca_dev_free waits for the device like hipFree does.
-hipError_t dca_dev_malloc(void** p, size_t bytes, bool zero_recycled = true);   // false: buffers their first kernel overwrites completely
-hipError_t dca_dev_free(void* p);
+#include "dev_buf.h"
 
 static inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// rows per pass of the set entries (dca_hamming_nearest, dca_three_site_values): DCA_NN_PASS, read per call; 32768, at most 2^20
+static inline int dca_nn_pass_size()
+{
+    const char* e = getenv("DCA_NN_PASS");
+    const long v = e ? atol(e) : 0;
+    return v > 0 ? (int)(v < (1 << 20) ? v : 1 << 20) : 32768;
+}
 
 // number of XCDs on MI355X; workgroup b is observed to run on XCD b % 8
 // (used for L2 locality only, never for correctness)
@@ -128,6 +148,26 @@ const uint8_t* dca_host_msa(dca_ctx* ctx);
 int dca_remember_scores(dca_ctx* ctx, const double* dScores, int n);
 // rank.hip: indices of a device score vector in descending order, ties by ascending index (stable)
 int dca_scores_order_device(dca_ctx* ctx, const double* dScores, int n, int32_t* order_out /* host */);
+
+// n doubles computed on the device by compute(d) (an int (double*) that reports its own errors), copied to the host `out` once
+// the stream has drained.  A failing copy reads "<who>: ..."; with nomem_who a failing allocation reads "<nomem_who>: out of
+// device memory" and is DCA_ERR_NOMEM.
+template <class F>
+int dca_download_doubles(dca_ctx* ctx, size_t n, double* out, const char* who, F&& compute, const char* nomem_who = nullptr)
+{
+    DevBuf<double> d;
+    const hipError_t ea = d.alloc(n);
+    if (ea != hipSuccess && nomem_who) {
+        (void)hipGetLastError();
+        dca_set_error("%s: out of device memory", nomem_who);
+        return DCA_ERR_NOMEM;
+    }
+    HIP_TRY(ea);
+    DCA_TRY(compute(d.get()));
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
+    HIP_TRY_AS(hipMemcpy(out, d, n * sizeof(double), hipMemcpyDeviceToHost), who);
+    return DCA_OK;
+}
 
 // ---- weights.hip
 // part / parts: this context counts the tile pairs  t % parts == part  of the upper triangle (1 / parts of the N^2 L / 2
@@ -244,12 +284,11 @@ static __device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t 
 // the tag "sample"; with dBase (L x q device doubles) the sweeps draw from the AIS interpolation h0 + bk * (u - h0) instead
 // (beta unused).  dca_chains_read: the n x L rows to the host (synchronises).  Any nS that is a multiple of 64 works (ais.hip
 // uses multiples of 128, the energy kernels' stride).
-struct DcaChains { int n = 0, L = 0, nS = 0; uint8_t* dState = nullptr; };
+struct DcaChains { int n = 0, L = 0, nS = 0; DevBuf<uint8_t> dState; };
 int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial);
 int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const PottsSource& ps, int sweeps, uint64_t seed, uint64_t first_chain,
                       uint64_t first_sweep, double beta, const double* dBase = nullptr, double bk = 0.0);
 int dca_chains_read(dca_ctx* ctx, const DcaChains& ch, uint8_t* out);
-void dca_chains_free(DcaChains* ch);
 
 // ---- ais.hip : annealed importance sampling of log Z under the same sources (dca_plm_ais / dca_mf_ais; arguments checked here)
 int dca_potts_ais(dca_ctx* ctx, const PottsSource& ps, const dca_ais_args* args, double* log_weights_out, double* log_z0_out,
@@ -314,8 +353,8 @@ int dca_mf_engine_set_row_window(MfEngine*, int first, int count);   // count < 
 void dca_mf_engine_invalidate(MfEngine*);      // weights changed: counts, frequencies, C and J are recomputed on demand
 int dca_mf_engine_pair_couplings(MfEngine*, const int* pairs, int npairs, int shift, double* out);
 // the mean-field model as a Potts source: J = -inv(C), h = the fields of dca_mf_engine_fields in a device buffer allocated here
-// (*dH_owned; the caller frees it once the stream has drained)
-int dca_mf_engine_potts_source(MfEngine*, PottsSource* out, double** dH_owned);
+// (*dH_owned: it must outlive the use of the source)
+int dca_mf_engine_potts_source(MfEngine*, PottsSource* out, DevBuf<double>* dH_owned);
 // data statistics of a Boltzmann-learning run from this engine's weighted counts (dca_plm_bm_begin): device outputs
 // fi (L*q) = (1 - lambda) * f_i + lambda / q and fij (pairs*q*q, pair order, gap included) = (1 - lambda) * f_ij + lambda / q^2
 int dca_mf_engine_bm_freqs(MfEngine*, double lambda, double* dFi, double* dFij);

@@ -199,14 +199,6 @@ hipError_t launch_tiles(dca_ctx* ctx, const uint32_t* dPQ, const uint32_t* dPR, 
     return hipGetLastError();
 }
 
-// queries per pass: the scratch of a pass is its rows (L bytes each) and planes (Ls / 32 * PLP dwords each)
-int nn_pass_size()
-{
-    const char* e = getenv("DCA_NN_PASS");        // read per call, like DCA_AR_PASS
-    const long v = e ? atol(e) : 0;
-    return v > 0 ? (int)std::min<long>(v, 1 << 20) : 32768;
-}
-
 }  // namespace
 
 int dca_hamming_nearest_impl(dca_ctx* ctx, const uint8_t* Q, int nq, const uint8_t* R, int nr, bool skipSame, int32_t* dist_out,
@@ -224,51 +216,47 @@ int dca_hamming_nearest_impl(dca_ctx* ctx, const uint8_t* Q, int nq, const uint8
         dca_set_error("dca_hamming_nearest: %d x %d sequences are more than one launch holds; split the reference set", nq, nr);
         return DCA_ERR_ARG;
     }
-    const int pass = Q ? std::min(nq, nn_pass_size()) : nq;
-    uint8_t *dR = nullptr, *dQ = nullptr;
-    uint32_t *dPR = nullptr, *dPQ = nullptr;
-    unsigned long long *dKeys = nullptr, *dHist = nullptr;
-    int32_t* dOut = nullptr;
-    auto cleanup = [&]() { dca_dev_free(dR); dca_dev_free(dQ); dca_dev_free(dPR); dca_dev_free(dPQ); dca_dev_free(dKeys); dca_dev_free(dHist); dca_dev_free(dOut); };
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dPR), (size_t)nr * G * PLP * sizeof(uint32_t), false);
-    if (e == hipSuccess && R) e = dca_dev_malloc(reinterpret_cast<void**>(&dR), (size_t)nr * L, false);
-    if (e == hipSuccess && Q) e = dca_dev_malloc(reinterpret_cast<void**>(&dQ), (size_t)pass * L, false);
-    if (e == hipSuccess && Q) e = dca_dev_malloc(reinterpret_cast<void**>(&dPQ), (size_t)pass * G * PLP * sizeof(uint32_t), false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dKeys), (size_t)nq * sizeof(unsigned long long), false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dOut), (size_t)nq * 2 * sizeof(int32_t), false);
-    if (e == hipSuccess && hist_out) e = dca_dev_malloc(reinterpret_cast<void**>(&dHist), (size_t)(L + 1) * sizeof(unsigned long long), false);
-    if (e == hipSuccess && hist_out) e = hipMemsetAsync(dHist, 0, (size_t)(L + 1) * sizeof(unsigned long long), ctx->stream);
-    if (e == hipSuccess && R) e = hipMemcpyAsync(dR, R, (size_t)nr * L, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
+    const int pass = Q ? std::min(nq, dca_nn_pass_size()) : nq;
+    static const char* who = "dca_hamming_nearest";
+    DevBuf<uint8_t> dR, dQ;
+    DevBuf<uint32_t> dPR, dPQ;
+    DevBuf<unsigned long long> dKeys, dHist;
+    DevBuf<int32_t> dOut;
+    HIP_TRY_AS(dPR.alloc((size_t)nr * G * PLP, false), who);
+    if (R) HIP_TRY_AS(dR.alloc((size_t)nr * L, false), who);
+    if (Q) HIP_TRY_AS(dQ.alloc((size_t)pass * L, false), who);
+    if (Q) HIP_TRY_AS(dPQ.alloc((size_t)pass * G * PLP, false), who);
+    HIP_TRY_AS(dKeys.alloc((size_t)nq, false), who);
+    HIP_TRY_AS(dOut.alloc((size_t)nq * 2, false), who);
+    if (hist_out) HIP_TRY_AS(dHist.alloc((size_t)(L + 1), false), who);
+    if (hist_out) HIP_TRY_AS(hipMemsetAsync(dHist, 0, (size_t)(L + 1) * sizeof(unsigned long long), ctx->stream), who);
+    if (R) HIP_TRY_AS(hipMemcpyAsync(dR, R, (size_t)nr * L, hipMemcpyHostToDevice, ctx->stream), who);
+    {
         ScopedKernelClock kc(ctx, "hamming");
-        hipLaunchKernelGGL(nn_fill_keys_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, dKeys, nq);
-        const uint8_t* rows = R ? dR : ctx->dX;
+        hipLaunchKernelGGL(nn_fill_keys_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, dKeys.get(), nq);
+        const uint8_t* rows = R ? dR.get() : ctx->dX;
         const size_t stride = R ? (size_t)L : (size_t)ctx->Ls;
-        e = small ? launch_planes<3>(ctx, rows, stride, nr, dPR) : launch_planes<5>(ctx, rows, stride, nr, dPR);
+        HIP_TRY_AS(small ? launch_planes<3>(ctx, rows, stride, nr, dPR) : launch_planes<5>(ctx, rows, stride, nr, dPR), who);
     }
     // the passes: queries [k0, k0 + n) against the whole reference set; a query's key sees the same pairs whatever the split
-    for (int k0 = 0; k0 < nq && e == hipSuccess; k0 += pass) {
+    for (int k0 = 0; k0 < nq; k0 += pass) {
         const int n = std::min(pass, nq - k0);
-        if (Q) e = hipMemcpyAsync(dQ, Q + (size_t)k0 * L, (size_t)n * L, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) break;
+        if (Q) HIP_TRY_AS(hipMemcpyAsync(dQ, Q + (size_t)k0 * L, (size_t)n * L, hipMemcpyHostToDevice, ctx->stream), who);
         ScopedKernelClock kc(ctx, "hamming");
-        if (Q) e = small ? launch_planes<3>(ctx, dQ, (size_t)L, n, dPQ) : launch_planes<5>(ctx, dQ, (size_t)L, n, dPQ);
-        if (e != hipSuccess) break;
-        const uint32_t* pq = Q ? dPQ : dPR;
-        e = small ? launch_tiles<3>(ctx, pq, dPR, n, nr, k0, skipSame, dKeys + k0, dHist)
-                  : launch_tiles<5>(ctx, pq, dPR, n, nr, k0, skipSame, dKeys + k0, dHist);
-        if (e == hipSuccess && Q && k0 + pass < nq) e = hipStreamSynchronize(ctx->stream);       // the next pass refills dQ / dPQ
+        if (Q) HIP_TRY_AS(small ? launch_planes<3>(ctx, dQ, (size_t)L, n, dPQ) : launch_planes<5>(ctx, dQ, (size_t)L, n, dPQ), who);
+        const uint32_t* pq = Q ? dPQ.get() : dPR.get();
+        HIP_TRY_AS(small ? launch_tiles<3>(ctx, pq, dPR, n, nr, k0, skipSame, dKeys + k0, dHist)
+                         : launch_tiles<5>(ctx, pq, dPR, n, nr, k0, skipSame, dKeys + k0, dHist), who);
+        if (Q && k0 + pass < nq) HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);       // the next pass refills dQ / dPQ
     }
-    if (e == hipSuccess) {
+    {
         ScopedKernelClock kc(ctx, "hamming");
-        hipLaunchKernelGGL(nn_unpack_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, dKeys, dOut, dOut + nq, nq);
-        e = hipGetLastError();
+        hipLaunchKernelGGL(nn_unpack_kernel, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, dKeys.get(), dOut.get(), dOut + nq, nq);
+        HIP_TRY_AS(hipGetLastError(), who);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(dist_out, dOut, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && index_out) e = hipMemcpy(index_out, dOut + nq, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && hist_out) e = hipMemcpy(hist_out, dHist, (size_t)(L + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) { dca_set_error("dca_hamming_nearest: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
+    HIP_TRY_AS(hipMemcpy(dist_out, dOut, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost), who);
+    if (index_out) HIP_TRY_AS(hipMemcpy(index_out, dOut + nq, (size_t)nq * sizeof(int32_t), hipMemcpyDeviceToHost), who);
+    if (hist_out) HIP_TRY_AS(hipMemcpy(hist_out, dHist, (size_t)(L + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost), who);
     return DCA_OK;
 }

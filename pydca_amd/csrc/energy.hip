@@ -169,31 +169,26 @@ int energies_t(dca_ctx* ctx, const PottsView<S>& pv, const uint8_t* X, int n, do
     const EnergyGeom eg = energy_geometry(L, pv.q, sizeof(S));
     const int cap = std::min(n, kEChunk);
     const int NqS = (int)round_up((size_t)cap, 128);
-    uint8_t *dRows = nullptr, *dQT = nullptr;
-    double *dSlabs = nullptr, *dOut = nullptr;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)cap * L, false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dQT), (size_t)L * NqS, false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dSlabs), (size_t)eg.G * NqS * sizeof(double), false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dOut), (size_t)NqS * sizeof(double), false);
-    for (int first = 0; first < n && e == hipSuccess; first += cap) {
+    DevBuf<uint8_t> dRows, dQT;
+    DevBuf<double> dSlabs, dOut;
+    HIP_TRY_AS(dRows.alloc((size_t)cap * L, false), "energies");
+    HIP_TRY_AS(dQT.alloc((size_t)L * NqS, false), "energies");
+    HIP_TRY_AS(dSlabs.alloc((size_t)eg.G * NqS, false), "energies");
+    HIP_TRY_AS(dOut.alloc((size_t)NqS, false), "energies");
+    for (int first = 0; first < n; first += cap) {
         const int nq = std::min(cap, n - first);
-        e = hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) break;
-        e = dca_rows_to_sites(ctx, dRows, (size_t)L, nq, L, NqS, dQT);
-        if (e != hipSuccess) break;
+        HIP_TRY_AS(hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream), "energies");
+        HIP_TRY_AS(dca_rows_to_sites(ctx, dRows, (size_t)L, nq, L, NqS, dQT), "energies");
         {
             ScopedKernelClock kc(ctx, "energies");
-            e = dispatch_pairs<S>(ctx, pv, dQT, nq, NqS, dSlabs);
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(energy_finish_kernel<S>, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, pv, dQT, nq, NqS, dSlabs,
-                                   eg.G, dOut);
+            HIP_TRY_AS(dispatch_pairs<S>(ctx, pv, dQT, nq, NqS, dSlabs), "energies");
+            hipLaunchKernelGGL(energy_finish_kernel<S>, dim3(ceil_div(nq, 256)), dim3(256), 0, ctx->stream, pv, dQT.get(), nq, NqS,
+                               dSlabs.get(), eg.G, dOut.get());
         }
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(out + first, dOut, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        HIP_TRY_AS(hipGetLastError(), "energies");
+        HIP_TRY_AS(hipMemcpyAsync(out + first, dOut, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "energies");
+        HIP_TRY_AS(hipStreamSynchronize(ctx->stream), "energies");
     }
-    dca_dev_free(dRows); dca_dev_free(dQT); dca_dev_free(dSlabs); dca_dev_free(dOut);
-    if (e != hipSuccess) { dca_set_error("energies: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
     return DCA_OK;
 }
 
@@ -201,20 +196,18 @@ template <typename S>
 int mutation_scan_t(dca_ctx* ctx, const PottsView<S>& pv, const uint8_t* wt, double* out)
 {
     const int L = pv.L, q = pv.q;
-    uint8_t* dWt = nullptr;
-    double* dOut = nullptr;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dWt), (size_t)L);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dOut), (size_t)L * q * sizeof(double), false);
-    if (e == hipSuccess) e = hipMemcpyAsync(dWt, wt, (size_t)L, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
+    DevBuf<uint8_t> dWt;
+    DevBuf<double> dOut;
+    HIP_TRY_AS(dWt.alloc((size_t)L), "mutation scan");
+    HIP_TRY_AS(dOut.alloc((size_t)L * q, false), "mutation scan");
+    HIP_TRY_AS(hipMemcpyAsync(dWt, wt, (size_t)L, hipMemcpyHostToDevice, ctx->stream), "mutation scan");
+    {
         ScopedKernelClock kc(ctx, "mutation_scan");
-        hipLaunchKernelGGL(mutation_scan_kernel<S>, dim3(L), dim3(64), 0, ctx->stream, pv, dWt, dOut);
-        e = hipGetLastError();
+        hipLaunchKernelGGL(mutation_scan_kernel<S>, dim3(L), dim3(64), 0, ctx->stream, pv, dWt.get(), dOut.get());
+        HIP_TRY_AS(hipGetLastError(), "mutation scan");
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dOut, (size_t)L * q * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dca_dev_free(dWt); dca_dev_free(dOut);
-    if (e != hipSuccess) { dca_set_error("mutation scan: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    HIP_TRY_AS(hipMemcpyAsync(out, dOut, (size_t)L * q * sizeof(double), hipMemcpyDeviceToHost, ctx->stream), "mutation scan");
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), "mutation scan");
     return DCA_OK;
 }
 

@@ -322,15 +322,15 @@ __global__ void mf_corr_from_freqs_kernel(const double* __restrict__ fi, const d
 struct MfEngine {
     dca_ctx* ctx;
     int N, L, q, Ls, Lq, n, np;
-    uint32_t* dPerm = nullptr;
-    int* dOff = nullptr;
-    uint8_t *dXT = nullptr, *dDom = nullptr;
-    double* dCnt1 = nullptr;
-    double *dCraw = nullptr, *dFi = nullptr, *dC = nullptr, *dJ = nullptr, *dWork = nullptr;
+    DevBuf<uint32_t> dPerm;
+    DevBuf<int> dOff;
+    DevBuf<uint8_t> dXT, dDom;
+    DevBuf<double> dCnt1, dCraw, dFi, dC, dWork;
+    double* dJ = nullptr;           // inside dWork
     bool have_counts = false, have_corr = false, have_J = false;
     bool corr_on_device = false;    // dC holds the correlation matrix (the factorisation of dca_mf_engine_couplings destroys it)
     double theta = 0.0;
-    double* dRegFi = nullptr;
+    DevBuf<double> dRegFi;
     dca_reduce_hook hook = nullptr;   // sequence sharding: sums Craw and Meff over the shards
     void* hook_user = nullptr;
     bool native_reduce = false;       // the same sum through ctx->comm (RCCL on the context's stream)
@@ -341,7 +341,6 @@ struct MfEngine {
     bool counts_global = false;       // the cached counts are the sum over all ranks' windows (= the whole alignment's)
     double meff = 0.0;                // Meff the frequencies are normalised by: ctx->meff (this context's weights) summed over
                                       // the shards when a hook / the native reduction is set; ctx->meff itself stays local
-    ~MfEngine() { dca_dev_free(dRegFi); dca_dev_free(dPerm); dca_dev_free(dOff); dca_dev_free(dXT); dca_dev_free(dDom); dca_dev_free(dCnt1); dca_dev_free(dCraw); dca_dev_free(dFi); dca_dev_free(dC); dca_dev_free(dWork); }
 };
 
 MfEngine* dca_make_mf_engine(dca_ctx* ctx)
@@ -367,13 +366,13 @@ static int mf_counts(MfEngine* m)
     const uint8_t* Xw = ctx->dX + (size_t)rowFirst * m->Ls;
     const double* Ww = ctx->dWd + rowFirst;
     if (!m->dPerm) {
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dPerm), (size_t)m->L * m->N * sizeof(uint32_t), false));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dOff), (size_t)m->L * (m->q + 1) * sizeof(int)));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dCraw), (size_t)m->Lq * m->Lq * sizeof(double), false));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dFi), (size_t)m->Lq * sizeof(double)));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dXT), (size_t)m->L * Nt, false));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dDom), (size_t)m->L));
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dCnt1), (size_t)m->Lq * sizeof(double)));
+        HIP_TRY(m->dPerm.alloc((size_t)m->L * m->N, false));
+        HIP_TRY(m->dOff.alloc((size_t)m->L * (m->q + 1)));
+        HIP_TRY(m->dCraw.alloc((size_t)m->Lq * m->Lq, false));
+        HIP_TRY(m->dFi.alloc((size_t)m->Lq));
+        HIP_TRY(m->dXT.alloc((size_t)m->L * Nt, false));
+        HIP_TRY(m->dDom.alloc((size_t)m->L));
+        HIP_TRY(m->dCnt1.alloc((size_t)m->Lq));
     }
     {
         ScopedKernelClock kc(ctx, "mf_sort");
@@ -432,14 +431,10 @@ int dca_mf_engine_pair_freqs(MfEngine* m, double* fij_out)
     DCA_TRY(mf_counts(m));
     const int qm = m->q - 1;
     const size_t total = (size_t)m->L * (m->L - 1) / 2 * qm * qm;
-    double* dOut = nullptr;
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dOut), total * sizeof(double)));
-    hipLaunchKernelGGL(mf_fij_export_kernel, dim3(m->L, m->L), dim3(64), 0, m->ctx->stream, m->dCraw, dOut, m->L, m->q, m->Lq, m->meff);
-    hipError_t e = hipStreamSynchronize(m->ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(fij_out, dOut, total * sizeof(double), hipMemcpyDeviceToHost);
-    dca_dev_free(dOut);
-    if (e != hipSuccess) { dca_set_error("pair freqs: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
-    return DCA_OK;
+    return dca_download_doubles(m->ctx, total, fij_out, "pair freqs", [&](double* dOut) {
+        hipLaunchKernelGGL(mf_fij_export_kernel, dim3(m->L, m->L), dim3(64), 0, m->ctx->stream, m->dCraw.get(), dOut, m->L, m->q, m->Lq, m->meff);
+        return DCA_OK;
+    });
 }
 
 int dca_mf_engine_bm_freqs(MfEngine* m, double lambda, double* dFi, double* dFij)
@@ -465,7 +460,7 @@ static int copy_out_square(MfEngine* m, const double* dSrc, double* out)
 static int mf_build_corr(MfEngine* m, double theta)
 {
     dca_ctx* ctx = m->ctx;
-    if (!m->dC) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dC), (size_t)m->np * m->np * sizeof(double), false));
+    if (!m->dC) HIP_TRY(m->dC.alloc((size_t)m->np * m->np, false));
     dim3 grid(ceil_div(m->np, 256), ceil_div(m->np, kCorrRows));
     if (m->q == 21) hipLaunchKernelGGL(mf_corr_kernel<21>, grid, dim3(256), 0, ctx->stream, m->dCraw, m->dFi, m->dC, m->L, m->q, m->Lq, m->np, m->meff, theta);
     else if (m->q == 5) hipLaunchKernelGGL(mf_corr_kernel<5>, grid, dim3(256), 0, ctx->stream, m->dCraw, m->dFi, m->dC, m->L, m->q, m->Lq, m->np, m->meff, theta);
@@ -494,7 +489,7 @@ int dca_mf_engine_couplings(MfEngine* m, double* out)
     // The factorisation runs in place on the correlation matrix (1.4 ms to rebuild from the counts if it is asked
     // for again) and leaves -inv(C) in the second half of the workspace: no copy in, no copy out, no negation pass.
     if (!m->corr_on_device) DCA_TRY(mf_build_corr(m, m->theta));
-    if (!m->dWork) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dWork), 2 * nn * sizeof(double), false));
+    if (!m->dWork) HIP_TRY(m->dWork.alloc(2 * nn, false));
     int info = 0;
     m->corr_on_device = false;
     m->have_J = false;
@@ -512,16 +507,8 @@ int dca_mf_engine_scores(MfEngine* m, int apc, double* out)
 {
     if (!m->have_J) { dca_set_error("dca_mf_couplings first"); return DCA_ERR_STATE; }
     const size_t npairs = (size_t)m->L * (m->L - 1) / 2;
-    double* dOut = nullptr;
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dOut), npairs * sizeof(double)));
-    int rc = dca_fn_scores(m->ctx, m->dJ, 1, DCA_F64, m->L, m->q, m->np, apc, dOut);
-    if (rc == DCA_OK) {
-        hipError_t e = hipStreamSynchronize(m->ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(out, dOut, npairs * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { dca_set_error("scores: %s", hipGetErrorString(e)); rc = DCA_ERR_HIP; }
-    }
-    dca_dev_free(dOut);
-    return rc;
+    return dca_download_doubles(m->ctx, npairs, out, "scores",
+                                [&](double* dOut) { return dca_fn_scores(m->ctx, m->dJ, 1, DCA_F64, m->L, m->q, m->np, apc, dOut); });
 }
 
 // stage API: construct_corr_mat on caller-provided regularised frequencies
@@ -531,25 +518,18 @@ extern "C" int dca_mf_corr_from_freqs(dca_ctx* ctx, const double* reg_fi, const 
     HIP_TRY(hipSetDevice(ctx->device));
     const int qm = q - 1, n = L * qm;
     const size_t nfij = (size_t)L * (L - 1) / 2 * qm * qm;
-    double *dFi = nullptr, *dFij = nullptr, *dC = nullptr;
-    int rc = DCA_OK;
-    if (dca_dev_malloc(reinterpret_cast<void**>(&dFi), (size_t)L * q * sizeof(double)) != hipSuccess ||
-        dca_dev_malloc(reinterpret_cast<void**>(&dFij), nfij * sizeof(double)) != hipSuccess ||
-        dca_dev_malloc(reinterpret_cast<void**>(&dC), (size_t)n * n * sizeof(double)) != hipSuccess) {
+    DevBuf<double> dFi, dFij, dC;
+    if (dFi.alloc((size_t)L * q) != hipSuccess || dFij.alloc(nfij) != hipSuccess || dC.alloc((size_t)n * n) != hipSuccess) {
         dca_set_error("out of device memory");
-        rc = DCA_ERR_NOMEM;
+        return DCA_ERR_NOMEM;
     }
-    if (rc == DCA_OK) {
-        hipMemcpy(dFi, reg_fi, (size_t)L * q * sizeof(double), hipMemcpyHostToDevice);
-        hipMemcpy(dFij, reg_fij, nfij * sizeof(double), hipMemcpyHostToDevice);
-        dim3 grid(ceil_div(n, 256), n);
-        hipLaunchKernelGGL(mf_corr_from_freqs_kernel, grid, dim3(256), 0, ctx->stream, dFi, dFij, dC, L, q);
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(corr_out, dC, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { dca_set_error("corr_from_freqs: %s", hipGetErrorString(e)); rc = DCA_ERR_HIP; }
-    }
-    dca_dev_free(dFi); dca_dev_free(dFij); dca_dev_free(dC);
-    return rc;
+    hipMemcpy(dFi, reg_fi, (size_t)L * q * sizeof(double), hipMemcpyHostToDevice);
+    hipMemcpy(dFij, reg_fij, nfij * sizeof(double), hipMemcpyHostToDevice);
+    dim3 grid(ceil_div(n, 256), n);
+    hipLaunchKernelGGL(mf_corr_from_freqs_kernel, grid, dim3(256), 0, ctx->stream, dFi.get(), dFij.get(), dC.get(), L, q);
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), "corr_from_freqs");
+    HIP_TRY_AS(hipMemcpy(corr_out, dC, (size_t)n * n * sizeof(double), hipMemcpyDeviceToHost), "corr_from_freqs");
+    return DCA_OK;
 }
 
 namespace {
@@ -566,19 +546,12 @@ int dca_mf_engine_di(MfEngine* m, int apc, double* out)
 {
     if (!m->have_J) { dca_set_error("dca_mf_couplings first"); return DCA_ERR_STATE; }
     dca_ctx* ctx = m->ctx;
-    if (!m->dRegFi) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dRegFi), (size_t)m->Lq * sizeof(double)));
+    if (!m->dRegFi) HIP_TRY(m->dRegFi.alloc((size_t)m->Lq));
     hipLaunchKernelGGL(mf_regfi_kernel, dim3(ceil_div(m->Lq, 256)), dim3(256), 0, ctx->stream, m->dFi, m->dRegFi, m->Lq, m->q, m->theta);
     const size_t npairs = (size_t)m->L * (m->L - 1) / 2;
-    double* dOut = nullptr;
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dOut), npairs * sizeof(double)));
-    int rc = dca_di_scores(ctx, m->dJ, 1, DCA_F64, m->dRegFi, m->L, m->q, m->np, apc, dOut);
-    if (rc == DCA_OK) {
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = hipMemcpy(out, dOut, npairs * sizeof(double), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) { dca_set_error("DI scores: %s", hipGetErrorString(e)); rc = DCA_ERR_HIP; }
-    }
-    dca_dev_free(dOut);
-    return rc;
+    return dca_download_doubles(ctx, npairs, out, "DI scores", [&](double* dOut) {
+        return dca_di_scores(ctx, m->dJ, 1, DCA_F64, m->dRegFi, m->L, m->q, m->np, apc, dOut);
+    });
 }
 
 namespace {
@@ -605,37 +578,35 @@ void mf_fields_kernel(const double* __restrict__ J, const double* __restrict__ r
 }
 }  // namespace
 
-// fields of the global model into a device buffer of L*(q-1) doubles (allocated here; the caller frees it)
-static int mf_fields_device(MfEngine* m, double** dOut)
+// fields of the global model into a device buffer of L*(q-1) doubles (allocated here)
+static int mf_fields_device(MfEngine* m, DevBuf<double>* dOut)
 {
-    *dOut = nullptr;
+    dOut->reset();
     if (!m->have_J) { dca_set_error("dca_mf_couplings first"); return DCA_ERR_STATE; }
     dca_ctx* ctx = m->ctx;
-    if (!m->dRegFi) HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&m->dRegFi), (size_t)m->Lq * sizeof(double)));
+    if (!m->dRegFi) HIP_TRY(m->dRegFi.alloc((size_t)m->Lq));
     hipLaunchKernelGGL(mf_regfi_kernel, dim3(ceil_div(m->Lq, 256)), dim3(256), 0, ctx->stream, m->dFi, m->dRegFi, m->Lq, m->q, m->theta);
     const int n = m->L * (m->q - 1);
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(dOut), (size_t)n * sizeof(double)));
-    hipLaunchKernelGGL(mf_fields_kernel, dim3(n), dim3(256), 0, ctx->stream, m->dJ, m->dRegFi, m->L, m->q, m->np, *dOut);
+    HIP_TRY(dOut->alloc((size_t)n));
+    hipLaunchKernelGGL(mf_fields_kernel, dim3(n), dim3(256), 0, ctx->stream, m->dJ, m->dRegFi.get(), m->L, m->q, m->np, dOut->get());
     return DCA_OK;
 }
 
 int dca_mf_engine_fields(MfEngine* m, double* out)
 {
-    double* dOut = nullptr;
+    DevBuf<double> dOut;
     DCA_TRY(mf_fields_device(m, &dOut));
     const int n = m->L * (m->q - 1);
-    hipError_t e = hipStreamSynchronize(m->ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(out, dOut, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-    dca_dev_free(dOut);
-    if (e != hipSuccess) { dca_set_error("fields: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    HIP_TRY_AS(hipStreamSynchronize(m->ctx->stream), "fields");
+    HIP_TRY_AS(hipMemcpy(out, dOut, (size_t)n * sizeof(double), hipMemcpyDeviceToHost), "fields");
     return DCA_OK;
 }
 
 // The mean-field model as a Potts source: J = dJ, h = the fields above, both zero on the gap state
-int dca_mf_engine_potts_source(MfEngine* m, PottsSource* out, double** dH_owned)
+int dca_mf_engine_potts_source(MfEngine* m, PottsSource* out, DevBuf<double>* dH_owned)
 {
     DCA_TRY(mf_fields_device(m, dH_owned));
-    *out = PottsSource{m->dJ, 1, DCA_F64, *dH_owned, m->L, m->q, m->np};
+    *out = PottsSource{m->dJ, 1, DCA_F64, dH_owned->get(), m->L, m->q, m->np};
     return DCA_OK;
 }
 

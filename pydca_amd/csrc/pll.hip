@@ -111,34 +111,32 @@ hipError_t dca_site_passes(dca_ctx* ctx, const SitePasses& sp, int L, int q, con
                           (cond_out ? (size_t)L * q * sizeof(double) : 0);
     const int cap = site_pass_size(n, perSeq, sp.budget, sp.env, sp.granule);
     const int NqS = (int)round_up((size_t)cap, kSiteSeqBlock);
-    uint8_t *dRows = nullptr, *dQT = nullptr;
-    double *dSite = nullptr, *dSum = nullptr, *dSiteRows = nullptr, *dCond = nullptr;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)cap * L, false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dQT), (size_t)L * NqS, false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dSite), (size_t)L * NqS * sizeof(double), false);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dSum), (size_t)NqS * sizeof(double), false);
-    if (e == hipSuccess && site_out) e = dca_dev_malloc(reinterpret_cast<void**>(&dSiteRows), (size_t)cap * L * sizeof(double), false);
-    if (e == hipSuccess && cond_out) e = dca_dev_malloc(reinterpret_cast<void**>(&dCond), (size_t)cap * L * q * sizeof(double), false);
-    for (int first = 0; first < n && e == hipSuccess; first += cap) {
+    DevBuf<uint8_t> dRows, dQT;
+    DevBuf<double> dSite, dSum, dSiteRows, dCond;
+    HIP_PASS(dRows.alloc((size_t)cap * L, false));
+    HIP_PASS(dQT.alloc((size_t)L * NqS, false));
+    HIP_PASS(dSite.alloc((size_t)L * NqS, false));
+    HIP_PASS(dSum.alloc((size_t)NqS, false));
+    if (site_out) HIP_PASS(dSiteRows.alloc((size_t)cap * L, false));
+    if (cond_out) HIP_PASS(dCond.alloc((size_t)cap * L * q, false));
+    for (int first = 0; first < n; first += cap) {
         const int nq = std::min(cap, n - first);
-        e = hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = dca_rows_to_sites(ctx, dRows, (size_t)L, nq, L, NqS, dQT);
-        if (e != hipSuccess) break;
+        HIP_PASS(hipMemcpyAsync(dRows, X + (size_t)first * L, (size_t)nq * L, hipMemcpyHostToDevice, ctx->stream));
+        HIP_PASS(dca_rows_to_sites(ctx, dRows, (size_t)L, nq, L, NqS, dQT));
         {
             ScopedKernelClock kc(ctx, sp.tag);
-            e = launch(dQT, nq, NqS, dSite, dCond);
-            if (e == hipSuccess) e = dca_site_finish(ctx, dSite, L, nq, NqS, dSum, dSiteRows);
+            HIP_PASS(launch(dQT, nq, NqS, dSite, dCond));
+            HIP_PASS(dca_site_finish(ctx, dSite, L, nq, NqS, dSum, dSiteRows));
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(sum_out + first, dSum, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && site_out)
-            e = hipMemcpyAsync(site_out + (size_t)first * L, dSiteRows, (size_t)nq * L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && cond_out)
-            e = hipMemcpyAsync(cond_out + (size_t)first * L * q, dCond, (size_t)nq * L * q * sizeof(double), hipMemcpyDeviceToHost,
-                               ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        HIP_PASS(hipMemcpyAsync(sum_out + first, dSum, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (site_out)
+            HIP_PASS(hipMemcpyAsync(site_out + (size_t)first * L, dSiteRows, (size_t)nq * L * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (cond_out)
+            HIP_PASS(hipMemcpyAsync(cond_out + (size_t)first * L * q, dCond, (size_t)nq * L * q * sizeof(double), hipMemcpyDeviceToHost,
+                                    ctx->stream));
+        HIP_PASS(hipStreamSynchronize(ctx->stream));
     }
-    dca_dev_free(dRows); dca_dev_free(dQT); dca_dev_free(dSite); dca_dev_free(dSum); dca_dev_free(dSiteRows); dca_dev_free(dCond);
-    return e;
+    return hipSuccess;
 }
 
 int dca_potts_pseudo_likelihood(dca_ctx* ctx, const PottsSource& ps, const uint8_t* X, int n, double* pll_out, double* site_out,

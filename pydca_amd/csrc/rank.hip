@@ -20,23 +20,21 @@ __global__ void iota_kernel(int32_t* v, int n)
 int dca_scores_order_device(dca_ctx* ctx, const double* dScores, int n, int32_t* order_out)
 {
     if (n <= 0) return DCA_OK;
-    double* dKeysOut = nullptr;
-    int32_t *dIdx = nullptr, *dIdxOut = nullptr;
-    void* dTemp = nullptr;
+    static const char* who = "ranking scores";
+    DevBuf<double> dKeysOut;
+    DevBuf<int32_t> dIdx, dIdxOut;
+    DevBuf<char> dTemp;
     size_t tempBytes = 0;
-    int rc = DCA_OK;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dKeysOut), (size_t)n * sizeof(double));
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dIdx), (size_t)n * sizeof(int32_t));
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dIdxOut), (size_t)n * sizeof(int32_t));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, ctx->stream, dIdx, n);
-        e = rocprim::radix_sort_pairs_desc(nullptr, tempBytes, dScores, dKeysOut, dIdx, dIdxOut, (size_t)n, 0, 64, ctx->stream);
-    }
-    if (e == hipSuccess) e = dca_dev_malloc(&dTemp, std::max<size_t>(tempBytes, 16));
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs_desc(dTemp, tempBytes, dScores, dKeysOut, dIdx, dIdxOut, (size_t)n, 0, 64, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e == hipSuccess) e = hipMemcpy(order_out, dIdxOut, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { dca_set_error("ranking scores: %s", hipGetErrorString(e)); rc = DCA_ERR_HIP; }
-    dca_dev_free(dKeysOut); dca_dev_free(dIdx); dca_dev_free(dIdxOut); dca_dev_free(dTemp);
-    return rc;
+    HIP_TRY_AS(dKeysOut.alloc((size_t)n), who);
+    HIP_TRY_AS(dIdx.alloc((size_t)n), who);
+    HIP_TRY_AS(dIdxOut.alloc((size_t)n), who);
+    hipLaunchKernelGGL(iota_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, ctx->stream, dIdx.get(), n);
+    HIP_TRY_AS(rocprim::radix_sort_pairs_desc(nullptr, tempBytes, dScores, dKeysOut.get(), dIdx.get(), dIdxOut.get(), (size_t)n, 0, 64,
+                                              ctx->stream), who);
+    HIP_TRY_AS(dTemp.alloc(std::max<size_t>(tempBytes, 16)), who);
+    HIP_TRY_AS(rocprim::radix_sort_pairs_desc(dTemp.get(), tempBytes, dScores, dKeysOut.get(), dIdx.get(), dIdxOut.get(), (size_t)n, 0, 64,
+                                              ctx->stream), who);
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
+    HIP_TRY_AS(hipMemcpy(order_out, dIdxOut, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost), who);
+    return DCA_OK;
 }

@@ -269,25 +269,21 @@ hipError_t dca_sites_to_rows(dca_ctx* ctx, const uint8_t* dSites, int n, int L, 
 // ---- device-resident chains (dca_internal.h): the sampler's state between calls
 int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial)
 {
-    dca_chains_free(ch);
+    *ch = DcaChains();
     ch->n = n; ch->L = L;
     ch->nS = (int)round_up((size_t)n, kSChains);
     const size_t sites = (size_t)L * ch->nS;
-    uint8_t* dRows = nullptr;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&ch->dState), sites, false);
-    if (e == hipSuccess) {
-        if (initial) {
-            e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), (size_t)n * L, false);
-            if (e == hipSuccess) e = hipMemcpyAsync(dRows, initial, (size_t)n * L, hipMemcpyHostToDevice, ctx->stream);
-            if (e == hipSuccess) e = dca_rows_to_sites(ctx, dRows, (size_t)L, n, L, ch->nS, ch->dState);
-        } else {
-            hipLaunchKernelGGL(initial_state_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, n, L, q, ch->nS, seed,
-                               first_chain, ch->dState);
-        }
-        if (e == hipSuccess) e = hipGetLastError();
+    DevBuf<uint8_t> dRows;
+    HIP_TRY_AS(ch->dState.alloc(sites, false), "sample");
+    if (initial) {
+        HIP_TRY_AS(dRows.alloc((size_t)n * L, false), "sample");
+        HIP_TRY_AS(hipMemcpyAsync(dRows, initial, (size_t)n * L, hipMemcpyHostToDevice, ctx->stream), "sample");
+        HIP_TRY_AS(dca_rows_to_sites(ctx, dRows, (size_t)L, n, L, ch->nS, ch->dState), "sample");
+    } else {
+        hipLaunchKernelGGL(initial_state_kernel, dim3((unsigned)((sites + 255) / 256)), dim3(256), 0, ctx->stream, n, L, q, ch->nS, seed,
+                           first_chain, ch->dState.get());
     }
-    dca_dev_free(dRows);
-    if (e != hipSuccess) { dca_chains_free(ch); dca_set_error("sample: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    HIP_TRY_AS(hipGetLastError(), "sample");
     return DCA_OK;
 }
 
@@ -310,20 +306,12 @@ int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const PottsSource& ps, 
 int dca_chains_read(dca_ctx* ctx, const DcaChains& ch, uint8_t* out)
 {
     const size_t total = (size_t)ch.n * ch.L;
-    uint8_t* dRows = nullptr;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dRows), total, false);
-    if (e == hipSuccess) e = dca_sites_to_rows(ctx, ch.dState, ch.n, ch.L, ch.nS, dRows);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dRows, total, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    dca_dev_free(dRows);
-    if (e != hipSuccess) { dca_set_error("sample: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    DevBuf<uint8_t> dRows;
+    HIP_TRY_AS(dRows.alloc(total, false), "sample");
+    HIP_TRY_AS(dca_sites_to_rows(ctx, ch.dState, ch.n, ch.L, ch.nS, dRows), "sample");
+    HIP_TRY_AS(hipMemcpyAsync(out, dRows, total, hipMemcpyDeviceToHost, ctx->stream), "sample");
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), "sample");
     return DCA_OK;
-}
-
-void dca_chains_free(DcaChains* ch)
-{
-    dca_dev_free(ch->dState);
-    *ch = DcaChains();
 }
 
 int dca_potts_sample(dca_ctx* ctx, const PottsSource& ps, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep,
@@ -336,11 +324,9 @@ int dca_potts_sample(dca_ctx* ctx, const PottsSource& ps, int n, int sweeps, uin
     if (n == 0) return DCA_OK;
     if (initial) DCA_TRY(dca_check_codes(initial, (size_t)n * ps.L, ps.q, "sample: initial "));
     DcaChains ch;
-    int rc = dca_chains_start(ctx, &ch, n, ps.L, ps.q, seed, first_chain, initial);
-    if (rc == DCA_OK) rc = dca_chains_sweeps(ctx, ch, ps, sweeps, seed, first_chain, first_sweep, beta);
-    if (rc == DCA_OK) rc = dca_chains_read(ctx, ch, out);
-    dca_chains_free(&ch);
-    return rc;
+    DCA_TRY(dca_chains_start(ctx, &ch, n, ps.L, ps.q, seed, first_chain, initial));
+    DCA_TRY(dca_chains_sweeps(ctx, ch, ps, sweeps, seed, first_chain, first_sweep, beta));
+    return dca_chains_read(ctx, ch, out);
 }
 
 int dca_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])

@@ -247,6 +247,18 @@ void pair_blocks_kernel(const S* __restrict__ src, int kind, const int* __restri
     }
 }
 
+// the average-product correction of the pair-ordered scores, in place
+int apc_correct(dca_ctx* ctx, double* dScores, int L)
+{
+    DevBuf<double> dAv;
+    HIP_TRY(dAv.alloc((size_t)(L + 1)));
+    hipLaunchKernelGGL(apc_site_kernel, dim3(L), dim3(256), 0, ctx->stream, dScores, L, dAv.get());
+    hipLaunchKernelGGL(apc_mean_kernel, dim3(1), dim3(256), 0, ctx->stream, dAv.get(), L, dAv + L);
+    hipLaunchKernelGGL(apc_apply_kernel, dim3(L - 1), dim3(256), 0, ctx->stream, dScores, dAv.get(), dAv + L, L);
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), "apc");
+    return DCA_OK;
+}
+
 }  // namespace
 
 int dca_fn_scores(dca_ctx* ctx, const void* src, int src_kind, int dtype, int L, int q, int ld, int apc, double* dOut)
@@ -259,16 +271,7 @@ int dca_fn_scores(dca_ctx* ctx, const void* src, int src_kind, int dtype, int L,
         hipLaunchKernelGGL(fn_kernel<float>, dim3((unsigned)npairs), dim3(64), lds, ctx->stream, static_cast<const float*>(src), src_kind, L, q, ld, dOut);
     else
         hipLaunchKernelGGL(fn_kernel<double>, dim3((unsigned)npairs), dim3(64), lds, ctx->stream, static_cast<const double*>(src), src_kind, L, q, ld, dOut);
-    if (apc) {
-        double* dAv = nullptr;
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dAv), (size_t)(L + 1) * sizeof(double)));
-        hipLaunchKernelGGL(apc_site_kernel, dim3(L), dim3(256), 0, ctx->stream, dOut, L, dAv);
-        hipLaunchKernelGGL(apc_mean_kernel, dim3(1), dim3(256), 0, ctx->stream, dAv, L, dAv + L);
-        hipLaunchKernelGGL(apc_apply_kernel, dim3(L - 1), dim3(256), 0, ctx->stream, dOut, dAv, dAv + L, L);
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        dca_dev_free(dAv);
-        if (e != hipSuccess) { dca_set_error("apc: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
-    }
+    if (apc) DCA_TRY(apc_correct(ctx, dOut, L));
     HIP_TRY(hipGetLastError());
     return dca_remember_scores(ctx, dOut, (int)npairs);
 }
@@ -284,16 +287,7 @@ int dca_di_scores(dca_ctx* ctx, const void* src, int src_kind, int dtype, const 
         hipLaunchKernelGGL(di_kernel<float>, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, static_cast<const float*>(src), src_kind, dRegFi, L, q, ld, dOut, static_cast<double*>(nullptr), static_cast<const double*>(nullptr));
     else
         hipLaunchKernelGGL(di_kernel<double>, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, static_cast<const double*>(src), src_kind, dRegFi, L, q, ld, dOut, static_cast<double*>(nullptr), static_cast<const double*>(nullptr));
-    if (apc) {
-        double* dAv = nullptr;
-        HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dAv), (size_t)(L + 1) * sizeof(double)));
-        hipLaunchKernelGGL(apc_site_kernel, dim3(L), dim3(256), 0, ctx->stream, dOut, L, dAv);
-        hipLaunchKernelGGL(apc_mean_kernel, dim3(1), dim3(256), 0, ctx->stream, dAv, L, dAv + L);
-        hipLaunchKernelGGL(apc_apply_kernel, dim3(L - 1), dim3(256), 0, ctx->stream, dOut, dAv, dAv + L, L);
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        dca_dev_free(dAv);
-        if (e != hipSuccess) { dca_set_error("apc: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
-    }
+    if (apc) DCA_TRY(apc_correct(ctx, dOut, L));
     HIP_TRY(hipGetLastError());
     return dca_remember_scores(ctx, dOut, (int)npairs);
 }
@@ -307,21 +301,17 @@ int dca_pair_blocks(dca_ctx* ctx, const void* src, int src_kind, int dtype, int 
     for (int k = 0; k < npairs; ++k)
         if (pairs[2 * k] < 0 || pairs[2 * k] >= pairs[2 * k + 1] || pairs[2 * k + 1] >= L) { dca_set_error("site pair %d out of order or range", k); return DCA_ERR_ARG; }
     const size_t per = (size_t)(q - 1) * (q - 1);
-    int* dPairs = nullptr;
-    double* dOut = nullptr;
-    HIP_TRY(dca_dev_malloc(reinterpret_cast<void**>(&dPairs), (size_t)npairs * 2 * sizeof(int)));
-    if (dca_dev_malloc(reinterpret_cast<void**>(&dOut), (size_t)npairs * per * sizeof(double)) != hipSuccess) { dca_dev_free(dPairs); return DCA_ERR_NOMEM; }
-    hipError_t e = hipMemcpyAsync(dPairs, pairs, (size_t)npairs * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-        if (dtype == DCA_F32)
-            hipLaunchKernelGGL(pair_blocks_kernel<float>, dim3(npairs), dim3(64), 0, ctx->stream, static_cast<const float*>(src), src_kind, dPairs, L, q, ld, shift, dOut);
-        else
-            hipLaunchKernelGGL(pair_blocks_kernel<double>, dim3(npairs), dim3(64), 0, ctx->stream, static_cast<const double*>(src), src_kind, dPairs, L, q, ld, shift, dOut);
-        e = hipStreamSynchronize(ctx->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, dOut, (size_t)npairs * per * sizeof(double), hipMemcpyDeviceToHost);
-    dca_dev_free(dPairs); dca_dev_free(dOut);
-    if (e != hipSuccess) { dca_set_error("pair blocks: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    DevBuf<int> dPairs;
+    DevBuf<double> dOut;
+    HIP_TRY(dPairs.alloc((size_t)npairs * 2));
+    if (dOut.alloc((size_t)npairs * per) != hipSuccess) { dca_set_error("pair blocks: out of device memory"); return DCA_ERR_NOMEM; }
+    HIP_TRY_AS(hipMemcpyAsync(dPairs, pairs, (size_t)npairs * 2 * sizeof(int), hipMemcpyHostToDevice, ctx->stream), "pair blocks");
+    if (dtype == DCA_F32)
+        hipLaunchKernelGGL(pair_blocks_kernel<float>, dim3(npairs), dim3(64), 0, ctx->stream, static_cast<const float*>(src), src_kind, dPairs.get(), L, q, ld, shift, dOut.get());
+    else
+        hipLaunchKernelGGL(pair_blocks_kernel<double>, dim3(npairs), dim3(64), 0, ctx->stream, static_cast<const double*>(src), src_kind, dPairs.get(), L, q, ld, shift, dOut.get());
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), "pair blocks");
+    HIP_TRY_AS(hipMemcpy(out, dOut, (size_t)npairs * per * sizeof(double), hipMemcpyDeviceToHost), "pair blocks");
     return DCA_OK;
 }
 
@@ -335,22 +325,20 @@ int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, c
     const int qm = q - 1, n = L * qm;
     const size_t npairs = (size_t)L * (L - 1) / 2;
     const size_t nc = layout == 1 ? (size_t)n * n : npairs * qm * qm;
-    double *dC = nullptr, *dF = nullptr, *dDi = nullptr, *dFields = nullptr, *dFieldsIn = nullptr;
-    hipError_t e = dca_dev_malloc(reinterpret_cast<void**>(&dC), nc * sizeof(double));
-    if (e == hipSuccess && fields_in) e = dca_dev_malloc(reinterpret_cast<void**>(&dFieldsIn), npairs * 2 * q * sizeof(double));
-    if (e == hipSuccess && fields_in) e = hipMemcpy(dFieldsIn, fields_in, npairs * 2 * q * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dF), (size_t)L * q * sizeof(double));
-    if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dDi), npairs * sizeof(double));
-    if (e == hipSuccess && fields_out) e = dca_dev_malloc(reinterpret_cast<void**>(&dFields), npairs * 2 * q * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(dC, couplings, nc * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(dF, reg_fi, (size_t)L * q * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(di_kernel<double>, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, dC, layout == 1 ? 1 : 2, dF, L, q, n, dDi, dFields, dFieldsIn);
-        e = hipStreamSynchronize(ctx->stream);
-    }
-    if (e == hipSuccess && di_out) e = hipMemcpy(di_out, dDi, npairs * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && fields_out) e = hipMemcpy(fields_out, dFields, npairs * 2 * q * sizeof(double), hipMemcpyDeviceToHost);
-    dca_dev_free(dC); dca_dev_free(dF); dca_dev_free(dDi); dca_dev_free(dFields); dca_dev_free(dFieldsIn);
-    if (e != hipSuccess) { dca_set_error("dca_di_from_arrays: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
+    static const char* who = "dca_di_from_arrays";
+    DevBuf<double> dC, dF, dDi, dFields, dFieldsIn;
+    HIP_TRY_AS(dC.alloc(nc), who);
+    if (fields_in) HIP_TRY_AS(dFieldsIn.alloc(npairs * 2 * q), who);
+    if (fields_in) HIP_TRY_AS(hipMemcpy(dFieldsIn, fields_in, npairs * 2 * q * sizeof(double), hipMemcpyHostToDevice), who);
+    HIP_TRY_AS(dF.alloc((size_t)L * q), who);
+    HIP_TRY_AS(dDi.alloc(npairs), who);
+    if (fields_out) HIP_TRY_AS(dFields.alloc(npairs * 2 * q), who);
+    HIP_TRY_AS(hipMemcpy(dC, couplings, nc * sizeof(double), hipMemcpyHostToDevice), who);
+    HIP_TRY_AS(hipMemcpy(dF, reg_fi, (size_t)L * q * sizeof(double), hipMemcpyHostToDevice), who);
+    hipLaunchKernelGGL(di_kernel<double>, dim3((unsigned)npairs), dim3(64), 0, ctx->stream, dC.get(), layout == 1 ? 1 : 2, dF.get(), L, q, n,
+                       dDi.get(), dFields.get(), dFieldsIn.get());
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
+    if (di_out) HIP_TRY_AS(hipMemcpy(di_out, dDi, npairs * sizeof(double), hipMemcpyDeviceToHost), who);
+    if (fields_out) HIP_TRY_AS(hipMemcpy(fields_out, dFields, npairs * 2 * q * sizeof(double), hipMemcpyDeviceToHost), who);
     return DCA_OK;
 }

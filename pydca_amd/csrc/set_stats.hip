@@ -87,53 +87,40 @@ int dca_set_statistics_impl(dca_ctx* ctx, const uint8_t* Q, int nq, double* fi_o
     const size_t Lq = (size_t)L * q, pairs = (size_t)L * (L - 1) / 2, nij = pairs * q * q;
     if (Q) DCA_TRY(dca_check_codes(Q, (size_t)nq * L, q, "dca_sequence_statistics: "));
     const bool wantX = !Q || cmp_out;
-    double *dXi = nullptr, *dXij = nullptr, *dYi = nullptr, *dYij = nullptr, *dSlab = nullptr;
+    static const char* who = "dca_sequence_statistics";
+    DevBuf<double> dXi, dXij, dYi, dYij, dSlab;
     DcaChains ch;
-    auto done = [&](int rc) {
-        if (ctx->stream) hipStreamSynchronize(ctx->stream);
-        dca_chains_free(&ch);
-        dca_dev_free(dXi); dca_dev_free(dXij); dca_dev_free(dYi); dca_dev_free(dYij); dca_dev_free(dSlab);
-        return rc;
-    };
-    hipError_t e = hipSuccess;
-    if (wantX) {
-        e = dca_dev_malloc(reinterpret_cast<void**>(&dXi), Lq * sizeof(double), false);
-        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dXij), nij * sizeof(double), false);
+    if ((wantX && (dXi.alloc(Lq, false) != hipSuccess || dXij.alloc(nij, false) != hipSuccess)) ||
+        (Q && (dYi.alloc(Lq, false) != hipSuccess || dYij.alloc(nij, false) != hipSuccess)) ||
+        (cmp_out && dSlab.alloc(((size_t)L + 1) * kVals, false) != hipSuccess)) {
+        dca_set_error("%s: out of device memory", who);
+        return DCA_ERR_NOMEM;
     }
-    if (e == hipSuccess && Q) {
-        e = dca_dev_malloc(reinterpret_cast<void**>(&dYi), Lq * sizeof(double), false);
-        if (e == hipSuccess) e = dca_dev_malloc(reinterpret_cast<void**>(&dYij), nij * sizeof(double), false);
-    }
-    if (e == hipSuccess && cmp_out) e = dca_dev_malloc(reinterpret_cast<void**>(&dSlab), ((size_t)L + 1) * kVals * sizeof(double), false);
-    if (e != hipSuccess) { dca_set_error("dca_sequence_statistics: out of device memory"); return done(DCA_ERR_NOMEM); }
     if (wantX) {
         // a private engine, so the context's own mf state (counts, correlation matrix, couplings, hooks) stays as it is
         MfEngine* m = dca_make_mf_engine(ctx);
-        if (!m) return done(DCA_ERR_NOMEM);
+        if (!m) return DCA_ERR_NOMEM;
         const int rc = dca_mf_engine_bm_freqs(m, 0.0, dXi, dXij);
         dca_free_mf_engine(m);
-        if (rc != DCA_OK) return done(rc);
+        DCA_TRY(rc);
     }
     if (Q) {
         // the set as site-major device codes, the layout the statistics kernels count
-        const int rc = dca_chains_start(ctx, &ch, nq, L, q, 0, 0, Q);
-        if (rc != DCA_OK) return done(rc);
-        e = dca_bm_count_chains(ctx, ch, q, dYi, dYij);
+        DCA_TRY(dca_chains_start(ctx, &ch, nq, L, q, 0, 0, Q));
+        HIP_TRY_AS(dca_bm_count_chains(ctx, ch, q, dYi, dYij), who);
     }
-    if (e == hipSuccess && cmp_out) {
+    if (cmp_out) {
         ScopedKernelClock kc(ctx, "set_compare");
-        hipLaunchKernelGGL(set_compare_kernel, dim3(L), dim3(kThreads), 0, ctx->stream, dXi, dXij, dYi, dYij, L, q, dSlab);
-        hipLaunchKernelGGL(set_reduce_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, dSlab, L, dSlab + (size_t)L * kVals);
-        e = hipGetLastError();
+        hipLaunchKernelGGL(set_compare_kernel, dim3(L), dim3(kThreads), 0, ctx->stream, dXi.get(), dXij.get(), dYi.get(), dYij.get(), L, q,
+                           dSlab.get());
+        hipLaunchKernelGGL(set_reduce_kernel, dim3(1), dim3(kThreads), 0, ctx->stream, dSlab.get(), L, dSlab + (size_t)L * kVals);
+        HIP_TRY_AS(hipGetLastError(), who);
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    const double* srcI = Q ? dYi : dXi;
-    const double* srcIJ = Q ? dYij : dXij;
-    if (e == hipSuccess && fi_out) e = hipMemcpy(fi_out, srcI, Lq * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && fij_out) e = hipMemcpy(fij_out, srcIJ, nij * sizeof(double), hipMemcpyDeviceToHost);
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
+    if (fi_out) HIP_TRY_AS(hipMemcpy(fi_out, (Q ? dYi : dXi).get(), Lq * sizeof(double), hipMemcpyDeviceToHost), who);
+    if (fij_out) HIP_TRY_AS(hipMemcpy(fij_out, (Q ? dYij : dXij).get(), nij * sizeof(double), hipMemcpyDeviceToHost), who);
     double r[kVals];
-    if (e == hipSuccess && cmp_out) e = hipMemcpy(r, dSlab + (size_t)L * kVals, sizeof(r), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { dca_set_error("dca_sequence_statistics: %s", hipGetErrorString(e)); return done(DCA_ERR_HIP); }
+    if (cmp_out) HIP_TRY_AS(hipMemcpy(r, dSlab + (size_t)L * kVals, sizeof(r), hipMemcpyDeviceToHost), who);
     if (cmp_out) {
         for (int k = 0; k < 3; ++k) {
             const double sxx = r[4 * k], syy = r[4 * k + 1], sxy = r[4 * k + 2];
@@ -145,5 +132,5 @@ int dca_set_statistics_impl(dca_ctx* ctx, const uint8_t* Q, int nq, double* fi_o
             cmp_out->terms[k] = k == 0 ? (double)Lq : (double)nij;
         }
     }
-    return done(DCA_OK);
+    return DCA_OK;
 }

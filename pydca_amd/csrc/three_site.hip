@@ -225,15 +225,8 @@ void ts_values_final_kernel(int U, int q, double Md, const int32_t* __restrict__
 }
 
 // ---------------------------------------------------------------- host side
-int ts_pass_size()
-{
-    const char* e = getenv("DCA_NN_PASS");          // the pass variable of dca_hamming_nearest, read per call
-    const long v = e ? atol(e) : 0;
-    return v > 0 ? (int)std::min<long>(v, 1 << 20) : 32768;
-}
-
-// the context's weights as integers on the device (caller frees); *M = their sum
-int ts_alignment_weights(dca_ctx* ctx, const char* who, uint64_t** dW, uint64_t* M)
+// the context's weights as integers on the device; *M = their sum
+int ts_alignment_weights(dca_ctx* ctx, const char* who, DevBuf<uint64_t>* dW, uint64_t* M)
 {
     const int N = ctx->N;
     if (N > (1 << 23)) { dca_set_error("%s: %d sequences are more than the 2^23 the integer sums allow", who, N); return DCA_ERR_ARG; }
@@ -249,11 +242,11 @@ int ts_alignment_weights(dca_ctx* ctx, const char* who, uint64_t** dW, uint64_t*
         sum += (uint64_t)v;
     }
     if (sum == 0) { dca_set_error("%s: the weights sum to zero", who); return DCA_ERR_ARG; }
-    if (dca_dev_malloc(reinterpret_cast<void**>(dW), (size_t)N * sizeof(uint64_t), false) != hipSuccess) {
+    if (dW->alloc((size_t)N, false) != hipSuccess) {
         dca_set_error("%s: out of device memory", who);
         return DCA_ERR_NOMEM;
     }
-    HIP_TRY(hipMemcpy(*dW, wq.data(), (size_t)N * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dW->get(), wq.data(), (size_t)N * sizeof(uint64_t), hipMemcpyHostToDevice));
     *M = sum;
     return DCA_OK;
 }
@@ -283,33 +276,8 @@ hipError_t launch_scan(dca_ctx* ctx, int TB, int grid, const TsScanArgs& A)
     return hipGetLastError();
 }
 
-struct DevBufs {
-    std::vector<void*> p;
-    dca_ctx* ctx;
-    explicit DevBufs(dca_ctx* c) : ctx(c) {}
-    template <class T> hipError_t get(T** out, size_t count, bool zero)
-    {
-        void* v = nullptr;
-        const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-        hipError_t e = dca_dev_malloc(&v, bytes, false);
-        if (e != hipSuccess) return e;
-        p.push_back(v);
-        *out = static_cast<T*>(v);
-        return zero ? hipMemsetAsync(v, 0, bytes, ctx->stream) : hipSuccess;
-    }
-    ~DevBufs()
-    {
-        if (ctx->stream) hipStreamSynchronize(ctx->stream);
-        for (void* v : p) dca_dev_free(v);
-    }
-};
-
-#define TS_HIP(expr, who)                                                                     \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e == hipErrorOutOfMemory) { dca_set_error("%s: out of device memory", who); return DCA_ERR_NOMEM; } \
-        if (_e != hipSuccess) { dca_set_error("%s: %s", who, hipGetErrorString(_e)); return DCA_ERR_HIP; }      \
-    } while (0)
+// a buffer of max(count, 1) elements, not zeroed; out of memory is DCA_ERR_NOMEM
+#define TS_ALLOC(buf, count) HIP_TRY_AS_NOMEM((buf).alloc(std::max<size_t>(count, 1), false), who)
 
 }  // namespace
 
@@ -352,60 +320,58 @@ int dca_three_site_values_impl(dca_ctx* ctx, const uint8_t* Q, int nq, const int
     goff.push_back((int32_t)keys.size());
     const int U = (int)keys.size(), G = (int)goff.size() - 1, nt = 3 * q + 3 * qq;
 
-    DevBufs B(ctx);
-    uint64_t* dW = nullptr;
+    DevBuf<uint64_t> dW;
     uint64_t M = (uint64_t)nq;
-    if (!Q) {
-        DCA_TRY(ts_alignment_weights(ctx, who, &dW, &M));
-        B.p.push_back(dW);
-    }
-    int32_t *dTri = nullptr, *dGoff = nullptr, *dKeys = nullptr, *dGrp = nullptr;
-    unsigned long long *dCnt = nullptr, *dTab = nullptr;
-    double *dF3 = nullptr, *dC3 = nullptr;
-    uint8_t* dRows = nullptr;
-    TS_HIP(B.get(&dTri, tri.size(), false), who);
-    TS_HIP(B.get(&dGoff, goff.size(), false), who);
-    TS_HIP(B.get(&dKeys, keys.size(), false), who);
-    TS_HIP(B.get(&dGrp, grp.size(), false), who);
-    TS_HIP(B.get(&dCnt, (size_t)U, true), who);
-    TS_HIP(B.get(&dTab, (size_t)G * nt, true), who);
-    TS_HIP(B.get(&dF3, (size_t)U, false), who);
-    TS_HIP(B.get(&dC3, (size_t)U, false), who);
-    const int pass = Q ? std::min(nq, ts_pass_size()) : 0;
-    if (Q) TS_HIP(B.get(&dRows, (size_t)pass * Ls, false), who);
-    TS_HIP(hipMemcpyAsync(dTri, tri.data(), tri.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), who);
-    TS_HIP(hipMemcpyAsync(dGoff, goff.data(), goff.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), who);
-    TS_HIP(hipMemcpyAsync(dKeys, keys.data(), keys.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), who);
-    TS_HIP(hipMemcpyAsync(dGrp, grp.data(), grp.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), who);
-    TS_HIP(hipStreamSynchronize(ctx->stream), who);
+    if (!Q) DCA_TRY(ts_alignment_weights(ctx, who, &dW, &M));
+    DevBuf<int32_t> dTri, dGoff, dKeys, dGrp;
+    DevBuf<unsigned long long> dCnt, dTab;
+    DevBuf<double> dF3, dC3;
+    DevBuf<uint8_t> dRows;
+    TS_ALLOC(dTri, tri.size());
+    TS_ALLOC(dGoff, goff.size());
+    TS_ALLOC(dKeys, keys.size());
+    TS_ALLOC(dGrp, grp.size());
+    TS_ALLOC(dCnt, (size_t)U);
+    HIP_TRY_AS_NOMEM(hipMemsetAsync(dCnt, 0, std::max<size_t>(U, 1) * sizeof(unsigned long long), ctx->stream), who);
+    TS_ALLOC(dTab, (size_t)G * nt);
+    HIP_TRY_AS_NOMEM(hipMemsetAsync(dTab, 0, std::max<size_t>((size_t)G * nt, 1) * sizeof(unsigned long long), ctx->stream), who);
+    TS_ALLOC(dF3, (size_t)U);
+    TS_ALLOC(dC3, (size_t)U);
+    const int pass = Q ? std::min(nq, dca_nn_pass_size()) : 0;
+    if (Q) TS_ALLOC(dRows, (size_t)pass * Ls);
+    HIP_TRY_AS_NOMEM(hipMemcpyAsync(dTri, tri.data(), tri.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), who);
+    HIP_TRY_AS_NOMEM(hipMemcpyAsync(dGoff, goff.data(), goff.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), who);
+    HIP_TRY_AS_NOMEM(hipMemcpyAsync(dKeys, keys.data(), keys.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), who);
+    HIP_TRY_AS_NOMEM(hipMemcpyAsync(dGrp, grp.data(), grp.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream), who);
+    HIP_TRY_AS_NOMEM(hipStreamSynchronize(ctx->stream), who);
     if (!Q) {
         ScopedKernelClock kc(ctx, "three_site_values");
         hipLaunchKernelGGL(ts_values_count_kernel, dim3(G), dim3(kThreads), 0, ctx->stream, ctx->dX, dW, ctx->N, Ls, q, dTri, dGoff,
                            dKeys, dCnt, dTab);
-        TS_HIP(hipGetLastError(), who);
+        HIP_TRY_AS_NOMEM(hipGetLastError(), who);
     } else {
         for (int first = 0; first < nq; first += pass) {
             const int m = std::min(pass, nq - first);
-            TS_HIP(hipStreamSynchronize(ctx->stream), who);          // the previous pass has read the rows
+            HIP_TRY_AS_NOMEM(hipStreamSynchronize(ctx->stream), who);          // the previous pass has read the rows
             DCA_TRY(ts_upload_rows(Q + (size_t)first * L, m, L, Ls, dRows));
             ScopedKernelClock kc(ctx, "three_site_values");
             hipLaunchKernelGGL(ts_values_count_kernel, dim3(G), dim3(kThreads), 0, ctx->stream, dRows, (const uint64_t*)nullptr, m, Ls,
                                q, dTri, dGoff, dKeys, dCnt, dTab);
-            TS_HIP(hipGetLastError(), who);
+            HIP_TRY_AS_NOMEM(hipGetLastError(), who);
         }
     }
     {
         ScopedKernelClock kc(ctx, "three_site_values");
         hipLaunchKernelGGL(ts_values_final_kernel, dim3(ceil_div(U, kThreads)), dim3(kThreads), 0, ctx->stream, U, q, (double)M, dGrp,
                            dKeys, dCnt, dTab, dF3, dC3);
-        TS_HIP(hipGetLastError(), who);
+        HIP_TRY_AS_NOMEM(hipGetLastError(), who);
     }
-    TS_HIP(hipStreamSynchronize(ctx->stream), who);
+    HIP_TRY_AS_NOMEM(hipStreamSynchronize(ctx->stream), who);
     std::vector<uint64_t> hc(count_out ? U : 0);
     std::vector<double> hf(f3_out ? U : 0), hcc(c3_out ? U : 0);
-    if (count_out) TS_HIP(hipMemcpy(hc.data(), dCnt, (size_t)U * sizeof(uint64_t), hipMemcpyDeviceToHost), who);
-    if (f3_out) TS_HIP(hipMemcpy(hf.data(), dF3, (size_t)U * sizeof(double), hipMemcpyDeviceToHost), who);
-    if (c3_out) TS_HIP(hipMemcpy(hcc.data(), dC3, (size_t)U * sizeof(double), hipMemcpyDeviceToHost), who);
+    if (count_out) HIP_TRY_AS_NOMEM(hipMemcpy(hc.data(), dCnt, (size_t)U * sizeof(uint64_t), hipMemcpyDeviceToHost), who);
+    if (f3_out) HIP_TRY_AS_NOMEM(hipMemcpy(hf.data(), dF3, (size_t)U * sizeof(double), hipMemcpyDeviceToHost), who);
+    if (c3_out) HIP_TRY_AS_NOMEM(hipMemcpy(hcc.data(), dC3, (size_t)U * sizeof(double), hipMemcpyDeviceToHost), who);
     for (int e = 0; e < T; ++e) {
         if (count_out) count_out[e] = hc[slot[e]];
         if (f3_out) f3_out[e] = hf[slot[e]];
@@ -427,13 +393,9 @@ int dca_three_site_scan_impl(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int 
     if (!rows) { dca_set_error("%s: cannot read the alignment back", who); return DCA_ERR_HIP; }
     const int skip = skip_state >= 0 && skip_state < q ? skip_state : -1;
 
-    DevBufs B(ctx);
-    uint64_t* dW = nullptr;
+    DevBuf<uint64_t> dW;
     uint64_t M = (uint64_t)nq;
-    if (!Q) {
-        DCA_TRY(ts_alignment_weights(ctx, who, &dW, &M));
-        B.p.push_back(dW);
-    }
+    if (!Q) DCA_TRY(ts_alignment_weights(ctx, who, &dW, &M));
     // the sequences of every (site, state), the layout of the mean-field counting lists: perm[i * n + off[i][a] .. off[i][a + 1])
     std::vector<int32_t> off((size_t)L * (q + 1), 0), perm((size_t)L * n);
     for (int s = 0; s < n; ++s)
@@ -453,35 +415,37 @@ int dca_three_site_scan_impl(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int 
         for (int kt = jt; kt < nt1; ++kt) tiles.push_back(make_int2(jt, kt));
     const int nT = (int)tiles.size();
 
-    uint8_t* dRows = nullptr;
-    int32_t *dPerm = nullptr, *dOff = nullptr;
-    int2* dTiles = nullptr;
-    double *dF1 = nullptr, *dF2 = nullptr;
-    unsigned long long *dHist = nullptr, *dCursor = nullptr;
+    DevBuf<uint8_t> dRows;
+    DevBuf<int32_t> dPerm, dOff;
+    DevBuf<int2> dTiles;
+    DevBuf<double> dF1, dF2;
+    DevBuf<unsigned long long> dHist, dCursor;
+    DevBuf<TsRecord> dRec;
     if (Q) {
-        TS_HIP(B.get(&dRows, (size_t)n * Ls, false), who);
+        TS_ALLOC(dRows, (size_t)n * Ls);
         DCA_TRY(ts_upload_rows(Q, n, L, Ls, dRows));
     }
-    const uint8_t* dX = Q ? dRows : ctx->dX;
-    TS_HIP(B.get(&dPerm, perm.size(), false), who);
-    TS_HIP(B.get(&dOff, off.size(), false), who);
-    TS_HIP(B.get(&dTiles, tiles.size(), false), who);
-    TS_HIP(B.get(&dF1, (size_t)L * q, false), who);
-    TS_HIP(B.get(&dF2, pairs * qq, false), who);
-    TS_HIP(B.get(&dHist, (size_t)kBins, false), who);
-    TS_HIP(B.get(&dCursor, (size_t)1, true), who);
-    TS_HIP(hipMemcpy(dPerm, perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice), who);
-    TS_HIP(hipMemcpy(dOff, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice), who);
-    TS_HIP(hipMemcpy(dTiles, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice), who);
+    const uint8_t* dX = Q ? dRows.get() : ctx->dX;
+    TS_ALLOC(dPerm, perm.size());
+    TS_ALLOC(dOff, off.size());
+    TS_ALLOC(dTiles, tiles.size());
+    TS_ALLOC(dF1, (size_t)L * q);
+    TS_ALLOC(dF2, pairs * qq);
+    TS_ALLOC(dHist, (size_t)kBins);
+    TS_ALLOC(dCursor, (size_t)1);
+    HIP_TRY_AS_NOMEM(hipMemsetAsync(dCursor, 0, sizeof(unsigned long long), ctx->stream), who);
+    HIP_TRY_AS_NOMEM(hipMemcpy(dPerm, perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice), who);
+    HIP_TRY_AS_NOMEM(hipMemcpy(dOff, off.data(), off.size() * sizeof(int32_t), hipMemcpyHostToDevice), who);
+    HIP_TRY_AS_NOMEM(hipMemcpy(dTiles, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice), who);
 
     const double Md = (double)M;
     hipLaunchKernelGGL(ts_site_kernel, dim3(L), dim3(kThreads), 0, ctx->stream, dX, dW, n, Ls, q, Md, dF1);
     hipLaunchKernelGGL(ts_pair_kernel, dim3(ceil_div(L, kPairChunk), L), dim3(kThreads), (size_t)kPairChunk * qq * sizeof(unsigned long long),
                        ctx->stream, dX, dW, n, L, Ls, q, Md, dF2);
-    TS_HIP(hipGetLastError(), who);
+    HIP_TRY_AS_NOMEM(hipGetLastError(), who);
 
     hipDeviceProp_t prop;
-    TS_HIP(hipGetDeviceProperties(&prop, ctx->device), who);
+    HIP_TRY_AS_NOMEM(hipGetDeviceProperties(&prop, ctx->device), who);
     TsScanArgs A{};
     A.X = dX; A.W = dW; A.perm = dPerm; A.off = dOff; A.tiles = dTiles; A.F1 = dF1; A.F2 = dF2;
     A.n = n; A.L = L; A.Ls = Ls; A.q = q; A.nT = nT; A.skip = skip;
@@ -494,10 +458,10 @@ int dca_three_site_scan_impl(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int 
     std::vector<unsigned long long> hist(kBins);
     auto hist_pass = [&](unsigned long long flo, unsigned long long fhi, unsigned long long lo, int sh) -> int {
         A.mode = 0; A.flo = flo; A.fhi = fhi; A.lo = lo; A.sh = sh;
-        TS_HIP(hipMemsetAsync(dHist, 0, kBins * sizeof(unsigned long long), ctx->stream), who);
-        TS_HIP(launch_scan(ctx, TB, grid, A), who);
-        TS_HIP(hipStreamSynchronize(ctx->stream), who);
-        TS_HIP(hipMemcpy(hist.data(), dHist, kBins * sizeof(unsigned long long), hipMemcpyDeviceToHost), who);
+        HIP_TRY_AS_NOMEM(hipMemsetAsync(dHist, 0, kBins * sizeof(unsigned long long), ctx->stream), who);
+        HIP_TRY_AS_NOMEM(launch_scan(ctx, TB, grid, A), who);
+        HIP_TRY_AS_NOMEM(hipStreamSynchronize(ctx->stream), who);
+        HIP_TRY_AS_NOMEM(hipMemcpy(hist.data(), dHist, kBins * sizeof(unsigned long long), hipMemcpyDeviceToHost), who);
         return DCA_OK;
     };
     // level 1: the exponent and 4 mantissa bits of |c|, the 64 binades below 4.0; everything smaller (0 included) in bin 0
@@ -540,19 +504,18 @@ int dca_three_site_scan_impl(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int 
             return DCA_ERR_ARG;
         }
     }
-    TsRecord* dRec = nullptr;
-    TS_HIP(B.get(&dRec, (size_t)ncand, false), who);
+    TS_ALLOC(dRec, (size_t)ncand);
     A.mode = 1; A.edge = edge; A.cap = ncand; A.rec = dRec;
-    TS_HIP(launch_scan(ctx, TB, grid, A), who);
-    TS_HIP(hipStreamSynchronize(ctx->stream), who);
+    HIP_TRY_AS_NOMEM(launch_scan(ctx, TB, grid, A), who);
+    HIP_TRY_AS_NOMEM(hipStreamSynchronize(ctx->stream), who);
     unsigned long long appended = 0;
-    TS_HIP(hipMemcpy(&appended, dCursor, sizeof(appended), hipMemcpyDeviceToHost), who);
+    HIP_TRY_AS_NOMEM(hipMemcpy(&appended, dCursor, sizeof(appended), hipMemcpyDeviceToHost), who);
     if (appended != ncand) {
         dca_set_error("%s: the append pass found %llu elements where the histogram counted %llu", who, appended, ncand);
         return DCA_ERR_HIP;
     }
     std::vector<TsRecord> rec((size_t)ncand);
-    TS_HIP(hipMemcpy(rec.data(), dRec, (size_t)ncand * sizeof(TsRecord), hipMemcpyDeviceToHost), who);
+    HIP_TRY_AS_NOMEM(hipMemcpy(rec.data(), dRec, (size_t)ncand * sizeof(TsRecord), hipMemcpyDeviceToHost), who);
     std::sort(rec.begin(), rec.end(), [](const TsRecord& x, const TsRecord& y) {
         const double ax = std::fabs(x.c), ay = std::fabs(y.c);
         return ax != ay ? ax > ay : x.idx < y.idx;

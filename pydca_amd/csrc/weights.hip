@@ -271,47 +271,44 @@ int dca_weights_compute(dca_ctx* ctx, double seqid, int compare_precision, int p
         const char* orderEnv = getenv("DCA_WEIGHTS_ORDER");
         const bool wantRanked = orderEnv ? (orderEnv[0] == 'v') : (double)N * N * L >= 2e11;
         const bool ranked = wantRanked && (size_t)L * sizeof(unsigned long long) <= 60000;
-        uint32_t *dP = nullptr, *dHist = nullptr;
-        int* dPerm = nullptr;
-        unsigned long long* dWork = nullptr;
-        hipError_t ea = dca_dev_malloc(reinterpret_cast<void**>(&dP), (size_t)N * G * PLP * sizeof(uint32_t));
-        if (ea == hipSuccess) ea = dca_dev_malloc(reinterpret_cast<void**>(&dPerm), (size_t)ctx->Ls * sizeof(int));
+        static const char* who = "weights scratch";
+        DevBuf<uint32_t> dP, dHist;
+        DevBuf<int> dPerm;
+        DevBuf<unsigned long long> dWork;
+        HIP_TRY_AS(dP.alloc((size_t)N * G * PLP), who);
+        HIP_TRY_AS(dPerm.alloc((size_t)ctx->Ls), who);
         // the work counter (a 64-bit atomic per wave, a 32 KB read-back: what bench.py prices the kernel with) only on request
         const bool countWork = getenv("DCA_WEIGHTS_WORK") && atoi(getenv("DCA_WEIGHTS_WORK")) != 0;       // read per call: bench.py asks for ONE counted pass
         ctx->weightsWork[0] = ctx->weightsWork[1] = 0;
         if (countWork) {
-            if (ea == hipSuccess) ea = dca_dev_malloc(reinterpret_cast<void**>(&dWork), kWorkSlots * sizeof(unsigned long long));
-            if (ea == hipSuccess) ea = hipMemsetAsync(dWork, 0, kWorkSlots * sizeof(unsigned long long), ctx->stream);
+            HIP_TRY_AS(dWork.alloc(kWorkSlots), who);
+            HIP_TRY_AS(hipMemsetAsync(dWork, 0, kWorkSlots * sizeof(unsigned long long), ctx->stream), who);
         }
-        if (ea == hipSuccess && ranked) {            // the site histogram only exists for the ranked order
-            ea = dca_dev_malloc(reinterpret_cast<void**>(&dHist), (size_t)L * 32 * sizeof(uint32_t));
-            if (ea == hipSuccess) ea = hipMemsetAsync(dHist, 0, (size_t)L * 32 * sizeof(uint32_t), ctx->stream);
-        }
-        if (ea != hipSuccess) {                      // nothing of the scratch is left behind
-            dca_dev_free(dP); dca_dev_free(dHist); dca_dev_free(dPerm); dca_dev_free(dWork);
-            dca_set_error("weights scratch: %s", hipGetErrorString(ea));
-            return DCA_ERR_HIP;
+        if (ranked) {            // the site histogram only exists for the ranked order
+            HIP_TRY_AS(dHist.alloc((size_t)L * 32), who);
+            HIP_TRY_AS(hipMemsetAsync(dHist, 0, (size_t)L * 32 * sizeof(uint32_t), ctx->stream), who);
         }
         if (ranked)
             hipLaunchKernelGGL(weights_column_hist_kernel, dim3(ceil_div(L, 256), ceil_div(N, kSeqPerBlock)), dim3(256), 0, ctx->stream,
-                               ctx->dX, dHist, N, L, ctx->Ls, kSeqPerBlock);
+                               ctx->dX, dHist.get(), N, L, ctx->Ls, kSeqPerBlock);
         hipLaunchKernelGGL(weights_column_rank_kernel, dim3(1), dim3(1024), ranked ? (size_t)L * sizeof(unsigned long long) : 0, ctx->stream,
-                           ranked ? dHist : nullptr, dPerm, L, ctx->Ls);
+                           dHist.get(), dPerm.get(), L, ctx->Ls);
         const unsigned tb = (unsigned)(((size_t)N * G + 255) / 256);
         const int tilesPerSide = ceil_div(N, kTile);
         const int superPerSide = ceil_div(tilesPerSide, 32);
         dim3 grid((unsigned)ceil_div(superPerSide * superPerSide * 32 * 32, parts));
         if (small) {
-            hipLaunchKernelGGL(weights_bitplanes_kernel<3>, dim3(tb), dim3(256), 0, ctx->stream, ctx->dX, dPerm, dP, N, ctx->Ls);
-            hipLaunchKernelGGL(weights_count_kernel<3>, grid, dim3(256), 0, ctx->stream, dP, ctx->dCounts, N, L, G, thresh, tilesPerSide, part, parts, dWork);
+            hipLaunchKernelGGL(weights_bitplanes_kernel<3>, dim3(tb), dim3(256), 0, ctx->stream, ctx->dX, dPerm.get(), dP.get(), N, ctx->Ls);
+            hipLaunchKernelGGL(weights_count_kernel<3>, grid, dim3(256), 0, ctx->stream, dP.get(), ctx->dCounts, N, L, G, thresh, tilesPerSide, part, parts, dWork.get());
         } else {
-            hipLaunchKernelGGL(weights_bitplanes_kernel<5>, dim3(tb), dim3(256), 0, ctx->stream, ctx->dX, dPerm, dP, N, ctx->Ls);
-            hipLaunchKernelGGL(weights_count_kernel<5>, grid, dim3(256), 0, ctx->stream, dP, ctx->dCounts, N, L, G, thresh, tilesPerSide, part, parts, dWork);
+            hipLaunchKernelGGL(weights_bitplanes_kernel<5>, dim3(tb), dim3(256), 0, ctx->stream, ctx->dX, dPerm.get(), dP.get(), N, ctx->Ls);
+            hipLaunchKernelGGL(weights_count_kernel<5>, grid, dim3(256), 0, ctx->stream, dP.get(), ctx->dCounts, N, L, G, thresh, tilesPerSide, part, parts, dWork.get());
         }
-        hipError_t e = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess && dWork) {
+        ctx->weightsPlanes = small ? 3 : 5;
+        HIP_TRY_AS(hipStreamSynchronize(ctx->stream), "weights kernel");
+        if (dWork) {
             std::vector<unsigned long long> slots(kWorkSlots);
-            e = hipMemcpy(slots.data(), dWork, kWorkSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+            HIP_TRY_AS(hipMemcpy(slots.data(), dWork, kWorkSlots * sizeof(unsigned long long), hipMemcpyDeviceToHost), "weights kernel");
             unsigned long long done = 0;
             for (unsigned long long v : slots) done += v;
             // without the early exit every wave of this part's tile pairs (upper triangle, diagonal included) compares all G groups
@@ -319,12 +316,6 @@ int dca_weights_compute(dca_ctx* ctx, double seqid, int compare_precision, int p
             ctx->weightsWork[0] = done;
             ctx->weightsWork[1] = (tp + parts - 1 - part) / parts * 4ull * (unsigned long long)G;
         }
-        ctx->weightsPlanes = small ? 3 : 5;
-        dca_dev_free(dWork);
-        dca_dev_free(dP);
-        dca_dev_free(dHist);
-        dca_dev_free(dPerm);
-        if (e != hipSuccess) { dca_set_error("weights kernel: %s", hipGetErrorString(e)); return DCA_ERR_HIP; }
     }
     ctx->have_weights = false;
     ctx->have_counts = false;          // ctx->dCounts holds this part's counts only; dca_weights_finish declares them complete
