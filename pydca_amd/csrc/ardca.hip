@@ -20,6 +20,7 @@
 // Sampler ("ar_sample"): chain c visits sites 0 .. L-1 once and draws s_l with sample.hip's rule at beta = 1 from
 // U = Philox(seed; chain, 0, site, 3).  DESIGN.md section 16 has the geometry and the measured numbers.
 #include "site_conditionals.h"
+#include "ar_plan.h"
 #include "more_thuente.h"
 #include "vec_kernels.h"
 
@@ -31,9 +32,6 @@
 namespace {
 
 constexpr size_t kAPassBudget = 1ull << 30;        // device scratch of one pass
-constexpr int kGTile = 64;                         // sequences per staged tile of the coupling gradient
-constexpr size_t kGBlockBudget = 56 * 1024;        // LDS of the gradient blocks of one workgroup
-constexpr int kGMaxThreads = 512;
 constexpr int kSSlices = 4;                        // sampler: lanes per chain (k = w mod 4)
 constexpr int kSChainsPerWave = 64 / kSSlices;
 constexpr int kDotBlocks = 256;
@@ -267,11 +265,6 @@ hipError_t launch_logits(dca_ctx* ctx, const double* x, int L, int q, const uint
     });
 }
 
-int grad_chunk(int q)
-{
-    return std::max(1, std::min({64, (int)(kGBlockBudget / ((size_t)q * q * sizeof(double))), kGMaxThreads / q}));
-}
-
 inline unsigned blocks_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -372,9 +365,9 @@ struct ArEngine {
     {
         const size_t Lq = (size_t)L * q;
         hipError_t e = hipSuccess;
-        const int KC = grad_chunk(q);
-        const int gthreads = (int)round_up((size_t)KC * q, 64);
-        const size_t glds = ((size_t)KC * q * q + (size_t)kGTile * q) * sizeof(double) + (size_t)KC * kGTile;
+        const ArGradPlan gp = ar_grad_plan(q);
+        const int KC = gp.KC, gthreads = gp.threads;
+        const size_t glds = gp.lds;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(ar_grad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds);
         for (int p = 0; p < npass && e == hipSuccess; ++p) {
             const int first = p * pass, nq = std::min(pass, N - first);
