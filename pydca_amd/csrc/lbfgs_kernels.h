@@ -197,6 +197,147 @@ __global__ void vec_compose_kernel(T* __restrict__ d, const T* __restrict__ g, V
 #undef ldp
 #undef stp
 
+// ---- direction, first trial point and coupling table in ONE pass (one GPU, plain path; PlmEngine::fused_step_ok)
+// After the first iteration the line search's first trial step is 1, known when the direction is composed.  So, per element:
+// d = vec_compose_kernel's expression, xt = vec_step_kernel's with step (T)1 on the accepted x and the rounded d, and W takes xt
+// where plm_expand_kernel would put it -- 12 reads and 2 writes of the packed vector and one write of W, where the three kernels
+// read 16, wrote 2 and wrote W in runs of q elements.  No sum is formed here: every element is a chain of its own, so the bits are
+// those of the three kernels whatever the tiling.
+// The pairs (i, j) are packed i-major.  A workgroup owns TI consecutive sites i (the columns of one 512-byte strip of W) x JC
+// consecutive sites j: per i one contiguous piece of JC q^2 packed elements, read and written in 16-byte packs (the packs at a
+// piece's two ends are shared with the neighbouring workgroup: both compute them, each stores its own elements).  xt goes through
+// LDS as tile[ii][jj][a][b]; rows (i, a) of W then take runs of JC q elements, the transposed rows (j, b) runs of TI q.  The
+// workgroups behind the pair blocks (their count rounded up to 64) do the fields, one element per thread.
+__host__ __device__ constexpr int fused_step_ti(int q, int elemBytes) { return kRowBytes / elemBytes / q; }
+// JC at q = 21: 42 KB of LDS, three workgroups of eight waves per CU.  Measured at config D (float32): JC 2 / 3 / 4 / 6 with 256 or
+// 512 threads all lie within 2.5 % of each other, this one first
+__host__ __device__ constexpr int fused_step_jc(int q) { return q == 21 ? 4 : 16; }
+constexpr int kFusedStepThreads = 512;
+
+template <typename T>
+__device__ __forceinline__ T compose_elem(const DirCoefs& c, T gv, const T* sv, const T* yv)
+{
+    double v = c.g * (double)gv;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v += c.s[k] * (double)sv[k] + c.y[k] * (double)yv[k];
+    return (T)v;
+}
+
+template <typename T, int Q>
+__global__ __launch_bounds__(kFusedStepThreads)
+void lbfgs_dir_trial_expand_kernel(T* __restrict__ d, T* __restrict__ xt, T* __restrict__ W, const T* __restrict__ x, const T* __restrict__ g,
+                                   VecPtrs5 P, const DirCoefs* __restrict__ cp, int L, int Cs, int numJC, int pairBlocks)
+{
+    constexpr int VEC = 16 / (int)sizeof(T), TI = fused_step_ti(Q, (int)sizeof(T)), JC = fused_step_jc(Q), Q2 = Q * Q;
+    extern __shared__ __attribute__((aligned(16))) unsigned char dca_smem[];
+    T* tile = reinterpret_cast<T*>(dca_smem);
+    __shared__ size_t sLo[TI];          // first packed element of site ii's piece
+    __shared__ int sCnt[TI];            // its elements
+    __shared__ int sPre[TI + 1];        // packs of the pieces in front of it
+    const DirCoefs c = *cp;
+    const T one = (T)1.0;
+    const int tid = threadIdx.x;
+    const int padded = (pairBlocks + 63) / 64 * 64;
+    if ((int)blockIdx.x >= padded) {
+        const size_t e = (size_t)((int)blockIdx.x - padded) * kFusedStepThreads + tid;
+        if (e < (size_t)L * Q) {
+            T sv[5], yv[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) { sv[k] = static_cast<const T*>(P.s[k])[e]; yv[k] = static_cast<const T*>(P.y[k])[e]; }
+            const T dv = compose_elem(c, g[e], sv, yv);
+            d[e] = dv;
+            const T v = one * dv;
+            xt[e] = x[e] + v;
+        }
+        return;
+    }
+    // Workgroups are dealt to the 8 XCDs in turn.  Of every 64 consecutive pair blocks, each XCD takes 8 consecutive ones: pieces
+    // that are neighbours in memory share the cache lines at their ends (reads of the packed vectors, runs of W), and seven
+    // of eight such ends then meet in one L2.  For speed only: nothing depends on where a workgroup runs.
+    const int blk = ((int)blockIdx.x & ~63) | (((int)blockIdx.x & 7) << 3) | (((int)blockIdx.x >> 3) & 7);
+    if (blk >= pairBlocks) return;
+    const int i0 = (blk / numJC) * TI, j0 = (blk % numJC) * JC;
+    const int j1 = min(j0 + JC, L);
+    if (j1 <= i0 + 1) return;           // below the diagonal; uniform over the workgroup
+    if (tid == 0) {
+        int pre = 0;
+        for (int ii = 0; ii < TI; ++ii) {
+            const int i = i0 + ii, jlo = max(j0, i + 1);
+            const int cnt = jlo < j1 ? (j1 - jlo) * Q2 : 0;
+            const size_t before = (size_t)L * (L - 1) / 2 - (size_t)(L - i) * (L - i - 1) / 2;       // pairs whose first site is < i
+            const size_t lo = cnt ? (size_t)L * Q + (before + (size_t)(jlo - i - 1)) * Q2 : 0;
+            sLo[ii] = lo; sCnt[ii] = cnt; sPre[ii] = pre;
+            pre += cnt ? (int)((lo + cnt + VEC - 1) / VEC - lo / VEC) : 0;
+        }
+        sPre[TI] = pre;
+    }
+    __syncthreads();
+    const int total = sPre[TI];
+    for (int idx = tid; idx < total; idx += kFusedStepThreads) {
+        int ii = 0;
+        while (idx >= sPre[ii + 1]) ++ii;
+        const size_t lo = sLo[ii], hi = lo + (size_t)sCnt[ii];
+        const size_t iv = lo / VEC + (size_t)(idx - sPre[ii]);
+        // all twelve loads of the pack are issued before the first store
+        const Pack<T> pg = ldp_at(g, iv); const Pack<T> px = ldp_at(x, iv);
+        Pack<T> psk[5]; Pack<T> pyk[5];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) { psk[k] = ldp_at(static_cast<const T*>(P.s[k]), iv); pyk[k] = ldp_at(static_cast<const T*>(P.y[k]), iv); }
+        Pack<T> od, ox;
+#pragma unroll
+        for (int u = 0; u < VEC; ++u) {
+            T sv[5], yv[5];
+#pragma unroll
+            for (int k = 0; k < 5; ++k) { sv[k] = psk[k].v[u]; yv[k] = pyk[k].v[u]; }
+            od.v[u] = compose_elem(c, pg.v[u], sv, yv);
+            const T v = one * od.v[u];
+            ox.v[u] = px.v[u] + v;
+        }
+        const size_t e0 = iv * VEC;
+        // tile[ii][jj][a][b]: the piece starts at site max(j0, i + 1)
+        T* const dst = tile + (size_t)(ii * JC + (max(j0, i0 + ii + 1) - j0)) * Q2;
+        if (e0 >= lo && e0 + VEC <= hi) {
+            stp_at(d, iv, od); stp_at(xt, iv, ox);
+#pragma unroll
+            for (int u = 0; u < VEC; ++u) dst[e0 + u - lo] = ox.v[u];
+        } else {
+#pragma unroll
+            for (int u = 0; u < VEC; ++u) {
+                const size_t e = e0 + u;
+                if (e >= lo && e < hi) { d[e] = od.v[u]; xt[e] = ox.v[u]; dst[e - lo] = ox.v[u]; }
+            }
+        }
+    }
+    __syncthreads();
+    // Both triangles are walked row by row of W, a thread stepping kFusedStepThreads elements at a time with its (row, column)
+    // kept up by additions.  tile[(ii JC + jj) q^2 + a q + b] with row = ii q + a, col = jj q + b is
+    // tile[row q + ii (JC - 1) q^2 + col + jj (q - 1) q].
+    // rows (i, a), columns (j, b): runs over the workgroup's sites j
+    {
+        constexpr int WD = JC * Q;
+        int row = tid / WD, col = tid % WD;
+        while (row < TI * Q) {
+            const int ii = row / Q, jj = col / Q;
+            const int i = i0 + ii, j = j0 + jj;
+            if (j > i && j < j1) W[(size_t)(i0 * Q + row) * Cs + j0 * Q + col] = tile[row * Q + ii * ((JC - 1) * Q2) + col + jj * ((Q - 1) * Q)];
+            row += kFusedStepThreads / WD; col += kFusedStepThreads % WD;
+            if (col >= WD) { col -= WD; ++row; }
+        }
+    }
+    // rows (j, b), columns (i, a): runs over the tile's sites i
+    {
+        constexpr int WD = TI * Q;
+        int row = tid / WD, col = tid % WD;
+        while (row < JC * Q) {
+            const int jj = row / Q, ii = col / Q;
+            const int i = i0 + ii, j = j0 + jj;
+            if (j > i && j < j1) W[(size_t)(j0 * Q + row) * Cs + i0 * Q + col] = tile[col * Q + ii * ((JC - 1) * Q2) + row + jj * ((Q - 1) * Q)];
+            row += kFusedStepThreads / WD; col += kFusedStepThreads % WD;
+            if (col >= WD) { col -= WD; ++row; }
+        }
+    }
+}
+
 // out[k] = sum_b of the (hi, lo) pairs partials[2 * (k*nb + b)], k < nk, rounded once; one block per k, fixed tree
 __global__ __launch_bounds__(256)
 void vec_final_kernel(const double* __restrict__ partials, int nb, int nk, double* __restrict__ out)

@@ -103,6 +103,9 @@ struct PlmEngine : PlmEngineBase {
         double last_step = 0;                 // step length the last completed iteration accepted (lbfgs_progress_t's `step`)
         double dginit = 0;                    // g.d of the current search direction
         bool dginit_on_device = false;        // ... still in dScal[kSlotDginit]: read with the next evaluation's scalars
+        // the fused step pass (lbfgs_dir_trial_expand_kernel) ran for the pending direction: dxp and W hold x + 1 * d.  Whatever
+        // rewrites x, d or W outside the line search's first trial clears it (the resets of `o` do so by themselves)
+        bool trial_ready = false;
     } o;
 
     explicit PlmEngine(dca_ctx* c) : ctx(c), N(c->N), L(c->L), q(c->q), Ls(c->Ls) {}
@@ -286,6 +289,7 @@ struct PlmEngine : PlmEngineBase {
             const T av = s / (T)q;
             for (int a = 0; a < q; ++a) hi[a] -= av;
         }
+        o.trial_ready = false;
         HIP_TRY(hipMemsetAsync(dx, 0, plan.P * sizeof(T), ctx->stream));
         HIP_TRY(hipMemcpyAsync(dx, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -310,6 +314,7 @@ struct PlmEngine : PlmEngineBase {
     int set_x(const void* x, int dtype) override
     {
         if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
+        o.trial_ready = false;
         if (dtype == DCA_F32) return upload(static_cast<const float*>(x), dx);
         if (dtype == DCA_F64) return upload(static_cast<const double*>(x), dx);
         return DCA_ERR_ARG;
@@ -331,11 +336,12 @@ struct PlmEngine : PlmEngineBase {
         return DCA_ERR_ARG;
     }
 
-    template <int Q> int launch_eval()
+    // w_ready: W already holds the table of dx (the fused step pass wrote it with the trial point)
+    template <int Q> int launch_eval(bool w_ready)
     {
         hipStream_t st = ctx->stream;
         const size_t npairs = (size_t)L * (L - 1) / 2;
-        {
+        if (!w_ready) {
             ScopedKernelClock kc(ctx, "plm_expand");
             hipLaunchKernelGGL(plm_expand_kernel<T>, dim3((unsigned)npairs), dim3(256), (size_t)q * q * sizeof(T), st,
                                dx, dWt, dPairs, L, q, plan.Cs, plan.cS0, plan.cS1);
@@ -454,11 +460,11 @@ struct PlmEngine : PlmEngineBase {
 
     // leaves fx in ctx->dScal[0] (device); no host sync unless a reduce hook is set
     // defer_fx: the caller is eval_scalars' (one GPU, no hook: nothing reads fx before the dot products are formed)
-    int evaluate_async(bool defer_fx = false)
+    int evaluate_async(bool defer_fx = false, bool w_ready = false)
     {
         if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
         deferFx = defer_fx && knobs.fuseFx != 0 && native_mode == 0 && !hook && !comm && !stripEmulate;
-        int rc = (q == 21) ? launch_eval<21>() : launch_eval<5>();
+        int rc = (q == 21) ? launch_eval<21>(w_ready) : launch_eval<5>(w_ready);
         if (rc != DCA_OK) return rc;
         o.evals += 1;
         if (native_mode == 4) {
@@ -650,6 +656,7 @@ struct PlmEngine : PlmEngineBase {
 
     int gradient(double* fx_out) override
     {
+        o.trial_ready = false;              // W becomes the table of the accepted point
         DCA_TRY(evaluate_async());
         DCA_TRY(reduce_scalars(0, 1));
         DCA_TRY(gather_vector(dg));
@@ -726,11 +733,17 @@ struct PlmEngine : PlmEngineBase {
         // g.d of the direction: known on the host, or still on its way from the device's two-loop recursion -- then
         // eval_scalars brings it into o.dginit with the scalars of the first evaluation
         const bool deferred = o.dginit_on_device;
+        bool first = true;
         const int ls = mt_line_search(params, stp, f, &o.dginit, deferred, [&](double t, double* ft, double* dgt) {
-            v_step(dx, dxp, t, dd);
-            DCA_ROUND_STAGE(32, dx, plan.P);
+            // the fused step pass left this trial point in dx and its table in W: only the first trial, only at step 1 exactly
+            const bool ready = o.trial_ready && first && t == 1.0 && fused_step_ok();
+            o.trial_ready = false; first = false;
+            if (!ready) {
+                v_step(dx, dxp, t, dd);
+                DCA_ROUND_STAGE(32, dx, plan.P);
+            }
             DCA_TRY(publish_x());                 // sharded vectors: every rank needs the x its evaluation reads
-            DCA_TRY(evaluate_async(true));
+            DCA_TRY(evaluate_async(true, ready));
             return eval_scalars(ft, dgt, xx, gg);
         }, rc_hip);
         if (deferred && ls == LB_INCREASEGRADIENT) o.evals -= 1;     // the reference returns before evaluating (lbfgs.cpp:858-861); the caller restores x, g
@@ -738,6 +751,23 @@ struct PlmEngine : PlmEngineBase {
     }
 
     void lbfgs_end() override { o = decltype(o)(); }
+    // The fused step pass is for the plain one-GPU path: everything else keeps the three kernels.
+    bool fused_step_ok() const
+    {
+#ifdef DCA_ROUND_ABLATE
+        if (round_stage_mask()) return false;
+#endif
+        return knobs.fuseStep != 0 && native_mode == 0 && !hook && !comm && !strips && !stripEmulate && vlo == 0 && vn == plan.P &&
+               plan.cS0 == 0 && plan.cS1 == L;
+    }
+    // d, the trial point x + 1 * d (into dxp: the next iteration's swap makes it dx) and its table W
+    template <int Q> void launch_fused_step(const VecPtrs5& ptrs)
+    {
+        const int numJC = ceil_div(L, fused_step_jc(Q)), pairBlocks = ceil_div(L, fused_step_ti(Q, (int)sizeof(T))) * numJC;
+        const size_t lds = (size_t)fused_step_ti(Q, (int)sizeof(T)) * fused_step_jc(Q) * Q * Q * sizeof(T);
+        hipLaunchKernelGGL((lbfgs_dir_trial_expand_kernel<T, Q>), dim3((unsigned)(ceil_div(pairBlocks, 64) * 64 + ceil_div(L * Q, kFusedStepThreads))), dim3(kFusedStepThreads), lds,
+                           ctx->stream, dd, dxp, dWt, dx, dg, ptrs, &dLb->cf, L, plan.Cs, numJC, pairBlocks);
+    }
     int lbfgs_iterate(int iterations, dca_plm_stats* st) override
     {
         if (!o.begun) { dca_set_error("dca_plm_lbfgs_begin first"); return DCA_ERR_STATE; }
@@ -755,6 +785,7 @@ struct PlmEngine : PlmEngineBase {
             if (ls < 0) {   // revert to the previous point (lbfgs.cpp:478-484)
                 std::swap(dx, dxp);
                 std::swap(dg, dgp);
+                o.trial_ready = false;
                 o.status = ls; o.finished = true;
                 break;
             }
@@ -797,8 +828,13 @@ struct PlmEngine : PlmEngineBase {
                 // two-loop recursion on the device (no host round trip), then d = cf.g g + sum cf.s_k s_k + cf.y_k y_k
                 ScopedKernelClock kc(ctx, "lbfgs_vec");
                 hipLaunchKernelGGL(lbfgs_two_loop_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->dScal, dLb, e, o.end, bound, gg);
-                hipLaunchKernelGGL(vec_compose_kernel<T>, dim3(kVecBlocks), dim3(kVecThreads), 0, ctx->stream, dd + vlo, dg + vlo, ptrs, &dLb->cf, vn);
-                DCA_ROUND_STAGE(64, dd, plan.P);
+                if (fused_step_ok()) {
+                    if (q == 21) launch_fused_step<21>(ptrs); else launch_fused_step<5>(ptrs);
+                    o.trial_ready = true;
+                } else {
+                    hipLaunchKernelGGL(vec_compose_kernel<T>, dim3(kVecBlocks), dim3(kVecThreads), 0, ctx->stream, dd + vlo, dg + vlo, ptrs, &dLb->cf, vn);
+                    DCA_ROUND_STAGE(64, dd, plan.P);
+                }
                 o.dginit_on_device = true;
             }
             o.step = 1.0;

@@ -50,8 +50,9 @@ struct PlmKnobs {
     int scatterMerge = -1;      // DCA_SCATTER_MERGE: 0 = the left-over strips as a launch of their own
     int foldMerge = -1;         // DCA_FOLD_MERGE: 0 = the field fold as a launch of its own
     int fuseFx = -1;            // DCA_PLM_FUSE_FX: 0 = fx summed by its own two kernels
+    int fuseStep = -1;          // DCA_PLM_FUSE_STEP: 0 = direction, trial point and expand as their own three kernels
     bool is_set(int v) const { return v != -1; }
-    // the only place where the engine reads these eight variables: once per configure
+    // the only place where the engine reads these nine variables: once per configure
     static PlmKnobs from_env()
     {
         PlmKnobs k;
@@ -59,6 +60,7 @@ struct PlmKnobs {
         rd("DCA_SCATTER_REM", k.scatterRem); rd("DCA_SCATTER_SPLIT", k.scatterSplit); rd("DCA_SCATTER_CANON", k.scatterCanon);
         rd("DCA_SCATTER_WAVES", k.scatterWaves); rd("DCA_PLM_PAIRS", k.plmPairs); rd("DCA_SCATTER_MERGE", k.scatterMerge);
         rd("DCA_FOLD_MERGE", k.foldMerge); rd("DCA_PLM_FUSE_FX", k.fuseFx);
+        rd("DCA_PLM_FUSE_STEP", k.fuseStep);
         return k;
     }
 };
