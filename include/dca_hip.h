@@ -677,12 +677,48 @@ int dca_three_site_values(dca_ctx* ctx, const uint8_t* Q, int nq, const int32_t*
 int dca_three_site_scan(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int skip_state,
                         int32_t* elements_out, double* c3_out, double* f3_out, int* found);
 
+/* Principal components of the reweighted alignment and projections of sequence sets onto them.
+ * With x_n the L q one-hot row of sequence n (all q states, the gap included, columns in the context's order), w_n the context's
+ * double weights and Meff = sum_n w_n:  f(i,a) = sum_n w_n [s_ni = a] / Meff,  C = sum_n w_n (x_n - f)(x_n - f)^T / Meff  (L q x
+ * L q; its blocks are f_ij - f_i f_j^T, the diagonal blocks included; never formed), total_variance = trace C = sum_i (1 -
+ * sum_a f(i,a)^2).
+ *
+ * dca_pca_fit: the k largest eigenpairs (lambda_m, v_m) of C, lambda descending, ||v_m|| = 1, the entry of v_m of largest
+ * magnitude positive (ties: the smallest index); components_out holds v_m at [m * L q + i q + a].  offsets_out[m] = c_m = sum
+ * over (i,a) ascending of f(i,a) v_m(i,a), one double chain.  Block subspace iteration with Rayleigh-Ritz on b = min(L q, k + 8)
+ * vectors whose start is a function of (seed, element) alone; one iteration applies C to the block by two passes over the code
+ * bytes.  residuals_out[m] = ||C v_m - lambda_m v_m|| as the last iteration evaluated it; the fit is converged (*converged_out
+ * = 1) when every one of the k is <= tol * lambda_1.  Out of iterations: DCA_OK with *converged_out = 0 and the residuals.  A
+ * component with lambda_m <= tol * lambda_1 is NULL: eigenvalue 0, an all-zero vector and offset (rank C < k, one sequence, a
+ * constant alignment; a trace of at most 4 L 2^-52 counts as C = 0 and returns k null components after 0 iterations).
+ * No float atomics; every sum runs in an order fixed by (N, L, q, b): the back-projection walks slabs of DCA_PCA_SLAB sequences
+ * in ascending order and adds the slabs ascending, so two calls with the same arguments return the same bits.
+ * residuals_out, total_variance_out and iterations_out may be NULL.
+ *
+ * dca_pca_project: proj_out[n * k + m] = (sum over the sites i ascending of v_m(i, s_ni)) - c_m: one double chain, then one
+ * subtraction, no contraction -- a pure function of (v_m, c_m, s_n), so a sequence has the same bits alone, in any batch and
+ * under any pass split.  Q == NULL: the context's alignment (nq ignored); else nq x L host codes, uploaded in passes of at most
+ * DCA_NN_PASS rows (the variable of dca_hamming_nearest).  components (k * L q) and offsets (k) are host arrays as dca_pca_fit
+ * returns them; any k >= 1 values are taken as given.
+ *
+ * Both are model-free and stateless: the alignment, the weights and any fitted model stay untouched; one GPU.
+ * DCA_ERR_STATE: no alignment; no weights (dca_pca_fit).  DCA_ERR_ARG: k < 1, k > min(64, L q) (dca_pca_fit), tol <= 0,
+ * max_iterations < 1, a NULL output or input, nq < 1 with Q, a code >= q, a NULL context.  Profiling tags "pca_project",
+ * "pca_back" (the slab sums and their reduction), "pca_small" (b x b products and rotations).  No reference counterpart. */
+#define DCA_PCA_SLAB 1024
+int dca_pca_fit(dca_ctx* ctx, int k, double tol, int max_iterations, uint64_t seed,
+                double* eigenvalues_out /* k */, double* components_out /* k*L*q */, double* offsets_out /* k */,
+                double* residuals_out /* k, may be NULL */, double* total_variance_out /* may be NULL */,
+                int* iterations_out /* may be NULL */, int* converged_out);
+int dca_pca_project(dca_ctx* ctx, const uint8_t* Q, int nq /* Q == NULL: the context's alignment */, int k,
+                    const double* components /* k*L*q, host */, const double* offsets /* k */, double* proj_out /* nq*k */);
+
 /* ------------------------------------------------------------------ timing
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
  * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "ar_logits", "ar_grad", "ar_sample", "ar_epistasis",
- * "bm_stats", "ais", "hamming", "set_compare", "three_site_scan", "three_site_values"). */
+ * "bm_stats", "ais", "hamming", "set_compare", "three_site_scan", "three_site_values", "pca_project", "pca_back", "pca_small"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it
  * instead of two per stage (an event record costs the stream ~5 us: 14 per plmDCA iteration are 5 % of config C's step, 0.4 % of

@@ -1,6 +1,7 @@
-"""Comparing sequence sets with the alignment (DESIGN.md sections 17 and 20): Hamming distances to the nearest natural sequence,
-the agreement of one- and two-site frequencies and connected correlations and, beyond what a pairwise fit has seen, of the
-strongest three-site connected correlations.  Model-free -- the methods need the alignment and its
+"""Comparing sequence sets with the alignment (DESIGN.md sections 17, 20 and 21): Hamming distances to the nearest natural sequence,
+the agreement of one- and two-site frequencies and connected correlations, beyond what a pairwise fit has seen, of the
+strongest three-site connected correlations, and the principal components of the reweighted alignment with the projections
+of natural and generated sequences onto them.  Model-free -- the methods need the alignment and its
 sequence weights, never fitted parameters -- so one mixin serves PlmDCA, MeanFieldDCA and ArDCA, before or after a fit."""
 import numpy as np
 
@@ -177,7 +178,59 @@ class SequenceComparison:
         _count, _denom, f3, c3 = self._compare_context().three_site_values(el if order is None else elements_to_order(el, order), Q)
         return f3, c3
 
-    def compare_with_alignment(self, sequences, return_frequencies=False, three_site=0, three_site_include_gaps=True):
+    def _pca_fit(self, num_components, tolerance, max_iterations, seed):
+        """The fit in the context's column order, cached per argument tuple."""
+        _bio, L, q = self._compare_dims()
+        try:
+            key = _lib.pca_arguments(num_components, tolerance, max_iterations, seed, L, q)
+        except ValueError as e:
+            raise self._compare_exc(str(e))
+        self._compare_one_gpu('compute_principal_components')
+        cache = self.__dict__.setdefault('_pca_cache', {})
+        if key not in cache:
+            k, tol, iters, sd = key
+            self._compare_logger.info('\n\t{} principal components of the reweighted alignment'.format(k))
+            fit = self._compare_context().pca_fit(k, tol, iters, sd)
+            if not fit['converged']:
+                lam1 = float(fit['eigenvalues'][0])
+                worst = int(np.argmax(fit['residuals']))
+                raise self._compare_exc('the principal components did not converge in {} iterations: component {} has the residual '
+                                        '{:.3e}, above tolerance * lambda_1 = {:.3e}'.format(fit['iterations'], worst,
+                                                                                            float(fit['residuals'][worst]), tol * lam1))
+            cache[key] = fit
+        return cache[key]
+
+    def compute_principal_components(self, num_components=2, tolerance=1e-10, max_iterations=1000, seed=0):
+        """The num_components largest eigenpairs of the covariance C = sum_n w_n (x_n - f)(x_n - f)^T / Meff of the one-hot
+        alignment under its sequence weights (all q states, the gap included; include/dca_hip.h: dca_pca_fit) -> dict:
+        eigenvalues float64[k] (descending), components float64[k, L, q] (unit vectors, sites in file order, the entry of largest
+        magnitude positive), offsets float64[k] (c_m = sum f v_m), explained_variance_ratio (eigenvalues / total_variance),
+        total_variance (the trace of C), residuals float64[k] (||C v - lambda v||) and iterations.  The fit stops when every
+        residual is <= tolerance * lambda_1; a component with lambda <= tolerance * lambda_1 is null (zeros).  Cached per
+        argument tuple; a fit that does not converge within max_iterations raises.  seed picks the start block."""
+        fit = self._pca_fit(num_components, tolerance, max_iterations, seed)
+        comp = fit['components']
+        order = self._compare_order()
+        if order is not None:
+            full = np.empty_like(comp)
+            full[:, order, :] = comp
+            comp = full
+        total = float(fit['total_variance'])
+        lam = fit['eigenvalues'].copy()
+        return {'eigenvalues': lam, 'components': comp.copy(), 'offsets': fit['offsets'].copy(),
+                'explained_variance_ratio': lam / total if total > 0.0 else np.zeros_like(lam), 'total_variance': total,
+                'residuals': fit['residuals'].copy(), 'iterations': int(fit['iterations'])}
+
+    def project_sequences(self, sequences=None, num_components=2, tolerance=1e-10, max_iterations=1000, seed=0):
+        """Coordinates of the sequences (a FASTA path or a list of aligned strings; None: the rows of the alignment the instance
+        fits on) along the principal components of compute_principal_components(num_components, ...) -> float64[n, k]:
+        p_m(s) = sum_i v_m(i, s_i) - c_m, so the alignment's weighted mean is 0 and its weighted variance lambda_m.  A sequence
+        has the same coordinates alone and in any batch."""
+        fit = self._pca_fit(num_components, tolerance, max_iterations, seed)
+        Q = None if sequences is None else self._compare_codes(sequences, 'project_sequences')
+        return self._compare_context().pca_project(fit['components'], fit['offsets'], Q)
+
+    def compare_with_alignment(self, sequences, return_frequencies=False, three_site=0, three_site_include_gaps=True, pca=0):
         """Do the sequences reproduce the alignment's statistics?  -> dict: pearson_fi / pearson_fij / pearson_cij, slope_* and
         max_abs_diff_* of the set's one-site frequencies, two-site frequencies and connected correlations c_ij(a, b) = f_ij(a, b)
         - f_i(a) f_j(b) against the alignment's under its sequence weights (no pseudocount; x = alignment, y = set; all states,
@@ -187,12 +240,17 @@ class SequenceComparison:
         sites in file order.  three_site = K > 0 adds the check on a statistic the fit never saw: the alignment's K strongest
         three-site connected correlations (compute_top_three_site_correlations, with three_site_include_gaps) against the set's
         values at the same elements -- pearson_cijk, slope_cijk, max_abs_diff_cijk (same definitions, analytic mean 0) and
-        three_site_terms, the number of elements compared."""
+        three_site_terms, the number of elements compared.  pca = K > 0 adds pca_eigenvalues (the alignment's K largest,
+        compute_principal_components) and pca_set_mean / pca_set_variance, float64[K]: the set's unweighted mean and variance
+        along each component (the alignment's own, under its weights, are 0 and the eigenvalue)."""
         rf = _flag('return_frequencies', return_frequencies, self._compare_exc)
         K3 = self._three_site_count('three_site', three_site)
         if K3 < 0:
             raise self._compare_exc('three_site must be >= 0, not {}'.format(K3))
         skip3 = self._three_site_skip(three_site_include_gaps, 'three_site_include_gaps')
+        Kp = self._three_site_count('pca', pca)
+        if Kp < 0:
+            raise self._compare_exc('pca must be >= 0, not {}'.format(Kp))
         self._compare_one_gpu('compare_with_alignment')
         Q = self._compare_codes(sequences, 'compare_with_alignment')
         ctx = self._compare_context()
@@ -212,6 +270,12 @@ class SequenceComparison:
             y3 = ctx.three_site_values(el, Q)[3] if el.shape[0] else np.zeros(0)
             out['pearson_cijk'], out['slope_cijk'], out['max_abs_diff_cijk'] = centred_fit(x3, y3)
             out['three_site_terms'] = int(el.shape[0])
+        if Kp > 0:
+            fit = self._pca_fit(Kp, 1e-10, 1000, 0)
+            p = ctx.pca_project(fit['components'], fit['offsets'], Q)
+            mean = p.mean(axis=0)
+            out['pca_eigenvalues'] = fit['eigenvalues'].copy()
+            out['pca_set_mean'], out['pca_set_variance'] = mean, ((p - mean[None, :]) ** 2).mean(axis=0)
         if rf:
             order = self._compare_order()
             if order is not None:
@@ -222,18 +286,82 @@ class SequenceComparison:
         return out
 
 
-def run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type, three_site=0, three_site_include_gaps=True):
+def run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type, three_site=0, three_site_include_gaps=True,
+                pca=0):
     """compare_sequences of the plmdca, mfdca and ardca command lines -> the path of <output_dir>/<prefix>_sequence_comparison_
-    <alignment base>.txt (dca_utilities.write_sequence_comparison).  No fit is run."""
+    <alignment base>.txt (dca_utilities.write_sequence_comparison).  pca = K > 0 adds the header lines pca_eigenvalues_<m>,
+    pca_set_mean_<m> and pca_set_variance_<m>, m = 1..K.  No fit is run."""
     from .dca_utilities import dca_utilities
     if not query_file:
         raise exc_type('compare_sequences needs --query_file')
     dca_utilities.create_directories(output_dir)
     extra = dict(three_site=int(three_site), three_site_include_gaps=bool(three_site_include_gaps)) if three_site else {}
-    summary = instance.compare_with_alignment(query_file, **extra)
+    if pca:
+        extra['pca'] = int(pca)
+    summary = dict(instance.compare_with_alignment(query_file, **extra))
+    for key in ('pca_eigenvalues', 'pca_set_mean', 'pca_set_variance'):        # the header takes scalars: one line per component
+        for m, v in enumerate(summary.pop(key, ())):
+            summary['{}_{}'.format(key, m + 1)] = float(v)
     dist, index, hist = instance.compute_distances_to_alignment(query_file, return_index=True, return_histogram=True)
     _d, self_hist = instance.compute_alignment_self_distances(return_histogram=True)
     path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_sequence_comparison_', postfix='.txt')
     dca_utilities.write_sequence_comparison(path, summary, dist, index, hist, self_hist, int(instance.sequences_len), metadata=metadata,
                                             query_file=query_file)
     return path
+
+
+def add_pca_arguments(p):
+    """The options of the compute_pca sub-command of the plmdca, mfdca and ardca command lines."""
+    p.add_argument('--num_components', type=int, default=2, help='number of principal components, 1 .. 64 (addition)')
+    p.add_argument('--query_file', help='FASTA file of aligned sequences to project besides the alignment (addition)')
+    p.add_argument('--seed', type=int, default=0, help='seed of the start block of the subspace iteration (addition)')
+
+
+def run_pca(instance, prefix, msa_file, output_dir, metadata, query_file=None, num_components=None, seed=None):
+    """compute_pca of the plmdca, mfdca and ardca command lines -> the paths written under <output_dir>:
+    <prefix>_pca_<alignment base>.txt (per component: eigenvalue, explained ratio, residual; the iterations in the header),
+    <prefix>_pca_components_<alignment base>.npy (float64[k, L, q]), <prefix>_pca_projections_<alignment base>.txt (row, weight,
+    coordinates of every alignment row) and, with a query file, <prefix>_pca_query_projections_<alignment base>.txt (record,
+    coordinates).  No model is fitted."""
+    from .dca_utilities import dca_utilities
+    dca_utilities.create_directories(output_dir)
+    k = 2 if num_components is None else num_components
+    sd = 0 if seed is None else seed
+    fit = instance.compute_principal_components(num_components=k, seed=sd)
+    proj = instance.project_sequences(None, num_components=k, seed=sd)
+    weights = instance._compare_context().weights()
+    path = lambda what, postfix: dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_' + what + '_', postfix=postfix)
+    rule = '#' + '=' * 100
+    g = lambda v: '%.17g' % float(v)
+
+    def write(name, header, rows):
+        with open(name, 'w') as fh:
+            for line in header:
+                fh.write(line + '\n')
+            for row in rows:
+                fh.write(row + '\n')
+
+    summary, comps, projections = path('pca', '.txt'), path('pca_components', '.npy'), path('pca_projections', '.txt')
+    head = [rule] + list(metadata or []) + [
+        '#\tPrincipal components of the reweighted one-hot alignment: {}'.format(len(fit['eigenvalues'])),
+        '#\tTotal variance (trace of the covariance): {}'.format(g(fit['total_variance'])),
+        '#\tIterations: {}'.format(int(fit['iterations'])),
+        '# The First column is the component (1-based), the Second its eigenvalue, the Third the explained variance ratio',
+        '# and the Fourth the residual ||C v - lambda v||', rule]
+    write(summary, head, ('{0:<5} {1} {2} {3}'.format(m + 1, g(fit['eigenvalues'][m]), g(fit['explained_variance_ratio'][m]),
+                                                       g(fit['residuals'][m])) for m in range(len(fit['eigenvalues']))))
+    np.save(comps, fit['components'])
+    head = [rule] + list(metadata or []) + [
+        '# The First column is the alignment row (0-based), the Second its sequence weight, then its coordinate along every component',
+        rule]
+    write(projections, head, ('{0:<7} {1} {2}'.format(n, g(weights[n]), ' '.join(g(v) for v in proj[n])) for n in range(proj.shape[0])))
+    out = [summary, comps, projections]
+    if query_file:
+        qp = instance.project_sequences(query_file, num_components=k, seed=sd)
+        queries = path('pca_query_projections', '.txt')
+        head = [rule] + list(metadata or []) + ['#\tQuery sequences: {}'.format(query_file),
+                                                '# The First column is the record number (1-based) of the query sequence, then its coordinate along every component',
+                                                rule]
+        write(queries, head, ('{0:<7} {1}'.format(n + 1, ' '.join(g(v) for v in qp[n])) for n in range(qp.shape[0])))
+        out.append(queries)
+    return tuple(out)

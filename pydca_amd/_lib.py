@@ -173,6 +173,8 @@ def lib():
         "dca_alignment_statistics": (i, [vp, vp, vp]),
         "dca_three_site_values": (i, [vp, vp, i, vp, i, vp, vp, vp, vp]),
         "dca_three_site_scan": (i, [vp, vp, i, i, i, vp, vp, vp, C.POINTER(i)]),
+        "dca_pca_fit": (i, [vp, i, d, i, C.c_uint64, vp, vp, vp, vp, C.POINTER(d), C.POINTER(i), C.POINTER(i)]),
+        "dca_pca_project": (i, [vp, vp, i, i, vp, vp, vp]),
         "dca_plm_ais": (i, [vp, C.POINTER(AisArgs), vp, C.POINTER(d), vp]),
         "dca_mf_ais": (i, [vp, C.POINTER(AisArgs), vp, C.POINTER(d), vp]),
         "dca_ais_estimate": (i, [vp, i, d, C.POINTER(d), C.POINTER(d), C.POINTER(d)]),
@@ -224,7 +226,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_plm_bm_begin", "dca_plm_bm_iterate", "dca_plm_bm_freqs", "dca_plm_bm_chains", "dca_plm_bm_end",
            "dca_plm_ais", "dca_mf_ais", "dca_ais_estimate",
            "dca_hamming_nearest", "dca_sequence_statistics", "dca_alignment_statistics",
-           "dca_three_site_values", "dca_three_site_scan",
+           "dca_three_site_values", "dca_three_site_scan", "dca_pca_fit", "dca_pca_project",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
            "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
@@ -254,6 +256,33 @@ def three_site_elements(elements, L, q):
         k = int(np.argmax(bad))
         raise ValueError("element %d names the states %s; states are 0 .. %d" % (k, tuple(int(v) for v in st[k]), q - 1))
     return np.ascontiguousarray(big, dtype=np.int32)
+
+
+PCA_SLAB = 1024            # DCA_PCA_SLAB (include/dca_hip.h): sequences per slab of the back-projection's fixed summation order
+PCA_MAX_COMPONENTS = 64
+
+
+def pca_arguments(num_components, tolerance, max_iterations, seed, L, q):
+    """The arguments of dca_pca_fit, checked as the library checks them -> (k, tol, max_iterations, seed); ValueError
+    otherwise.  Needs no device."""
+    def integer(name, v):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer, not %r" % (name, v))
+        return int(v)
+    k, it, sd = integer("num_components", num_components), integer("max_iterations", max_iterations), integer("seed", seed)
+    cap = min(PCA_MAX_COMPONENTS, int(L) * int(q))
+    if k < 1 or k > cap:
+        raise ValueError("num_components must be between 1 and min(%d, L q) = %d, not %d" % (PCA_MAX_COMPONENTS, cap, k))
+    if isinstance(tolerance, (bool, np.bool_)) or not isinstance(tolerance, (int, float, np.integer, np.floating)):
+        raise ValueError("tolerance must be a number, not %r" % (tolerance,))
+    tol = float(tolerance)
+    if not (tol > 0.0) or not np.isfinite(tol):
+        raise ValueError("tolerance must be a finite number > 0, not %r" % (tolerance,))
+    if it < 1:
+        raise ValueError("max_iterations must be >= 1, not %d" % it)
+    if sd < 0 or sd >= 1 << 64:
+        raise ValueError("seed must be in 0 .. 2^64 - 1, not %d" % sd)
+    return k, tol, it, sd
 
 
 def ais_schedule(temperatures, betas=None):
@@ -940,6 +969,33 @@ class Context:
                                           int(skip_state), _ptr(el), _ptr(c3), _ptr(f3), C.byref(found)))
         n = found.value
         return el[:n].copy(), c3[:n].copy(), f3[:n].copy()
+
+    # ---- principal components of the reweighted alignment (pca.hip): model-free, nothing of the context changes
+    def pca_fit(self, k, tol=1e-10, max_iterations=1000, seed=0):
+        """dca_pca_fit -> dict: eigenvalues float64[k], components float64[k, L, q] (the context's column order), offsets float64[k],
+        residuals float64[k], total_variance, iterations, converged (bool).  A fit out of iterations returns converged False."""
+        k = int(k)
+        lam, off, res = np.zeros(max(k, 1)), np.zeros(max(k, 1)), np.zeros(max(k, 1))
+        comp = np.zeros((max(k, 1), self.L, self.q), dtype=np.float64)
+        total, it, conv = C.c_double(0), C.c_int(0), C.c_int(0)
+        check(self._l.dca_pca_fit(self._h, k, float(tol), int(max_iterations), int(seed), _ptr(lam), _ptr(comp), _ptr(off), _ptr(res),
+                                  C.byref(total), C.byref(it), C.byref(conv)))
+        return {"eigenvalues": lam, "components": comp, "offsets": off, "residuals": res, "total_variance": total.value,
+                "iterations": it.value, "converged": bool(conv.value)}
+
+    def pca_project(self, components, offsets, Q=None):
+        """dca_pca_project: components float64[k, L, q], offsets float64[k]; Q uint8[n, L] or None (the alignment) -> float64[n, k]"""
+        off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        k = int(off.size)
+        comp = np.ascontiguousarray(components, dtype=np.float64)
+        if comp.size != k * self.L * self.q:
+            raise ValueError("components must hold k x L x q = %d x %d x %d values, not %d" % (k, self.L, self.q, comp.size))
+        q_ = None if Q is None else np.ascontiguousarray(Q, dtype=np.uint8).reshape(-1, self.L)
+        n = self.N if q_ is None else int(q_.shape[0])
+        out = np.zeros((n, max(k, 1)), dtype=np.float64)
+        check(self._l.dca_pca_project(self._h, None if q_ is None else _ptr(q_), 0 if q_ is None else n, k,
+                                      _ptr(comp) if k else None, _ptr(off) if k else None, _ptr(out) if n else None))
+        return out[:, :k]
 
     # ---- log Z by annealed importance sampling (ais.hip) -> (float64[n] log weights, log Z0, uint8[n, L] final chains or None)
     def _ais(self, fn, chains, temperatures, sweeps_per_temperature, seed, first_chain, betas, base_fields, return_chains):

@@ -131,7 +131,7 @@ def log_likelihood(energies, weights, meff, log_z):
 
 
 POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences', 'compute_log_likelihood',
-                     'compute_pseudo_log_likelihood', 'compare_sequences')
+                     'compute_pseudo_log_likelihood', 'compare_sequences', 'compute_pca')
 
 
 def pll_flag(per_site, exc_type):
@@ -318,11 +318,12 @@ def run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, opts):
 
 
 def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata, biomolecule, table, exc_type,
-                   query_file=None, wildtype_file=None, sampling=None, ais=None, three_site=0, three_site_no_gaps=False):
+                   query_file=None, wildtype_file=None, sampling=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None):
     """compute_energies / compute_mutation_effects / sample_sequences / compute_pseudo_log_likelihood / compare_sequences of the
     plmdca and mfdca command lines -> the path of the file written: <output_dir>/<prefix>_energies_<alignment base>.txt,
     <prefix>_mutation_effects_<alignment base>.txt, <prefix>_samples_<alignment base>.fa,
-    <prefix>_pseudo_log_likelihoods_<alignment base>.txt or <prefix>_sequence_comparison_<alignment base>.txt.  sampling: the sample_sequences options (num_sequences, num_sweeps, seed,
+    <prefix>_pseudo_log_likelihoods_<alignment base>.txt or <prefix>_sequence_comparison_<alignment base>.txt; compute_pca -> the
+    paths of _compare.run_pca (pca: its options num_components and seed, and the K of compare_sequences --pca).  sampling: the sample_sequences options (num_sequences, num_sweeps, seed,
     temperature, initial_file)."""
     from .dca_utilities import dca_utilities
     if the_command == 'compute_log_likelihood':
@@ -330,7 +331,12 @@ def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata
     if the_command == 'compare_sequences':
         from . import _compare
         return _compare.run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type, three_site=int(three_site or 0),
-                                    three_site_include_gaps=not three_site_no_gaps)
+                                    three_site_include_gaps=not three_site_no_gaps, pca=int((pca or {}).get('pca') or 0))
+    if the_command == 'compute_pca':
+        from . import _compare
+        opts = dict(pca or {})
+        return _compare.run_pca(instance, prefix, msa_file, output_dir, metadata, query_file=query_file,
+                                num_components=opts.get('num_components'), seed=opts.get('seed'))
     dca_utilities.create_directories(output_dir)
     if the_command == 'sample_sequences':
         opts = dict(sampling or {})

@@ -8,13 +8,13 @@ from argparse import ArgumentParser
 
 import numpy as np
 
-from . import _lib, _potts
+from . import _compare, _lib, _potts
 from .ardca import ardca
 from .dca_utilities import dca_utilities
 
 logger = logging.getLogger(__name__)
 ARDCA_SUBCOMMANDS = ('fit', 'compute_log_probabilities', 'compute_log_likelihood', 'sample_sequences', 'compute_mutation_effects',
-                    'compare_sequences', 'compute_fn', 'compute_epistasis')
+                    'compare_sequences', 'compute_fn', 'compute_epistasis', 'compute_pca')
 _RULE = '#' + '=' * 70
 
 
@@ -73,7 +73,7 @@ def write_mutation_effects(path, dlogp, wildtype_letters, state_letters, metadat
 def execute_from_command_line(biomolecule, msa_file, the_command=None, seqid=None, lambda_h=None, lambda_J=None, max_iterations=None,
                               epsilon=None, order=None, output_dir=None, verbose=False, device=0, query_file=None, wildtype_file=None,
                               num_sequences=None, seed=None, apc=False, refseq_file=None, three_site=0,
-                              three_site_no_gaps=False):
+                              three_site_no_gaps=False, pca=0, num_components=None):
     if verbose:
         logging.basicConfig(level=logging.INFO, format='%(levelname)s %(name)s: %(message)s')
     if the_command not in ARDCA_SUBCOMMANDS:
@@ -96,9 +96,11 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, seqid=Non
         return params, fit_file
     meta = ardca_param_metadata(instance)
     if the_command == 'compare_sequences':
-        from . import _compare
         return _compare.run_compare(instance, 'ARDCA', msa_file, output_dir, meta, query_file, ardca.ArDCAException,
-                                    three_site=int(three_site or 0), three_site_include_gaps=not three_site_no_gaps)
+                                    three_site=int(three_site or 0), three_site_include_gaps=not three_site_no_gaps, pca=int(pca or 0))
+    if the_command == 'compute_pca':
+        return _compare.run_pca(instance, 'ARDCA', msa_file, output_dir, meta, query_file=query_file, num_components=num_components,
+                                seed=seed)
     if the_command == 'compute_log_probabilities':
         logp = instance.compute_sequence_log_probabilities(query_file)
         out = path('log_probabilities', '.txt')
@@ -171,6 +173,10 @@ def build_parser():
                            'connected correlations, found by a scan of all triples, with the set\'s')
             p.add_argument('--three_site_no_gaps', action='store_true', help='leave elements that name the gap state out of '
                            '--three_site')
+            p.add_argument('--pca', type=int, default=0, help='K > 0: also the set\'s mean and variance along the alignment\'s K '
+                           'first principal components')
+        if name == 'compute_pca':
+            _compare.add_pca_arguments(p)
         if name == 'compute_mutation_effects':
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence')
         if name in ('compute_fn', 'compute_epistasis'):
@@ -198,7 +204,8 @@ def run_ardca(argv=None):
         device=args.get('device'), query_file=args.get('query_file'), wildtype_file=args.get('wildtype_file'),
         num_sequences=args.get('num_sequences'), seed=args.get('seed'), apc=bool(args.get('apc')),
         refseq_file=args.get('refseq_file'), three_site=args.get('three_site') or 0,
-        three_site_no_gaps=bool(args.get('three_site_no_gaps')))
+        three_site_no_gaps=bool(args.get('three_site_no_gaps')), pca=args.get('pca') or 0,
+        num_components=args.get('num_components'))
 
 
 if __name__ == '__main__':

@@ -641,6 +641,30 @@ int dca_three_site_scan(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int skip_
     return dca_three_site_scan_impl(ctx, Q, nq, K, skip_state, elements_out, c3_out, f3_out, found);
 }
 
+int dca_pca_fit(dca_ctx* ctx, int k, double tol, int max_iterations, uint64_t seed, double* eigenvalues_out, double* components_out,
+                double* offsets_out, double* residuals_out, double* total_variance_out, int* iterations_out, int* converged_out)
+{
+    CHECK_CTX(ctx);
+    if (!eigenvalues_out || !components_out || !offsets_out || !converged_out) { dca_set_error("dca_pca_fit: eigenvalues_out, components_out, offsets_out or converged_out is NULL"); return DCA_ERR_ARG; }
+    if (!(tol > 0.0)) { dca_set_error("dca_pca_fit: tol %g must be > 0", tol); return DCA_ERR_ARG; }
+    if (max_iterations < 1) { dca_set_error("dca_pca_fit: max_iterations %d < 1", max_iterations); return DCA_ERR_ARG; }
+    if (k < 1) { dca_set_error("dca_pca_fit: k %d < 1", k); return DCA_ERR_ARG; }
+    if (!ctx->dX) { dca_set_error("dca_pca_fit: dca_set_msa first"); return DCA_ERR_STATE; }
+    if (k > 64 || k > ctx->L * ctx->q) { dca_set_error("dca_pca_fit: k %d is more than min(64, L q = %d)", k, ctx->L * ctx->q); return DCA_ERR_ARG; }
+    if (!ctx->have_weights) { dca_set_error("dca_pca_fit: dca_compute_weights or dca_set_weights first"); return DCA_ERR_STATE; }
+    return dca_pca_fit_impl(ctx, k, tol, max_iterations, seed, eigenvalues_out, components_out, offsets_out, residuals_out,
+                            total_variance_out, iterations_out, converged_out);
+}
+int dca_pca_project(dca_ctx* ctx, const uint8_t* Q, int nq, int k, const double* components, const double* offsets, double* proj_out)
+{
+    CHECK_CTX(ctx);
+    if (!components || !offsets || !proj_out) { dca_set_error("dca_pca_project: components, offsets or proj_out is NULL"); return DCA_ERR_ARG; }
+    if (k < 1) { dca_set_error("dca_pca_project: k %d < 1", k); return DCA_ERR_ARG; }
+    if (Q && nq < 1) { dca_set_error("dca_pca_project: nq %d < 1", nq); return DCA_ERR_ARG; }
+    if (!ctx->dX) { dca_set_error("dca_pca_project: dca_set_msa first"); return DCA_ERR_STATE; }
+    return dca_pca_project_impl(ctx, Q, nq, k, components, offsets, proj_out);
+}
+
 int dca_plm_di_scores(dca_ctx* ctx, const double* reg_fi, int apc, double* out)
 {
     CHECK_CTX(ctx);

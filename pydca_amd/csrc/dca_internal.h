@@ -54,7 +54,7 @@ void dca_set_error(const char* fmt, ...);
 static inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// rows per pass of the set entries (dca_hamming_nearest, dca_three_site_values): DCA_NN_PASS, read per call; 32768, at most 2^20
+// rows per pass of the set entries (dca_hamming_nearest, dca_three_site_values, dca_pca_project): DCA_NN_PASS, read per call; 32768, at most 2^20
 static inline int dca_nn_pass_size()
 {
     const char* e = getenv("DCA_NN_PASS");
@@ -323,6 +323,14 @@ int dca_three_site_values_impl(dca_ctx* ctx, const uint8_t* Q, int nq, const int
                                uint64_t* denom_out, double* f3_out, double* c3_out);
 int dca_three_site_scan_impl(dca_ctx* ctx, const uint8_t* Q, int nq, int K, int skip_state, int32_t* elements_out, double* c3_out,
                              double* f3_out, int* found);
+
+// ---- pca.hip : principal components of the reweighted alignment and projections onto them (dca_pca_fit, dca_pca_project;
+// arguments checked in capi.cpp except the codes)
+int dca_pca_fit_impl(dca_ctx* ctx, int k, double tol, int max_iterations, uint64_t seed, double* eigenvalues_out,
+                     double* components_out, double* offsets_out, double* residuals_out, double* total_variance_out,
+                     int* iterations_out, int* converged_out);
+int dca_pca_project_impl(dca_ctx* ctx, const uint8_t* Q, int nq, int k, const double* components, const double* offsets,
+                         double* proj_out);
 
 int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, const double* reg_fi, int L, int q,
                             double* fields_out, double* di_out, const double* fields_in = nullptr);

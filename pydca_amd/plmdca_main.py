@@ -5,7 +5,7 @@ import os
 import sys
 from argparse import ArgumentParser
 
-from . import _lib, _potts
+from . import _compare, _lib, _potts
 from .dca_utilities import dca_utilities
 from .plmdca import plmdca
 from .sequence_backmapper.sequence_backmapper import SequenceBackmapper
@@ -23,7 +23,7 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
                               lambda_J=None, max_iterations=None, apc=False, verbose=False, output_dir=None,
                               num_threads=None, ranked_by=None, linear_dist=None, num_site_pairs=None, device=0,
                               exact_gradient=False, precision=32, devices=None, query_file=None, wildtype_file=None, sampling=None,
-                              boltzmann=None, ais=None, three_site=0, three_site_no_gaps=False):
+                              boltzmann=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None):
     if verbose:
         configure_logging()
     plmdca_instance = plmdca.PlmDCA(msa_file, biomolecule, seqid=seqid, lambda_h=lambda_h, lambda_J=lambda_J,
@@ -36,7 +36,7 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
                                      dca_utilities.plmdca_param_metadata(plmdca_instance),
                                      _lib.DCA_BIOMOLECULE_PROTEIN if plmdca_instance.biomolecule == 'PROTEIN' else _lib.DCA_BIOMOLECULE_RNA, 0,
                                      plmdca.PlmDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling,
-                                     ais=ais, three_site=three_site, three_site_no_gaps=bool(three_site_no_gaps))
+                                     ais=ais, three_site=three_site, three_site_no_gaps=bool(three_site_no_gaps), pca=pca)
     if the_command == BOLTZMANN_SUBCOMMAND:
         if not output_dir:
             output_dir = 'PLMDCA_output_' + os.path.splitext(os.path.basename(msa_file))[0]
@@ -120,6 +120,10 @@ def run_plm_dca(argv=None):
                            'connected correlations, found by a scan of all triples, with the set\'s (addition)')
             p.add_argument('--three_site_no_gaps', action='store_true', help='leave elements that name the gap state out of '
                            '--three_site (addition)')
+            p.add_argument('--pca', type=int, default=0, help='K > 0: also the set\'s mean and variance along the alignment\'s K '
+                           'first principal components (addition)')
+        if name == 'compute_pca':
+            _compare.add_pca_arguments(p)
         if name == 'compute_mutation_effects':
             p.add_argument('--wildtype_file', required=True, help='FASTA file with one aligned wild-type sequence (addition)')
         if name == 'sample_sequences':
@@ -153,7 +157,8 @@ def run_plm_dca(argv=None):
         sampling={k: args.get(k) for k in ('num_sequences', 'num_sweeps', 'seed', 'temperature', 'initial_file')},
         boltzmann={k: args.get(k) for k in _potts.BOLTZMANN_OPTIONS},
         ais={k: args.get(k) for k in _potts.AIS_OPTIONS},
-        three_site=args.get('three_site') or 0, three_site_no_gaps=bool(args.get('three_site_no_gaps')))
+        three_site=args.get('three_site') or 0, three_site_no_gaps=bool(args.get('three_site_no_gaps')),
+        pca={k: args.get(k) for k in ('pca', 'num_components', 'seed')})
 
 
 if __name__ == '__main__':
