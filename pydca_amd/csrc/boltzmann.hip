@@ -18,8 +18,7 @@
 
 namespace {
 
-constexpr int kBmThreads = 256;
-constexpr int kBmSums = 6;                 // slab: max |d|, sum Cd, sum Cm, sum Cd^2, sum Cm^2, sum Cd Cm
+// kBmThreads, kBmSums (slab: max |d|, sum Cd, sum Cm, sum Cd^2, sum Cm^2, sum Cd Cm) and bm_tile: potts_plan.h
 
 // theta' = theta + eta * ((f - g) - mu * theta), every step in double, rounded once to S
 template <typename S>
@@ -69,6 +68,7 @@ void bm_pairs_kernel(const uint8_t* __restrict__ st, int nS, int n, int L, int q
     extern __shared__ __attribute__((aligned(16))) unsigned char bm_smem[];
     uint32_t* hist = reinterpret_cast<uint32_t*>(bm_smem);              // [TB * TB][q * q]
     __shared__ double red[kBmSums][kBmThreads];
+    static_assert(sizeof(red) == kBmStaticLds, "potts_plan.h holds the static LDS of this kernel");
     const int I = blockIdx.y, J = blockIdx.x;
     if (J < I) return;
     const int t = threadIdx.x, qq = q * q, i0 = I * TB, j0 = J * TB;
@@ -173,14 +173,11 @@ struct BmRun {
 
 namespace {
 
-// site-pair tile edge: the tile's histogram (TB^2 q^2 uint32) stays within 64 KiB
-int bm_tile(int q) { return q <= 8 ? 16 : q <= 24 ? 4 : 2; }
-
 template <typename S, int TB, bool UPDATE>
 hipError_t launch_pairs_tb(dca_ctx* ctx, const BmRun* r, const DcaChains& ch, S* x, double* gi, double* gij)
 {
     auto kern = bm_pairs_kernel<S, TB, UPDATE>;
-    const size_t lds = (size_t)TB * TB * r->q * r->q * sizeof(uint32_t);
+    const size_t lds = bm_lds(TB, r->q);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(r->nb, r->nb), dim3(kBmThreads), lds, ctx->stream, ch.dState.get(), ch.nS, ch.n, r->L, r->q, r->nb,

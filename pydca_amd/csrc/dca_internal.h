@@ -51,8 +51,7 @@ void dca_set_error(const char* fmt, ...);
 
 #include "dev_buf.h"
 
-static inline size_t round_up(size_t v, size_t m) { return (v + m - 1) / m * m; }
-static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+#include "potts_plan.h"      // round_up, ceil_div and the launch geometry of the sequence-model kernels
 
 // rows per pass of the set entries (dca_hamming_nearest, dca_three_site_values, dca_pca_project): DCA_NN_PASS, read per call; 32768, at most 2^20
 static inline int dca_nn_pass_size()

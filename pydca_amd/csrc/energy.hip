@@ -11,6 +11,8 @@
 //   finish kernel: per sequence the fields in ascending site order, then the slabs in ascending g.
 // Neither order depends on the number of query sequences or on a sequence's place among them.
 //
+// The tile size and the grouping are energy_geometry's (potts_plan.h).
+//
 // The query codes are kept site-major (code of site s of sequence n at s * NqS + n, NqS a multiple of 128): the lanes of a
 // wave, one sequence each, then read one contiguous 64-byte run per site instead of 64 cache lines.
 #include "dca_internal.h"
@@ -19,10 +21,7 @@ namespace {
 
 constexpr int kEThreads = 512;                     // pair-kernel workgroup: 8 waves
 constexpr int kESeqPerThread = 8;                  // sequences per thread: one tile load serves 4096 sequences
-constexpr int kESeqBlock = kEThreads * kESeqPerThread;
-constexpr size_t kETileBudget = 72 * 1024;         // LDS per tile: two workgroups per CU (160 KiB), one loads while one gathers
-constexpr int kETargetGroups = 128;                // tile groups (slabs) for large L
-constexpr int kEChunk = 16 * kESeqBlock;           // query sequences per pass (bounds the slabs: G x 65536 doubles)
+static_assert(kESeqBlock == kEThreads * kESeqPerThread, "potts_plan.h holds the sequence block of this workgroup");
 
 // grid (G, sequence blocks).  LDS: one tile, TS*TS pairs of q*q values of type S (pair (ii, jj) at (ii*TS + jj) * q*q).
 template <typename S, int TS>
@@ -121,25 +120,10 @@ void mutation_scan_kernel(const PottsView<S> pv, const uint8_t* __restrict__ wt,
     if (a < q) dE[(size_t)i * q + a] = a == wi ? 0.0 : (h - hW) + (s - sumW);
 }
 
-struct EnergyGeom { int TS, nb, ntiles, tpg, G; };
-
-EnergyGeom energy_geometry(int L, int q, size_t elem)
-{
-    static const int kSizes[] = {24, 16, 12, 8, 6, 4, 3};
-    EnergyGeom g{};
-    for (int ts : kSizes)
-        if ((size_t)ts * ts * q * q * elem <= kETileBudget) { g.TS = ts; break; }
-    g.nb = ceil_div(L, g.TS);
-    g.ntiles = g.nb * (g.nb + 1) / 2;
-    g.tpg = ceil_div(g.ntiles, kETargetGroups);
-    g.G = ceil_div(g.ntiles, g.tpg);
-    return g;
-}
-
 template <typename S, int TS>
 hipError_t launch_pairs(dca_ctx* ctx, const EnergyGeom& eg, const PottsView<S>& pv, const uint8_t* QT, int nq, int NqS, double* slabs)
 {
-    const size_t lds = (size_t)TS * TS * pv.q * pv.q * sizeof(S);
+    const size_t lds = energy_lds(TS, pv.q, sizeof(S));
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(energy_pairs_kernel<S, TS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((energy_pairs_kernel<S, TS>), dim3(eg.G, ceil_div(nq, kESeqBlock)), dim3(kEThreads), lds, ctx->stream,

@@ -27,10 +27,7 @@
 
 namespace {
 
-constexpr int kSThreads = 256;                    // 4 waves, 64 chains
-constexpr int kSChains = 64;
-constexpr int kSResidentL = 512;                  // chain codes in LDS up to 32 KiB
-constexpr size_t kSChunkBudget = 40 * 1024;       // LDS per J chunk buffer (two of them)
+// kSThreads, kSChains, kSResidentL, kSChunkBudget and sample_geometry: potts_plan.h
 
 // rows (n x L) <-> site-major state (st[s * nS + c], nS a multiple of 64; chains past n start at code 0)
 __global__ void rows_to_sites_kernel(const uint8_t* __restrict__ rows, size_t ld, int n, int L, int nS, uint8_t* __restrict__ st)
@@ -199,28 +196,13 @@ void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __res
         for (int e = tid; e < L * kSChains; e += kSThreads) state[(size_t)(e >> 6) * nS + c0 + (e & 63)] = stL[e];
 }
 
-struct SampleGeom { int QM, CJ; bool res; size_t lds; };
-
-SampleGeom sample_geometry(int L, int q, size_t elem)
-{
-    SampleGeom g{};
-    g.QM = qm_of(q);
-    const size_t blkBytes = (size_t)q * g.QM * elem;
-    const int R = elem == 4 ? 32 : 16;
-    int cj = std::min((int)(kSThreads * R / (q * q)), (int)(kSChunkBudget / blkBytes));
-    g.CJ = std::max(4, cj / 4 * 4);
-    g.res = L <= kSResidentL;
-    g.lds = round_up(2 * (size_t)g.CJ * blkBytes, 16) + (size_t)g.QM * kSChains * sizeof(double) + (g.res ? (size_t)L * kSChains : 0);
-    return g;
-}
-
 // what one sweep launch takes besides the model
 struct SweepArgs { uint8_t* dState; int nS; uint64_t seed, first_chain, sweep; double beta; const double* h0; double bk; };
 
 template <typename S, int QM, bool RES, bool INTERP>
 hipError_t launch_sweep(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
-    constexpr int R = sizeof(S) == 4 ? 32 : 16;
+    constexpr int R = sample_regs(sizeof(S));
     auto kern = gibbs_sweep_kernel<S, QM, RES, R, INTERP>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds);
     if (e != hipSuccess) return e;

@@ -18,14 +18,7 @@
 #include <functional>
 #include <type_traits>
 
-constexpr int kSiteThreads = 256;                           // 4 waves
-constexpr int kSitePerLane = 2;                             // queries per lane
-constexpr int kSiteSeqBlock = kSiteThreads * kSitePerLane;  // queries per workgroup: one staging of a site's blocks serves 512
-constexpr int kSiteMaxCJ = 16;                              // blocks per chunk at most (bounds the code chunk to 8 KiB)
-constexpr size_t kSiteChunkBudget = 16 * 1024;              // LDS per block chunk buffer (two of them)
-
-// accumulators per query: the state count rounded up to a multiple of the 16-byte LDS reads
-inline int qm_of(int q) { return q <= 8 ? 8 : q <= 24 ? 24 : 32; }
+// kSiteThreads, kSitePerLane, kSiteSeqBlock, kSiteMaxCJ, kSiteChunkBudget, qm_of, chunk_blocks and site_lds: potts_plan.h
 
 // f(std::integral_constant<int, qm_of(q)>): a run-time q to a QM template argument (decltype(qm)::value)
 template <typename F>
@@ -36,18 +29,6 @@ auto with_qm(int q, F&& f)
     case 24: return f(std::integral_constant<int, 24>());
     default: return f(std::integral_constant<int, 32>());
     }
-}
-
-// Blocks per chunk: a chunk buffer holds CJ blocks of up to QM x QM values within kSiteChunkBudget (at most kSiteMaxCJ)
-template <typename S, int QM>
-constexpr int chunk_blocks() { return (int)(kSiteChunkBudget / (QM * QM * sizeof(S))) < kSiteMaxCJ ? (int)(kSiteChunkBudget / (QM * QM * sizeof(S))) : kSiteMaxCJ; }
-
-// dynamic LDS of a site kernel: two chunk buffers (CJ blocks of q x QM values of S each), then two code buffers (CJ x 512 bytes)
-template <typename S, int QM>
-size_t site_lds(int q)
-{
-    constexpr int CJ = chunk_blocks<S, QM>();
-    return round_up(2 * (size_t)CJ * q * QM * sizeof(S), 16) + 2 * (size_t)CJ * kSiteSeqBlock;
 }
 
 // The body of a site kernel (kSiteThreads threads): site i, the queries seq0 .. seq0 + 511 of QT (site-major codes, NqS a
@@ -64,9 +45,9 @@ __device__ __forceinline__ void site_conditional_body(const Policy& P, int i, in
                                                       int nq, int NqS, double* __restrict__ site, double* __restrict__ cond)
 {
     constexpr int CJ = chunk_blocks<S, QM>();
-    constexpr int KPB = (QM * QM + kSiteThreads - 1) / kSiteThreads;        // block elements per thread (q * q <= 256 * KPB)
+    constexpr int KPB = site_kpb<QM>();                                      // block elements per thread (q * q <= 256 * KPB)
     constexpr int codeBytes = CJ * kSiteSeqBlock;
-    constexpr int CPT = (codeBytes / 16 + kSiteThreads - 1) / kSiteThreads;   // 16-byte code pieces per thread
+    constexpr int CPT = site_cpt<S, QM>();                                    // 16-byte code pieces per thread
     static_assert(CPT <= 2, "at most two code pieces per thread");
     extern __shared__ __attribute__((aligned(16))) unsigned char site_smem[];
     const int blk = q * QM;                                   // values of one staged block
