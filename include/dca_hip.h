@@ -353,6 +353,34 @@ int dca_plm_pseudo_likelihood(dca_ctx* ctx, const uint8_t* X, int n, double* pll
  * DCA_ERR_STATE before dca_plm_configure.  Column strips: collective, like dca_plm_energies.  No reference counterpart. */
 int dca_plm_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
                    const uint8_t* initial, uint8_t* out);
+/* Conditional Gibbs sampling: dca_plm_sample with every site outside free_sites clamped.  free_sites:
+ * num_free = F distinct site indices in [0, L), strictly ascending, f_0 < ... < f_{F-1}; chain k keeps initial[k][j] at every
+ * other site j for ever.  initial (n x L codes < q, host) is required: each chain carries its own background.  random_start != 0:
+ * free site i of chain c starts from floor(U * q) with the Philox counter (chain, 0, i, 1), dca_plm_sample's start at that site;
+ * random_start == 0: the free sites start from initial.
+ * The sweep with global number first_sweep + t visits the free sites in ascending order.  At free site i = f_kappa a chain forms,
+ * every term widened to double and no contraction,
+ *   c_i(a) = h_i(a) + sum over the clamped j, ascending, of J_ij(a, s_j)    (once per call; h first, then j ascending, one
+ *                                                                           sequential double sum)
+ *   u_i(a) = (((c_i(a) + S_0(a)) + S_1(a)) + S_2(a)) + S_3(a),  S_w(a) = sum over the free positions k = w (mod 4), k != kappa,
+ *            ascending k, of J(a, s_{f_k})    (the terms of S_0 join c_i(a) one by one, as in dca_plm_sample; S_1 .. S_3 start from 0)
+ * and draws by dca_plm_sample's rule: p_a = exp(beta * (u(a) - max_b u(b))), T the ascending sum, r = U * T, the smallest a whose
+ * cumulative sum exceeds r (the largest a with p_a > 0 if rounding leaves none), U from the Philox counter (chain, sweep, i, 0):
+ * the site word is the site index i, not the position kappa.  So with F = L the entry is bit for bit dca_plm_sample; chain k's
+ * result depends only on the model, seed, first_chain + k, first_sweep, sweeps, its row of initial, the site list, random_start
+ * and beta (the same bits in any batch, split or pass); and a + b sweeps equal a sweeps continued with first_sweep = a and
+ * random_start = 0.  out: n x L codes (host); F == 0 or sweeps == 0 returns the start state.
+ * A sweep reads only the F x F sub-table of the couplings; the field buffer (n x F x q doubles) is bounded at 1 GiB by running
+ * blocks of chains (multiples of 64; DCA_COND_PASS caps the block) one after another.
+ * DCA_ERR_ARG: n < 0, sweeps < 0, beta < 0, NaN or infinite, initial or out NULL with n > 0, num_free outside [0, L], free_sites
+ * NULL with num_free > 0, an index out of range or not strictly ascending, an initial code >= q; n == 0 is DCA_OK.
+ * DCA_ERR_STATE: before dca_plm_configure; under column strips, vector sharding, a reduce / comm hook or a native-comm mode (one
+ * GPU only, like dca_plm_ais).  An L-BFGS or Boltzmann-learning run in progress is allowed; the alignment, the weights, x, g, the
+ * optimiser and the bmDCA chains are not touched.  Profiling tags: "cond_fields" (one pass per block of chains), "sample_cond"
+ * (one launch per sweep and block).  No reference counterpart. */
+int dca_plm_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep,
+                               double beta, const int32_t* free_sites, int num_free, const uint8_t* initial /* n x L, required */,
+                               int random_start, uint8_t* out /* n x L */);
 
 /* ------------------------------------------------------------------ Boltzmann machine learning (bmDCA) of the plm model
  * Refines the context's x (fields h: L*q, then the q x q blocks J_ij, i < j, pair order; storage precision P = the context's
@@ -499,6 +527,12 @@ int dca_mf_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first
 /* dca_plm_ais under the mean-field model (E, h as in dca_mf_energies; base_fields NULL: those fields, 0 on the gap state).  Same
  * rules, RNG layout, determinism and argument checks; DCA_ERR_STATE before dca_mf_couplings. */
 int dca_mf_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out);
+/* dca_plm_sample_conditional under the mean-field model (J, h as in dca_mf_energies; zero on the gap state; DESIGN.md section
+ * 23).  Same rule, RNG layout, determinism and argument checks; with F = L bit for bit dca_mf_sample; DCA_ERR_STATE before
+ * dca_mf_couplings. */
+int dca_mf_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep,
+                              double beta, const int32_t* free_sites, int num_free, const uint8_t* initial /* n x L, required */,
+                              int random_start, uint8_t* out /* n x L */);
 /* The counter-based generator of the samplers, on the host: Philox4x32-10 (Salmon et al., SC 2011; 10 rounds, multipliers
  * 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 / 0xBB67AE85).  Needs no device. */
 int dca_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
@@ -717,7 +751,7 @@ int dca_pca_project(dca_ctx* ctx, const uint8_t* Q, int nq /* Q == NULL: the con
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
- * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "ar_logits", "ar_grad", "ar_sample", "ar_epistasis",
+ * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "cond_fields", "sample_cond", "ar_logits", "ar_grad", "ar_sample", "ar_epistasis",
  * "bm_stats", "ais", "hamming", "set_compare", "three_site_scan", "three_site_values", "pca_project", "pca_back", "pca_small"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it

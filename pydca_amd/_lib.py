@@ -149,6 +149,8 @@ def lib():
         "dca_mf_pseudo_likelihood": (i, [vp, vp, i, vp, vp, vp]),
         "dca_plm_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
         "dca_mf_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
+        "dca_plm_sample_conditional": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, i, vp, i, vp]),
+        "dca_mf_sample_conditional": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, i, vp, i, vp]),
         "dca_philox4x32_10": (i, [vp, vp, vp]),
         "dca_ar_configure": (i, [vp, d, d]),
         "dca_ar_num_params": (sz, [i, i]),
@@ -219,7 +221,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_mf_di_scores", "dca_plm_pair_couplings", "dca_mf_fields", "dca_mf_pair_couplings",
            "dca_encode_sequences", "dca_plm_energies", "dca_plm_mutation_scan", "dca_mf_energies", "dca_mf_mutation_scan",
            "dca_plm_pseudo_likelihood", "dca_mf_pseudo_likelihood",
-           "dca_plm_sample", "dca_mf_sample", "dca_philox4x32_10",
+           "dca_plm_sample", "dca_mf_sample", "dca_plm_sample_conditional", "dca_mf_sample_conditional", "dca_philox4x32_10",
            "dca_ar_configure", "dca_ar_num_params", "dca_ar_init_x", "dca_ar_set_x", "dca_ar_get_x", "dca_ar_gradient", "dca_ar_get_g",
            "dca_ar_fit", "dca_ar_log_probabilities", "dca_ar_sample", "dca_ar_release",
            "dca_ar_epistasis", "dca_ar_epistatic_scores",
@@ -796,6 +798,28 @@ class Context:
 
     def mf_sample(self, n, sweeps, seed=0, beta=1.0, initial=None, first_chain=0, first_sweep=0):
         return self._sample(self._l.dca_mf_sample, n, sweeps, seed, beta, initial, first_chain, first_sweep)
+
+    # ---- conditional Gibbs sampling (sample_conditional.hip): the sites of free_sites (strictly ascending) are resampled, every
+    # other site keeps the chain's own row of `initial` (uint8[n, L], required) -> uint8[n, L] codes
+    def _sample_conditional(self, fn, initial, free_sites, sweeps, seed, beta, random_start, first_chain, first_sweep):
+        init = np.ascontiguousarray(initial, dtype=np.uint8)
+        if init.ndim != 2 or init.shape[1] != self.L:
+            raise ValueError("initial must be uint8[n, %d]" % self.L)
+        sites = np.ascontiguousarray(free_sites, dtype=np.int32).reshape(-1)
+        n = init.shape[0]
+        out = np.zeros((n, self.L), dtype=np.uint8)
+        check(fn(self._h, n, int(sweeps), int(seed), int(first_chain), int(first_sweep), float(beta),
+                 _ptr(sites) if sites.size else None, int(sites.size), _ptr(init) if n else None, int(bool(random_start)),
+                 _ptr(out) if n else None))
+        return out
+
+    def plm_sample_conditional(self, initial, free_sites, sweeps, seed=0, beta=1.0, random_start=True, first_chain=0, first_sweep=0):
+        return self._sample_conditional(self._l.dca_plm_sample_conditional, initial, free_sites, sweeps, seed, beta, random_start,
+                                        first_chain, first_sweep)
+
+    def mf_sample_conditional(self, initial, free_sites, sweeps, seed=0, beta=1.0, random_start=True, first_chain=0, first_sweep=0):
+        return self._sample_conditional(self._l.dca_mf_sample_conditional, initial, free_sites, sweeps, seed, beta, random_start,
+                                        first_chain, first_sweep)
 
     # ---- autoregressive model (ardca.hip): float64 x in the plm layout, sites in the alignment's column order
     def ar_configure(self, lambda_h, lambda_J):

@@ -1,4 +1,5 @@
 """Query sequences of the energy methods of PlmDCA and MeanFieldDCA, encoded for the context (dca_encode_sequences)."""
+import operator
 import os
 
 import numpy as np
@@ -54,6 +55,61 @@ def initial_codes(initial, num_sequences, biomolecule, L, table, exc_type):
                                                                                        num_sequences))
     X = query_codes(seqs, biomolecule, L, table, exc_type)
     return X if X.shape[0] == num_sequences else np.repeat(X, num_sequences, axis=0)
+
+
+def conditional_sites(free_sites, fixed_sites, L, exc_type):
+    """The free sites of sample_sequences_conditional -> int32[F], strictly ascending.  Exactly one of free_sites and fixed_sites
+    (iterables of 0-based ints, in any order) is given; fixed_sites names the complement.  A duplicate, an index outside
+    [0, L) or a value that is not an integer raises exc_type.  Needs no device."""
+    if (free_sites is None) == (fixed_sites is None):
+        raise exc_type('give exactly one of free_sites and fixed_sites')
+    name, given = ('free_sites', free_sites) if fixed_sites is None else ('fixed_sites', fixed_sites)
+    try:
+        idx = sorted(operator.index(v) for v in given)
+    except TypeError:
+        raise exc_type('{} must be an iterable of integers, not {!r}'.format(name, given))
+    for a, b in zip(idx, idx[1:]):
+        if a == b:
+            raise exc_type('{} names site {} twice'.format(name, a))
+    if idx and (idx[0] < 0 or idx[-1] >= L):
+        raise exc_type('{} holds site {}; the 0-based sites are 0 .. {}'.format(name, idx[0] if idx[0] < 0 else idx[-1], L - 1))
+    if fixed_sites is not None:
+        idx = sorted(set(range(L)) - set(idx))
+    return np.asarray(idx, dtype=np.int32)
+
+
+def parse_site_ranges(text, exc_type):
+    """'10-30,45' -> [9, 10, ..., 29, 44]: comma-separated 1-based sites and inclusive ranges, as the written files number the
+    sites -> 0-based ints in the order written (conditional_sites sorts and checks them).  An empty list, a site < 1, a range
+    that runs backwards or anything else raises exc_type."""
+    out = []
+    for part in str(text).split(','):
+        part = part.strip()
+        lo, sep, hi = part.partition('-')
+        try:
+            first = int(lo)
+            last = int(hi) if sep else first
+        except ValueError:
+            raise exc_type('sites are written like 10-30,45 (1-based, inclusive), not {!r}'.format(text))
+        if first < 1 or last < first:
+            raise exc_type('sites are 1-based and ranges ascend: {!r} in {!r}'.format(part, text))
+        out.extend(range(first - 1, last))
+    return out
+
+
+def template_codes(template, num_sequences, biomolecule, L, table, exc_type):
+    """template of sample_sequences_conditional (an aligned string, a list of them or a FASTA file; initial_codes) ->
+    uint8[n, L], n = num_sequences or, when that is None, the number of template records."""
+    if template is None:
+        raise exc_type('sample_sequences_conditional needs a template: an aligned string, a list of them or a FASTA file')
+    if num_sequences is None:
+        one = isinstance(template, str) and not os.path.isfile(template)
+        n = 1 if one else len(_records(template))
+    else:
+        n = operator.index(num_sequences)
+        if n < 0:
+            raise exc_type('num_sequences must be >= 0, not {}'.format(num_sequences))
+    return initial_codes(template, n, biomolecule, L, table, exc_type)
 
 
 def sampling_beta(temperature, exc_type):
@@ -131,7 +187,7 @@ def log_likelihood(energies, weights, meff, log_z):
 
 
 POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences', 'compute_log_likelihood',
-                     'compute_pseudo_log_likelihood', 'compare_sequences', 'compute_pca')
+                     'compute_pseudo_log_likelihood', 'compare_sequences', 'compute_pca', 'sample_conditional')
 
 
 def pll_flag(per_site, exc_type):
@@ -156,7 +212,7 @@ def pseudo_log_likelihood(plls, weights, meff):
 
 class PottsModel:
     """The fitted model of PlmDCA and MeanFieldDCA as a sequence model: energies, single-mutant effects, Gibbs samples, log Z and
-    pseudo-log-likelihoods (DESIGN.md sections 11, 12, 14 and 15; no reference counterpart).  E includes the gap state for PlmDCA
+    pseudo-log-likelihoods (DESIGN.md sections 11, 12, 14, 15 and 23; no reference counterpart).  E includes the gap state for PlmDCA
     (after fit_boltzmann: the refined model); under MeanFieldDCA couplings and fields are zero on the gap state, and the
     couplings of the current pseudocount are computed first if none are there yet.
 
@@ -205,6 +261,28 @@ class PottsModel:
         X0 = initial_codes(initial, n, bio, L, self._potts_table, self._potts_exc)
         self._potts_logger.info('\n\tGibbs sampling of {} sequences, {} sweeps'.format(n, num_sweeps))
         codes = self._potts_call('sample', n, num_sweeps, seed=seed, beta=beta, initial=X0)
+        if return_codes:
+            return codes
+        letters = state_letters(bio)
+        return [''.join(letters[c] for c in row) for row in codes]
+
+    def sample_sequences_conditional(self, template, free_sites=None, fixed_sites=None, num_sequences=None, num_sweeps=1000, seed=0,
+                                     temperature=1.0, randomize=True, return_codes=False):
+        """Draws sequences from P(s_free | s_fixed) ~ exp(E(s) / temperature) by systematic-scan Gibbs sampling over the free
+        sites only: every other site keeps the template's residue.  template: an aligned string, a list
+        of aligned strings or a FASTA file with 1 or num_sequences records (one record is replicated; num_sequences defaults
+        to the number of records), so every chain can carry its own background.  Exactly one of free_sites and fixed_sites
+        (iterables of 0-based site indices, any order) says which sites are redrawn.  randomize: the free sites start from
+        random residues (the plain sampler's start at those sites) instead of the template's.  A sweep reads (F / L)^2 of a
+        full one's couplings for F free sites.  -> aligned strings (gap '-'), or uint8[n, L] codes with return_codes."""
+        beta = sampling_beta(temperature, self._potts_exc)
+        bio, L, _q = self._potts_dims()
+        sites = conditional_sites(free_sites, fixed_sites, L, self._potts_exc)
+        self._one_gpu('sample_sequences_conditional')
+        X0 = template_codes(template, num_sequences, bio, L, self._potts_table, self._potts_exc)
+        self._potts_logger.info('\n\tConditional Gibbs sampling of {} sequences, {} free sites of {}, {} sweeps'.format(
+            X0.shape[0], sites.size, L, num_sweeps))
+        codes = self._potts_call('sample_conditional', X0, sites, num_sweeps, seed=seed, beta=beta, random_start=bool(randomize))
         if return_codes:
             return codes
         letters = state_letters(bio)
@@ -285,6 +363,56 @@ def add_sampling_arguments(p):
     p.add_argument('--initial_file', help='FASTA file with 1 or num_sequences aligned starting sequences (default: random) (addition)')
 
 
+def add_conditional_arguments(p):
+    """The options of the sample_conditional sub-command (plmdca and mfdca command lines)."""
+    p.add_argument('--template_file', required=True, help='FASTA file with 1 or num_sequences aligned template sequences: the '
+                   'sites that are not free keep its residues (addition)')
+    g = p.add_mutually_exclusive_group(required=True)
+    g.add_argument('--free_sites', help='sites to redraw, 1-based inclusive ranges such as 10-30,45 (addition)')
+    g.add_argument('--fixed_sites', help='sites to keep, in the same notation; every other site is redrawn (addition)')
+    p.add_argument('--num_sequences', type=int, help='number of sequences (default: the records of template_file) (addition)')
+    p.add_argument('--num_sweeps', type=int, default=1000, help='Gibbs sweeps over the free sites per chain (addition)')
+    p.add_argument('--seed', type=int, default=0, help='seed of the counter-based generator (addition)')
+    p.add_argument('--temperature', type=float, default=1.0, help='sampling temperature T, P(s) ~ exp(E(s) / T) (addition)')
+    p.add_argument('--keep_template_start', action='store_true', help='start the free sites from the template instead of from '
+                   'random residues (addition)')
+
+
+CONDITIONAL_OPTIONS = ('template_file', 'free_sites', 'fixed_sites', 'num_sequences', 'num_sweeps', 'seed', 'temperature',
+                       'keep_template_start')
+
+
+def run_sample_conditional(instance, prefix, msa_file, output_dir, biomolecule, exc_type, opts):
+    """sample_conditional of the plmdca and mfdca command lines -> the path of <output_dir>/<prefix>_conditional_samples_
+    <alignment base>.fa: '#' lines that name the free sites (1-based), then the records of sample_sequences."""
+    from .dca_utilities import dca_utilities
+    opts = dict(opts or {})
+    if not opts.get('template_file'):
+        raise exc_type('sample_conditional needs --template_file')
+    if (opts.get('free_sites') is None) == (opts.get('fixed_sites') is None):
+        raise exc_type('sample_conditional needs exactly one of --free_sites and --fixed_sites')
+    which = 'free_sites' if opts.get('free_sites') is not None else 'fixed_sites'
+    sites = {which: parse_site_ranges(opts[which], exc_type)}
+
+    def opt(name, default):
+        return default if opts.get(name) is None else opts[name]
+    L = int(instance.sequences_len)
+    free = conditional_sites(sites.get('free_sites'), sites.get('fixed_sites'), L, exc_type)
+    dca_utilities.create_directories(output_dir)
+    codes = instance.sample_sequences_conditional(opts['template_file'], num_sequences=opts.get('num_sequences'),
+                                                  num_sweeps=opt('num_sweeps', 1000), seed=opt('seed', 0),
+                                                  temperature=opt('temperature', 1.0), randomize=not opts.get('keep_template_start'),
+                                                  return_codes=True, **sites)
+    letters = state_letters(biomolecule)
+    seqs = [''.join(letters[c] for c in row) for row in codes]
+    energies = instance.compute_sequence_energies(seqs) if seqs else []
+    path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_conditional_samples_', postfix='.fa')
+    header = ['# Conditional Gibbs samples: template {}, {} free sites of {}'.format(opts['template_file'], free.size, L),
+              '# Free sites (1-based): {}'.format(','.join(str(int(i) + 1) for i in free))]
+    dca_utilities.write_sampled_sequences(path, seqs, energies, header=header)
+    return path
+
+
 def add_ais_arguments(p):
     """The options of the compute_log_likelihood sub-command (plmdca and mfdca command lines)."""
     p.add_argument('--num_chains', type=int, default=1000, help='AIS chains (addition)')
@@ -318,16 +446,19 @@ def run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, opts):
 
 
 def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata, biomolecule, table, exc_type,
-                   query_file=None, wildtype_file=None, sampling=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None):
+                   query_file=None, wildtype_file=None, sampling=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None,
+                   conditional=None):
     """compute_energies / compute_mutation_effects / sample_sequences / compute_pseudo_log_likelihood / compare_sequences of the
     plmdca and mfdca command lines -> the path of the file written: <output_dir>/<prefix>_energies_<alignment base>.txt,
     <prefix>_mutation_effects_<alignment base>.txt, <prefix>_samples_<alignment base>.fa,
     <prefix>_pseudo_log_likelihoods_<alignment base>.txt or <prefix>_sequence_comparison_<alignment base>.txt; compute_pca -> the
     paths of _compare.run_pca (pca: its options num_components and seed, and the K of compare_sequences --pca).  sampling: the sample_sequences options (num_sequences, num_sweeps, seed,
-    temperature, initial_file)."""
+    temperature, initial_file); conditional: the sample_conditional options (CONDITIONAL_OPTIONS; run_sample_conditional)."""
     from .dca_utilities import dca_utilities
     if the_command == 'compute_log_likelihood':
         return run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, ais)
+    if the_command == 'sample_conditional':
+        return run_sample_conditional(instance, prefix, msa_file, output_dir, biomolecule, exc_type, conditional)
     if the_command == 'compare_sequences':
         from . import _compare
         return _compare.run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type, three_site=int(three_site or 0),

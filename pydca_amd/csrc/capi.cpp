@@ -551,6 +551,17 @@ int dca_plm_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t firs
     DCA_TRY(ctx->plm->potts_source(&ps, false));
     return dca_potts_sample(ctx, ps, n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
 }
+// conditional Gibbs sampling (sample_conditional.hip) of the plm engine's x; one GPU only
+int dca_plm_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                               const int32_t* free_sites, int num_free, const uint8_t* initial, int random_start, uint8_t* out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    PottsSource ps;
+    DCA_TRY(ctx->plm->potts_source(&ps, true));
+    return dca_potts_sample_conditional(ctx, ps, n, sweeps, seed, first_chain, first_sweep, beta, free_sites, num_free, initial,
+                                        random_start, out);
+}
 // annealed importance sampling (ais.hip) of the plm engine's x
 int dca_plm_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
 {
@@ -832,6 +843,16 @@ int dca_mf_sample(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first
     MfPotts m;
     DCA_TRY(m.get(ctx));
     return dca_potts_sample(ctx, m.ps, n, sweeps, seed, first_chain, first_sweep, beta, initial, out);
+}
+int dca_mf_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep, double beta,
+                              const int32_t* free_sites, int num_free, const uint8_t* initial, int random_start, uint8_t* out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_mf(ctx));
+    MfPotts m;
+    DCA_TRY(m.get(ctx));
+    return dca_potts_sample_conditional(ctx, m.ps, n, sweeps, seed, first_chain, first_sweep, beta, free_sites, num_free, initial,
+                                        random_start, out);
 }
 int dca_mf_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
 {

@@ -1,6 +1,7 @@
 // Launch geometry of the kernels that read the fitted Potts model as a sequence model: the pair tiles of the energies
 // (energy.hip), the chunking of the site conditionals (site_conditionals.h: pll.hip, ardca.hip), the chunking of the Gibbs sweep
-// (sample.hip, ais.hip) and the pair tiles of the bmDCA statistics (boltzmann.hip), each from (L, q, element size) alone.
+// (sample.hip, ais.hip; sample_conditional.hip at its F free sites) and the pair tiles of the bmDCA statistics (boltzmann.hip),
+// each from (L, q, element size) alone.
 // Host code only, no HIP header: a host compiler builds it, and tests/potts_plan_driver.cpp prints it for
 // tests/test_potts_audit_host.py, which holds the audit's case table to these numbers.  Included from dca_internal.h.
 #pragma once
@@ -105,6 +106,25 @@ inline SampleGeom sample_geometry(int L, int q, size_t elem)
     g.res = L <= kSResidentL;
     g.lds = round_up(2 * (size_t)g.CJ * blkBytes, 16) + (size_t)g.QM * kSChains * sizeof(double) + (g.res ? (size_t)L * kSChains : 0);
     return g;
+}
+
+// ---- sample_conditional.hip: cond_sweep_kernel<S, QM, RES, R> over F free sites and cond_fields_kernel<S, QM, R>
+constexpr int kCFieldChains = 256;                // chains per workgroup of the field pass (lane = chain)
+constexpr size_t kCFieldBudget = (size_t)1 << 30; // the field buffer of one block of chains (F x q doubles per chain)
+
+// chunk elements per thread of the field pass: half the sweep's, every lane holds all QM accumulators there
+constexpr int cond_field_regs(size_t elem) { return sample_regs(elem) / 2; }
+
+// The sweep is the plain sweep's at F sites (the chunks run over the free positions, the free sites' codes sit in LDS up to
+// kSResidentL of them, and then the site list follows them there: F ints); the field pass stages chunks of CJF = CJ / 2 blocks
+// through two buffers and keeps nothing else in LDS.
+struct CondSampleGeom { int QM, CJ, CJF; bool res; size_t lds, ldsFields; };
+
+inline CondSampleGeom cond_sample_geometry(int F, int q, size_t elem)
+{
+    const SampleGeom s = sample_geometry(F, q, elem);
+    const int cjf = s.CJ / 2;
+    return {s.QM, s.CJ, cjf, s.res, s.lds + (s.res ? (size_t)F * sizeof(int) : 0), round_up(2 * (size_t)cjf * q * s.QM * elem, 16)};
 }
 
 // ---- boltzmann.hip: bm_pairs_kernel<S, TB, UPDATE>

@@ -146,11 +146,12 @@ def write_mutation_effects(file_name, dE, wildtype_letters, state_letters, metad
     _stream(file_name, header, rows, 'single-mutant effects')
 
 
-def write_sampled_sequences(file_name, sequences, energies):
+def write_sampled_sequences(file_name, sequences, energies, header=None):
     """FASTA of sampled sequences: one record '>sample_<k> energy=<E>' per sequence (k from 1, E written with %.17g so
-    that it reads back to the same double), the aligned sequence on one line (no reference counterpart)."""
+    that it reads back to the same double), the aligned sequence on one line; header: '#' lines written first
+    (sample_conditional names its free sites there).  No reference counterpart."""
     rows = ('>sample_{} energy={}\n{}'.format(k + 1, '%.17g' % float(e), seq) for k, (seq, e) in enumerate(zip(sequences, energies)))
-    _stream(file_name, [], rows, 'sampled sequences')
+    _stream(file_name, list(header or []), rows, 'sampled sequences')
 
 
 def write_boltzmann_history(file_name, history, metadata=None):
