@@ -382,6 +382,40 @@ int dca_plm_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, u
                                double beta, const int32_t* free_sites, int num_free, const uint8_t* initial /* n x L, required */,
                                int random_start, uint8_t* out /* n x L */);
 
+/* Greedy ascent to a local maximum of E (as dca_plm_energies defines it, gap state included) over a list of free sites, every other
+ * site clamped to the chain's own row of X.  free_sites: as in dca_plm_sample_conditional (num_free = F
+ * strictly ascending indices in [0, L)); NULL with 0 does NOT mean "all sites": pass 0 .. L-1.  Chain k, started at row k of X, does,
+ * every value widened to double and no contraction:
+ *   1. table: for every free site i and state a, U_i(a) = h_i(a) + sum over j != i, ascending j, of J_ij(a, s_j): one sequential
+ *      double sum, h first, then j ascending (the order of dca_plm_pseudo_likelihood's u_i(a)).  Clamped sites contribute here and
+ *      never again.
+ *   2. step t: g(i, a) = U_i(a) - U_i(s_i) for free i and a != s_i; the largest g wins, ties go to the smallest i, then the
+ *      smallest a.  If g > min_gain and t < max_steps the move is applied, otherwise the chain stops.
+ *   3. apply (i*, a*), old = s_i*: s_i* <- a*, and for every free j != i* and every b, U_j(b) <- U_j(b) + (J_{j i*}(b, a*) -
+ *      J_{j i*}(b, old)), the difference formed first, in double.  U_i* is unchanged.
+ * out: the final codes (n x L; clamped columns are those of X).  steps_out: the number of applied steps.  converged_out: 1 if the
+ * chain stopped because no g exceeded min_gain (also when that happens at t == max_steps, and with F == 0), 0 if it stopped at
+ * max_steps with a g > min_gain left.  gain_out (or NULL): the sequential double sum of the applied g.  path_out (or NULL; n x
+ * max_steps x 2: site, new state) and path_gain_out (or NULL; n x max_steps): one record per applied step, -1 / -1 / 0.0 past
+ * steps_out.  With max_steps = 0 or F = 0, out = X.
+ * A chain's result depends only on the model, its row of X, the site list, max_steps and min_gain: the same bits in any batch,
+ * split or pass, and wherever the table is kept.  Continuing an unconverged chain from its output forms the table afresh, so the
+ * continuation equals the uninterrupted run wherever the incrementally updated table has not drifted from a fresh one (it cannot
+ * when every partial sum is exact); nothing more is promised.
+ * The table (F x q doubles per chain) sits in LDS when it and the site list and codes fit (DCA_ASCENT_LDS: the largest table in
+ * bytes that may; 0 keeps it in device memory), and the device scratch is bounded at 1 GiB by running blocks of chains
+ * (DCA_ASCENT_PASS caps the block) one after another.
+ * DCA_ERR_ARG: n < 0, max_steps < 0, min_gain negative, NaN or infinite, X, out, steps_out or converged_out NULL with n > 0,
+ * num_free outside [0, L], free_sites NULL with num_free > 0, an index out of range or not strictly ascending, a code of X >= q;
+ * n == 0 is DCA_OK.  DCA_ERR_STATE: before dca_plm_configure; under column strips, vector sharding, a reduce / comm hook or a
+ * native-comm mode (one GPU only, like dca_plm_sample_conditional).  An L-BFGS or Boltzmann-learning run in progress is allowed; the
+ * alignment, the weights, x, g, the optimiser and the bmDCA chains are not touched.  Profiling tags: "ascent_init" (the table, one
+ * pass per block of chains), "ascent" (one launch per block: all steps of all its chains).  No reference counterpart. */
+int dca_plm_ascend(dca_ctx* ctx, const uint8_t* X /* n x L */, int n, const int32_t* free_sites, int num_free, int max_steps,
+                   double min_gain, uint8_t* out /* n x L */, int32_t* steps_out /* n */, uint8_t* converged_out /* n */,
+                   double* gain_out /* n, or NULL */, int32_t* path_out /* n x max_steps x 2, or NULL */,
+                   double* path_gain_out /* n x max_steps, or NULL */);
+
 /* ------------------------------------------------------------------ Boltzmann machine learning (bmDCA) of the plm model
  * Refines the context's x (fields h: L*q, then the q x q blocks J_ij, i < j, pair order; storage precision P = the context's
  * float32 / float64) by gradient ascent on the L2-regularised log-likelihood per effective sequence, with the model's
@@ -533,6 +567,12 @@ int dca_mf_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, 
 int dca_mf_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, uint64_t first_chain, uint64_t first_sweep,
                               double beta, const int32_t* free_sites, int num_free, const uint8_t* initial /* n x L, required */,
                               int random_start, uint8_t* out /* n x L */);
+/* dca_plm_ascend under the mean-field model (J, h as in dca_mf_energies; zero on the gap state).  Same
+ * rule, determinism and argument checks; DCA_ERR_STATE before dca_mf_couplings. */
+int dca_mf_ascend(dca_ctx* ctx, const uint8_t* X /* n x L */, int n, const int32_t* free_sites, int num_free, int max_steps,
+                  double min_gain, uint8_t* out /* n x L */, int32_t* steps_out /* n */, uint8_t* converged_out /* n */,
+                  double* gain_out /* n, or NULL */, int32_t* path_out /* n x max_steps x 2, or NULL */,
+                  double* path_gain_out /* n x max_steps, or NULL */);
 /* The counter-based generator of the samplers, on the host: Philox4x32-10 (Salmon et al., SC 2011; 10 rounds, multipliers
  * 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 / 0xBB67AE85).  Needs no device. */
 int dca_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

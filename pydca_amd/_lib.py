@@ -151,6 +151,8 @@ def lib():
         "dca_mf_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
         "dca_plm_sample_conditional": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, i, vp, i, vp]),
         "dca_mf_sample_conditional": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, i, vp, i, vp]),
+        "dca_plm_ascend": (i, [vp, vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp]),
+        "dca_mf_ascend": (i, [vp, vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp]),
         "dca_philox4x32_10": (i, [vp, vp, vp]),
         "dca_ar_configure": (i, [vp, d, d]),
         "dca_ar_num_params": (sz, [i, i]),
@@ -221,7 +223,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_mf_di_scores", "dca_plm_pair_couplings", "dca_mf_fields", "dca_mf_pair_couplings",
            "dca_encode_sequences", "dca_plm_energies", "dca_plm_mutation_scan", "dca_mf_energies", "dca_mf_mutation_scan",
            "dca_plm_pseudo_likelihood", "dca_mf_pseudo_likelihood",
-           "dca_plm_sample", "dca_mf_sample", "dca_plm_sample_conditional", "dca_mf_sample_conditional", "dca_philox4x32_10",
+           "dca_plm_sample", "dca_mf_sample", "dca_plm_sample_conditional", "dca_mf_sample_conditional", "dca_plm_ascend", "dca_mf_ascend", "dca_philox4x32_10",
            "dca_ar_configure", "dca_ar_num_params", "dca_ar_init_x", "dca_ar_set_x", "dca_ar_get_x", "dca_ar_gradient", "dca_ar_get_g",
            "dca_ar_fit", "dca_ar_log_probabilities", "dca_ar_sample", "dca_ar_release",
            "dca_ar_epistasis", "dca_ar_epistatic_scores",
@@ -820,6 +822,38 @@ class Context:
     def mf_sample_conditional(self, initial, free_sites, sweeps, seed=0, beta=1.0, random_start=True, first_chain=0, first_sweep=0):
         return self._sample_conditional(self._l.dca_mf_sample_conditional, initial, free_sites, sweeps, seed, beta, random_start,
                                         first_chain, first_sweep)
+
+    # ---- greedy ascent to local maxima (ascent.hip): every row of X (uint8[n, L]) climbs by the best single mutation of a free
+    # site (free_sites strictly ascending, every other site keeps the row's code) until none gains more than min_gain or max_steps
+    # moves are made -> dict: codes uint8[n, L], steps int32[n], converged bool[n], gains float64[n] and, with paths, path
+    # int32[n, max_steps, 2] (site, new state; -1 past steps) and path_gains float64[n, max_steps]
+    def _ascend(self, fn, X, free_sites, max_steps, min_gain, paths):
+        X = np.ascontiguousarray(X, dtype=np.uint8)
+        if X.ndim != 2 or X.shape[1] != self.L:
+            raise ValueError("X must be uint8[n, %d]" % self.L)
+        sites = np.ascontiguousarray(free_sites, dtype=np.int32).reshape(-1)
+        max_steps = 4 * int(sites.size) if max_steps is None else int(max_steps)
+        n = X.shape[0]
+        out = np.zeros((n, self.L), dtype=np.uint8)
+        steps = np.zeros(n, dtype=np.int32)
+        conv = np.zeros(n, dtype=np.uint8)
+        gains = np.zeros(n, dtype=np.float64)
+        path = np.zeros((n, max(max_steps, 0), 2), dtype=np.int32) if paths else None
+        pgain = np.zeros((n, max(max_steps, 0)), dtype=np.float64) if paths else None
+        some = n > 0
+        check(fn(self._h, _ptr(X) if some else None, n, _ptr(sites) if sites.size else None, int(sites.size), max_steps, float(min_gain),
+                 _ptr(out) if some else None, _ptr(steps) if some else None, _ptr(conv) if some else None, _ptr(gains) if some else None,
+                 _ptr(path) if paths and path.size else None, _ptr(pgain) if paths and pgain.size else None))
+        res = {"codes": out, "steps": steps, "converged": conv.astype(bool), "gains": gains}
+        if paths:
+            res["path"], res["path_gains"] = path, pgain
+        return res
+
+    def plm_ascend(self, X, free_sites, max_steps=None, min_gain=0.0, paths=False):
+        return self._ascend(self._l.dca_plm_ascend, X, free_sites, max_steps, min_gain, paths)
+
+    def mf_ascend(self, X, free_sites, max_steps=None, min_gain=0.0, paths=False):
+        return self._ascend(self._l.dca_mf_ascend, X, free_sites, max_steps, min_gain, paths)
 
     # ---- autoregressive model (ardca.hip): float64 x in the plm layout, sites in the alignment's column order
     def ar_configure(self, lambda_h, lambda_J):

@@ -187,7 +187,7 @@ def log_likelihood(energies, weights, meff, log_z):
 
 
 POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences', 'compute_log_likelihood',
-                     'compute_pseudo_log_likelihood', 'compare_sequences', 'compute_pca', 'sample_conditional')
+                     'compute_pseudo_log_likelihood', 'compare_sequences', 'compute_pca', 'sample_conditional', 'find_local_maxima')
 
 
 def pll_flag(per_site, exc_type):
@@ -210,9 +210,49 @@ def pseudo_log_likelihood(plls, weights, meff):
     return float(np.dot(np.asarray(weights, dtype=np.float64), np.asarray(plls, dtype=np.float64))) / float(meff)
 
 
+def ascent_options(free_sites, fixed_sites, max_steps, min_gain, L, exc_type):
+    """Checks the arguments of find_local_maxima (host only) -> (free sites int32[F] ascending, max_steps, min_gain).  With
+    neither site argument every site is free; max_steps None means 4 F."""
+    if free_sites is None and fixed_sites is None:
+        sites = np.arange(L, dtype=np.int32)
+    else:
+        sites = conditional_sites(free_sites, fixed_sites, L, exc_type)
+    if max_steps is None:
+        max_steps = 4 * int(sites.size)
+    elif isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or int(max_steps) < 0:
+        raise exc_type('max_steps must be an integer >= 0 or None, not {!r}'.format(max_steps))
+    try:
+        gain = float(min_gain)
+    except (TypeError, ValueError):
+        raise exc_type('min_gain must be a finite number >= 0, not {!r}'.format(min_gain))
+    if not (0.0 <= gain < float('inf')):
+        raise exc_type('min_gain must be a finite number >= 0, not {!r}'.format(min_gain))
+    return sites, int(max_steps), gain
+
+
+def basins(codes, converged, energies):
+    """The distinct final rows among the converged chains -> (maxima uint8[M, L], basin int64[n]: each chain's index into them or
+    -1 when unconverged, basin_sizes int64[M]).  The distinct rows come from np.unique over rows and
+    are ordered by descending energy, then lexicographic codes."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    converged = np.asarray(converged, dtype=bool)
+    energies = np.asarray(energies, dtype=np.float64)
+    basin = np.full(codes.shape[0], -1, dtype=np.int64)
+    idx = np.flatnonzero(converged)
+    if idx.size == 0:
+        return codes[:0].copy(), basin, np.zeros(0, dtype=np.int64)
+    rows, first, inverse, counts = np.unique(codes[idx], axis=0, return_index=True, return_inverse=True, return_counts=True)
+    e = energies[idx][first]
+    order = np.argsort(-e, kind='stable')                      # np.unique's rows are lexicographic: the stable sort keeps that among ties
+    rank = np.empty(order.size, dtype=np.int64)
+    rank[order] = np.arange(order.size)
+    basin[idx] = rank[np.asarray(inverse).reshape(-1)]
+    return rows[order], basin, counts[order].astype(np.int64)
+
+
 class PottsModel:
     """The fitted model of PlmDCA and MeanFieldDCA as a sequence model: energies, single-mutant effects, Gibbs samples, log Z and
-    pseudo-log-likelihoods (DESIGN.md sections 11, 12, 14, 15 and 23; no reference counterpart).  E includes the gap state for PlmDCA
+    pseudo-log-likelihoods, local maxima (DESIGN.md sections 11, 12, 14, 15, 23 and 24; no reference counterpart).  E includes the gap state for PlmDCA
     (after fit_boltzmann: the refined model); under MeanFieldDCA couplings and fields are zero on the gap state, and the
     couplings of the current pseudocount are computed first if none are there yet.
 
@@ -287,6 +327,39 @@ class PottsModel:
             return codes
         letters = state_letters(bio)
         return [''.join(letters[c] for c in row) for row in codes]
+
+    def find_local_maxima(self, sequences=None, free_sites=None, fixed_sites=None, max_steps=None, min_gain=0.0, return_paths=False):
+        """Greedy ascent of every sequence to a local maximum of E (as in compute_sequence_energies) on the GPU: a chain
+        repeatedly applies the single mutation of a free site with the largest gain in E (ties: the smallest site, then the
+        smallest state) until none gains more than min_gain or max_steps moves are made.  sequences: as
+        in compute_sequence_energies (None: the training alignment's rows).  free_sites / fixed_sites: as in
+        sample_sequences_conditional, at most one of them; with neither, every site is free.  max_steps None: 4 F.
+        -> {'sequences' (aligned strings), 'energies', 'start_energies' (float64[n], of compute_sequence_energies), 'num_steps',
+        'converged', 'gains' (the summed gains of the applied moves), 'maxima' (the distinct final sequences among the converged
+        chains, by descending energy, then codes), 'basin' (each chain's index into maxima, -1 when unconverged),
+        'basin_sizes'} and, with return_paths, 'paths': per chain a list of (site, letter, gain)."""
+        bio, L, _q = self._potts_dims()
+        sites, max_steps, min_gain = ascent_options(free_sites, fixed_sites, max_steps, min_gain, L, self._potts_exc)
+        self._one_gpu('find_local_maxima')
+        X = self._query(sequences)
+        self._potts_logger.info('\n\tGreedy ascent of {} sequences, {} free sites of {}, at most {} steps'.format(
+            X.shape[0], sites.size, L, max_steps))
+        res = self._potts_call('ascend', X, sites, max_steps=max_steps, min_gain=min_gain, paths=bool(return_paths))
+        codes = res['codes']
+        energies = self._potts_call('energies', codes)
+        start = self._potts_call('energies', X)
+        maxima, basin, sizes = basins(codes, res['converged'], energies)
+        letters = state_letters(bio)
+
+        def text(rows):
+            return [''.join(letters[c] for c in row) for row in rows]
+        out = {'sequences': text(codes), 'energies': energies, 'start_energies': start, 'num_steps': res['steps'],
+               'converged': res['converged'], 'gains': res['gains'], 'maxima': text(maxima), 'basin': basin,
+               'basin_sizes': sizes}
+        if return_paths:
+            out['paths'] = [[(int(res['path'][k, t, 0]), letters[res['path'][k, t, 1]], float(res['path_gains'][k, t]))
+                             for t in range(int(res['steps'][k]))] for k in range(codes.shape[0])]
+        return out
 
     def compute_log_partition_function(self, num_chains=1000, num_temperatures=1000, sweeps_per_temperature=1, seed=0, base='profile',
                                        pseudocount=None):
@@ -413,6 +486,38 @@ def run_sample_conditional(instance, prefix, msa_file, output_dir, biomolecule, 
     return path
 
 
+def add_ascent_arguments(p):
+    """The options of the find_local_maxima sub-command (plmdca and mfdca command lines)."""
+    p.add_argument('--query_file', help='FASTA file of aligned starting sequences (default: the records of msa_file) (addition)')
+    g = p.add_mutually_exclusive_group()
+    g.add_argument('--free_sites', help='sites that may mutate, 1-based inclusive ranges such as 10-30,45 (default: all) (addition)')
+    g.add_argument('--fixed_sites', help='sites to keep, in the same notation; every other site may mutate (addition)')
+    p.add_argument('--max_steps', type=int, help='moves per sequence at most (default: 4 x the number of free sites) (addition)')
+    p.add_argument('--min_gain', type=float, default=0.0, help='a move must gain more than this in E (addition)')
+
+
+ASCENT_OPTIONS = ('free_sites', 'fixed_sites', 'max_steps', 'min_gain')
+
+
+def run_find_local_maxima(instance, prefix, msa_file, output_dir, metadata, exc_type, query_file, opts):
+    """find_local_maxima of the plmdca and mfdca command lines -> the paths of <output_dir>/<prefix>_local_maxima_<alignment
+    base>.fa (the final sequences; a record's name carries its start record and its energy) and <prefix>_local_maxima_
+    <alignment base>.txt (one line per input: start energy, final energy, steps, converged, basin)."""
+    from .dca_utilities import dca_utilities
+    opts = dict(opts or {})
+    if opts.get('free_sites') is not None and opts.get('fixed_sites') is not None:
+        raise exc_type('find_local_maxima takes at most one of --free_sites and --fixed_sites')
+    sites = {k: parse_site_ranges(opts[k], exc_type) for k in ('free_sites', 'fixed_sites') if opts.get(k) is not None}
+    dca_utilities.create_directories(output_dir)
+    res = instance.find_local_maxima(query_file, max_steps=opts.get('max_steps'),
+                                     min_gain=0.0 if opts.get('min_gain') is None else opts['min_gain'], **sites)
+    fa = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_local_maxima_', postfix='.fa')
+    txt = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_local_maxima_', postfix='.txt')
+    dca_utilities.write_local_maxima_sequences(fa, res['sequences'], res['energies'])
+    dca_utilities.write_local_maxima(txt, res, metadata=metadata, query_file=query_file or msa_file)
+    return fa, txt
+
+
 def add_ais_arguments(p):
     """The options of the compute_log_likelihood sub-command (plmdca and mfdca command lines)."""
     p.add_argument('--num_chains', type=int, default=1000, help='AIS chains (addition)')
@@ -447,7 +552,7 @@ def run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, opts):
 
 def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata, biomolecule, table, exc_type,
                    query_file=None, wildtype_file=None, sampling=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None,
-                   conditional=None):
+                   conditional=None, ascent=None):
     """compute_energies / compute_mutation_effects / sample_sequences / compute_pseudo_log_likelihood / compare_sequences of the
     plmdca and mfdca command lines -> the path of the file written: <output_dir>/<prefix>_energies_<alignment base>.txt,
     <prefix>_mutation_effects_<alignment base>.txt, <prefix>_samples_<alignment base>.fa,
@@ -459,6 +564,8 @@ def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata
         return run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, ais)
     if the_command == 'sample_conditional':
         return run_sample_conditional(instance, prefix, msa_file, output_dir, biomolecule, exc_type, conditional)
+    if the_command == 'find_local_maxima':      # ascent: its options (ASCENT_OPTIONS; run_find_local_maxima)
+        return run_find_local_maxima(instance, prefix, msa_file, output_dir, metadata, exc_type, query_file, ascent)
     if the_command == 'compare_sequences':
         from . import _compare
         return _compare.run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type, three_site=int(three_site or 0),

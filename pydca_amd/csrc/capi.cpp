@@ -562,6 +562,17 @@ int dca_plm_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, u
     return dca_potts_sample_conditional(ctx, ps, n, sweeps, seed, first_chain, first_sweep, beta, free_sites, num_free, initial,
                                         random_start, out);
 }
+// greedy ascent to local maxima (ascent.hip) under the plm engine's x; one GPU only
+int dca_plm_ascend(dca_ctx* ctx, const uint8_t* X, int n, const int32_t* free_sites, int num_free, int max_steps, double min_gain,
+                   uint8_t* out, int32_t* steps_out, uint8_t* converged_out, double* gain_out, int32_t* path_out, double* path_gain_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    PottsSource ps;
+    DCA_TRY(ctx->plm->potts_source(&ps, true));
+    return dca_potts_ascend(ctx, ps, X, n, free_sites, num_free, max_steps, min_gain, out, steps_out, converged_out, gain_out, path_out,
+                            path_gain_out);
+}
 // annealed importance sampling (ais.hip) of the plm engine's x
 int dca_plm_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
 {
@@ -853,6 +864,16 @@ int dca_mf_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, ui
     DCA_TRY(m.get(ctx));
     return dca_potts_sample_conditional(ctx, m.ps, n, sweeps, seed, first_chain, first_sweep, beta, free_sites, num_free, initial,
                                         random_start, out);
+}
+int dca_mf_ascend(dca_ctx* ctx, const uint8_t* X, int n, const int32_t* free_sites, int num_free, int max_steps, double min_gain,
+                  uint8_t* out, int32_t* steps_out, uint8_t* converged_out, double* gain_out, int32_t* path_out, double* path_gain_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_mf(ctx));
+    MfPotts m;
+    DCA_TRY(m.get(ctx));
+    return dca_potts_ascend(ctx, m.ps, X, n, free_sites, num_free, max_steps, min_gain, out, steps_out, converged_out, gain_out, path_out,
+                            path_gain_out);
 }
 int dca_mf_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
 {

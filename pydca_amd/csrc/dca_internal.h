@@ -205,8 +205,8 @@ struct PlmEngineBase {
     virtual int scores(int apc, double* out) = 0;
     virtual int di_scores(const double* reg_fi, int apc, double* out) = 0;
     virtual int pair_couplings(const int* pairs, int npairs, int shift, double* out) = 0;
-    // the current x as a Potts source (energy.hip, pll.hip, sample.hip, sample_conditional.hip, ais.hip); column strips gather x first, as scores() does.
-    // one_gpu_only (AIS, conditional sampling): DCA_ERR_STATE under column strips, vector sharding, a reduce / comm hook or a native-comm mode instead
+    // the current x as a Potts source (energy.hip, pll.hip, sample.hip, sample_conditional.hip, ascent.hip, ais.hip); column strips gather x first, as scores() does.
+    // one_gpu_only (AIS, conditional sampling, ascent): DCA_ERR_STATE under column strips, vector sharding, a reduce / comm hook or a native-comm mode instead
     virtual int potts_source(PottsSource* out, bool one_gpu_only) = 0;
     // the device x a Boltzmann-learning run updates in place; DCA_ERR_STATE (with the reason) unconfigured, during an L-BFGS
     // run, under column strips, vector sharding, a reduce / comm hook or a native-comm mode
@@ -258,6 +258,12 @@ int dca_potts_sample(dca_ctx* ctx, const PottsSource& ps, int n, int sweeps, uin
 int dca_potts_sample_conditional(dca_ctx* ctx, const PottsSource& ps, int n, int sweeps, uint64_t seed, uint64_t first_chain,
                                  uint64_t first_sweep, double beta, const int32_t* free_sites, int num_free,
                                  const uint8_t* initial /* host n*L */, int random_start, uint8_t* out /* host n*L */);
+
+// ---- ascent.hip : greedy ascent of host rows X (n x L codes < q) to local maxima of E over the free sites (dca_plm_ascend
+// semantics; all arguments checked here).  All outputs on the host; gain_out, path_out and path_gain_out may be NULL.
+int dca_potts_ascend(dca_ctx* ctx, const PottsSource& ps, const uint8_t* X, int n, const int32_t* free_sites, int num_free, int max_steps,
+                     double min_gain, uint8_t* out, int32_t* steps_out, uint8_t* converged_out, double* gain_out, int32_t* path_out,
+                     double* path_gain_out);
 
 // Philox4x32-10 of the samplers (sample.hip, ais.hip): key = (seed lo, seed hi), counter = (chain, sweep, site, tag), each
 // word the value mod 2^32; U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  Tags: 0 Gibbs draw, 1 random start, 2 AIS start,

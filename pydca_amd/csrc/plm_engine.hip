@@ -588,15 +588,15 @@ struct PlmEngine : PlmEngineBase {
         *x = dx;
         return DCA_OK;
     }
-    // the current x for energy.hip, pll.hip, sample.hip, sample_conditional.hip and ais.hip; an L-BFGS run in progress is
-    // allowed.  Column strips gather x first, as scores() does; one_gpu_only (AIS, conditional sampling) refuses them instead
+    // the current x for energy.hip, pll.hip, sample.hip, sample_conditional.hip, ascent.hip and ais.hip; an L-BFGS run in progress is
+    // allowed.  Column strips gather x first, as scores() does; one_gpu_only (AIS, conditional sampling, ascent) refuses them instead
     int potts_source(PottsSource* out, bool one_gpu_only) override
     {
         if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
         if (one_gpu_only) {
-            if (strips || native_mode == 4) { dca_set_error("AIS and conditional sampling run on one GPU: configured for column strips"); return DCA_ERR_STATE; }
+            if (strips || native_mode == 4) { dca_set_error("AIS, conditional sampling and the ascent run on one GPU: configured for column strips"); return DCA_ERR_STATE; }
             if (comm || hook || native_mode != 0) {
-                dca_set_error("AIS and conditional sampling run on one GPU: vector sharding, a reduce / comm hook or a native-comm mode is set");
+                dca_set_error("AIS, conditional sampling and the ascent run on one GPU: vector sharding, a reduce / comm hook or a native-comm mode is set");
                 return DCA_ERR_STATE;
             }
         } else if (native_mode == 4 && !stripEmulate) {

@@ -1,5 +1,5 @@
-// The fitted Potts model as its consumers see it (energy.hip, pll.hip, sample.hip, sample_conditional.hip, ais.hip,
-// boltzmann.hip): one host-side description, PottsSource, and one typed device view, PottsView<S>, which alone knows the two
+// The fitted Potts model as its consumers see it (energy.hip, pll.hip, sample.hip, sample_conditional.hip, ascent.hip,
+// ais.hip, boltzmann.hip): one host-side description, PottsSource, and one typed device view, PottsView<S>, which alone knows the two
 // parameter layouts.
 //   kind 0: the packed plm vector x of element type `dtype` (DCA_F32 / DCA_F64): fields L*q first, then the upper-triangle
 //           q x q blocks in pair order (pair_index); mfh and ld unused;

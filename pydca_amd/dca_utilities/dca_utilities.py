@@ -154,6 +154,29 @@ def write_sampled_sequences(file_name, sequences, energies, header=None):
     _stream(file_name, list(header or []), rows, 'sampled sequences')
 
 
+def write_local_maxima_sequences(file_name, sequences, energies):
+    """FASTA of the final sequences of find_local_maxima: one record '>maximum_of_<k> energy=<E>' per input record k (from 1,
+    input order; E written with %.17g), the aligned sequence on one line.  No reference counterpart."""
+    rows = ('>maximum_of_{} energy={}\n{}'.format(k + 1, '%.17g' % float(e), seq) for k, (seq, e) in enumerate(zip(sequences, energies)))
+    _stream(file_name, [], rows, 'local maxima')
+
+
+def write_local_maxima(file_name, result, metadata=None, query_file=None):
+    """One row per input record of find_local_maxima: its number (1-based, input order), start energy, final energy, steps,
+    converged (1 / 0) and basin (1-based index of its maximum by descending energy, 0 when unconverged); energies written with
+    %.17g.  The header counts the distinct maxima (no reference counterpart)."""
+    header = [_RULE] + list(metadata or [])
+    if query_file:
+        header.append('#\tStarting sequences: {}'.format(query_file))
+    header += ['#\tDistinct local maxima among the converged sequences: {}'.format(len(result['basin_sizes'])),
+               '# Columns: record number (1-based), start energy, final energy, steps, converged (1 / 0) and basin: the 1-based',
+               '# rank of its local maximum by descending energy (0: not converged within max_steps)', _RULE]
+    rows = ('{0:<7} {1} {2} {3} {4} {5}'.format(k + 1, '%.17g' % float(result['start_energies'][k]), '%.17g' % float(result['energies'][k]),
+                                                int(result['num_steps'][k]), int(bool(result['converged'][k])), int(result['basin'][k]) + 1)
+            for k in range(len(result['energies'])))
+    _stream(file_name, header, rows, 'local maxima')
+
+
 def write_boltzmann_history(file_name, history, metadata=None):
     """Learning curve of PlmDCA.fit_boltzmann: one row per iteration t (0-based) with eps_h, eps_J and pearson, each
     written with %.17g (no reference counterpart)."""
