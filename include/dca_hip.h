@@ -416,6 +416,56 @@ int dca_plm_ascend(dca_ctx* ctx, const uint8_t* X /* n x L */, int n, const int3
                    double* gain_out /* n, or NULL */, int32_t* path_out /* n x max_steps x 2, or NULL */,
                    double* path_gain_out /* n x max_steps, or NULL */);
 
+/* Replica-exchange (parallel-tempering) Gibbs sampling on a temperature ladder: M ladders of R walkers,
+ * n = M R walkers in all, betas[0] < ... < betas[R-1].  Walker r of ladder m is row m R + r of every per-walker array; its Philox
+ * chain word is (first_ladder + m) R + r.  It starts at level r, or at initial_levels[m R + r] (within each ladder a permutation
+ * of 0 .. R-1), from the tag-1 random state of its chain word (dca_plm_sample's start), or from row m R + r of initial.  A walker
+ * keeps its codes for ever; what the exchanges move is its level.
+ * The sweep with global number g = first_sweep + t is dca_plm_sample's sweep (same summation order, draw rule and Philox counter
+ * (chain, g, site, 0)) with every walker under betas[level(walker)]: p_a = exp(beta_c * (u(a) - max_b u(b))).
+ * Exchange rounds: after global sweep g, if swap_interval = I > 0 and (g + 1) mod I == 0, round rho = (g + 1) / I - 1 runs.  E of
+ * every walker is formed bit for bit as dca_plm_energies forms it for the walker's codes.  For each ladder and each k with
+ * k = rho (mod 2) and k + 1 < R, with a the walker at level k and b the walker at level k + 1:
+ *   d = (betas[k+1] - betas[k]) * (E_a - E_b)    (both differences first, then one multiply, in double, no contraction)
+ *   U = the Philox uniform of key (seed) and counter (first_ladder + m, rho, k, 5)    (tag 5; U as in dca_plm_sample)
+ *   accept iff d >= 0 || U < exp(d);  accepting exchanges the levels of a and b (and so their beta); codes never move.
+ * The pairs of a round are disjoint.  rounds = floor((first_sweep + sweeps) / I) - floor(first_sweep / I) (0 when I == 0).
+ * Outputs (host): out, the codes after `sweeps` sweeps; levels_out, each walker's level then; energies_out (or NULL), E of the
+ * final codes (bit for bit dca_plm_energies of out); attempts_out / accepts_out (or NULL; R-1 each), the exchanges attempted and
+ * accepted between levels k and k + 1, summed over ladders and rounds; energy_trace_out (or NULL; rounds x M x R),
+ * trace[round][m][k] = E of the walker at level k before that round's exchange, rounds counted from the call's first;
+ * rounds_out (or NULL).
+ * Guarantees:
+ *   (a) with swap_interval == 0, row m R + r is bit for bit dca_plm_sample(1, sweeps, seed, (first_ladder + m) R + r, first_sweep,
+ *       betas[r], its start);
+ *   (b) a ladder's outputs depend only on the model, seed, first_ladder + m, betas, first_sweep, sweeps, I and its starts: the
+ *       same bits in any batch or split by ladders (the counters are sums over the ladders);
+ *   (c) a + b sweeps equal a sweeps continued from out / levels_out with first_sweep = a, for any a: rounds are numbered
+ *       globally (the counters and trace rows of the two parts add up to the whole run's).
+ * One launch per sweep for all walkers; nothing goes to the host between rounds except the trace.  The device scratch (state,
+ * energies' slabs, trace buffer) stays within 1 GiB: blocks of ladders run one after another (DCA_PT_PASS caps the ladders of a
+ * block) and the trace buffer (at most 256 MiB) is flushed in blocks of rounds (DCA_PT_TRACE_ROUNDS caps them); neither shows
+ * in the results.
+ * DCA_ERR_ARG: args NULL, ladders < 0, levels < 1, sweeps < 0, swap_interval < 0, more than 2^24 walkers, first_sweep + sweeps
+ * past 2^64 - 1, betas NULL, a beta that is negative, NaN, infinite or not above its predecessor, out or levels_out NULL with
+ * M > 0, initial_levels that are not a permutation within a ladder, an initial code >= q; M == 0 is DCA_OK.
+ * DCA_ERR_STATE: before dca_plm_configure; under column strips, vector sharding, a reduce / comm hook or a native-comm mode (one
+ * GPU only, like dca_plm_sample_conditional).  An L-BFGS or Boltzmann-learning run in progress is allowed; the alignment, the
+ * weights, x, g, the optimiser and the bmDCA chains are not touched.  Profiling tags: "sample" (the sweeps), "pt_energy" (the
+ * energy pass of a round), "pt_swap" (the exchange kernel).  No reference counterpart. */
+typedef struct dca_pt_args {
+    int ladders, levels;             /* M >= 0, R >= 1 */
+    const double* betas;             /* R values: finite, >= 0, strictly increasing */
+    int sweeps, swap_interval;       /* >= 0; swap_interval 0: no exchange */
+    uint64_t seed, first_ladder, first_sweep;
+    const uint8_t* initial;          /* M*R x L codes < q, or NULL */
+    const int32_t* initial_levels;   /* M*R, or NULL: walker r at level r */
+} dca_pt_args;
+int dca_plm_sample_tempered(dca_ctx* ctx, const dca_pt_args* args, uint8_t* out /* M*R x L */, int32_t* levels_out /* M*R */,
+                            double* energies_out /* M*R or NULL: E of the final codes */, uint64_t* attempts_out,
+                            uint64_t* accepts_out /* R-1 each, or NULL */, double* energy_trace_out /* rounds x M x R, or NULL */,
+                            int* rounds_out /* or NULL */);
+
 /* ------------------------------------------------------------------ Boltzmann machine learning (bmDCA) of the plm model
  * Refines the context's x (fields h: L*q, then the q x q blocks J_ij, i < j, pair order; storage precision P = the context's
  * float32 / float64) by gradient ascent on the L2-regularised log-likelihood per effective sequence, with the model's
@@ -573,6 +623,13 @@ int dca_mf_ascend(dca_ctx* ctx, const uint8_t* X /* n x L */, int n, const int32
                   double min_gain, uint8_t* out /* n x L */, int32_t* steps_out /* n */, uint8_t* converged_out /* n */,
                   double* gain_out /* n, or NULL */, int32_t* path_out /* n x max_steps x 2, or NULL */,
                   double* path_gain_out /* n x max_steps, or NULL */);
+/* dca_plm_sample_tempered under the mean-field model (J, h as in dca_mf_energies; zero on the gap state).
+ * Same rule, RNG layout, guarantees (with dca_mf_sample and dca_mf_energies in the place of the plm entries) and argument
+ * checks; DCA_ERR_STATE before dca_mf_couplings. */
+int dca_mf_sample_tempered(dca_ctx* ctx, const dca_pt_args* args, uint8_t* out /* M*R x L */, int32_t* levels_out /* M*R */,
+                           double* energies_out /* M*R or NULL: E of the final codes */, uint64_t* attempts_out,
+                           uint64_t* accepts_out /* R-1 each, or NULL */, double* energy_trace_out /* rounds x M x R, or NULL */,
+                           int* rounds_out /* or NULL */);
 /* The counter-based generator of the samplers, on the host: Philox4x32-10 (Salmon et al., SC 2011; 10 rounds, multipliers
  * 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 / 0xBB67AE85).  Needs no device. */
 int dca_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

@@ -48,6 +48,13 @@ class AisArgs(C.Structure):
                 ("seed", C.c_uint64), ("first_chain", C.c_uint64), ("base_fields", C.c_void_p)]
 
 
+class PtArgs(C.Structure):
+    """dca_pt_args (include/dca_hip.h)"""
+    _fields_ = [("ladders", C.c_int), ("levels", C.c_int), ("betas", C.c_void_p), ("sweeps", C.c_int), ("swap_interval", C.c_int),
+                ("seed", C.c_uint64), ("first_ladder", C.c_uint64), ("first_sweep", C.c_uint64), ("initial", C.c_void_p),
+                ("initial_levels", C.c_void_p)]
+
+
 class ArStats(C.Structure):
     """dca_ar_stats (include/dca_hip.h)"""
     _fields_ = [("status", C.c_int), ("iterations", C.c_int), ("evaluations", C.c_int), ("fx", C.c_double), ("gnorm", C.c_double),
@@ -151,6 +158,8 @@ def lib():
         "dca_mf_sample": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, vp]),
         "dca_plm_sample_conditional": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, i, vp, i, vp]),
         "dca_mf_sample_conditional": (i, [vp, i, i, C.c_uint64, C.c_uint64, C.c_uint64, d, vp, i, vp, i, vp]),
+        "dca_plm_sample_tempered": (i, [vp, C.POINTER(PtArgs), vp, vp, vp, vp, vp, vp, C.POINTER(i)]),
+        "dca_mf_sample_tempered": (i, [vp, C.POINTER(PtArgs), vp, vp, vp, vp, vp, vp, C.POINTER(i)]),
         "dca_plm_ascend": (i, [vp, vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp]),
         "dca_mf_ascend": (i, [vp, vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp]),
         "dca_philox4x32_10": (i, [vp, vp, vp]),
@@ -223,7 +232,8 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_mf_di_scores", "dca_plm_pair_couplings", "dca_mf_fields", "dca_mf_pair_couplings",
            "dca_encode_sequences", "dca_plm_energies", "dca_plm_mutation_scan", "dca_mf_energies", "dca_mf_mutation_scan",
            "dca_plm_pseudo_likelihood", "dca_mf_pseudo_likelihood",
-           "dca_plm_sample", "dca_mf_sample", "dca_plm_sample_conditional", "dca_mf_sample_conditional", "dca_plm_ascend", "dca_mf_ascend", "dca_philox4x32_10",
+           "dca_plm_sample", "dca_mf_sample", "dca_plm_sample_conditional", "dca_mf_sample_conditional",
+           "dca_plm_sample_tempered", "dca_mf_sample_tempered", "dca_plm_ascend", "dca_mf_ascend", "dca_philox4x32_10",
            "dca_ar_configure", "dca_ar_num_params", "dca_ar_init_x", "dca_ar_set_x", "dca_ar_get_x", "dca_ar_gradient", "dca_ar_get_g",
            "dca_ar_fit", "dca_ar_log_probabilities", "dca_ar_sample", "dca_ar_release",
            "dca_ar_epistasis", "dca_ar_epistatic_scores",
@@ -822,6 +832,53 @@ class Context:
     def mf_sample_conditional(self, initial, free_sites, sweeps, seed=0, beta=1.0, random_start=True, first_chain=0, first_sweep=0):
         return self._sample_conditional(self._l.dca_mf_sample_conditional, initial, free_sites, sweeps, seed, beta, random_start,
                                         first_chain, first_sweep)
+
+    # ---- replica-exchange Gibbs sampling (tempered.hip): `ladders` ladders of len(betas) walkers, walker r of ladder m at row
+    # m R + r; betas strictly increasing -> dict: codes uint8[n, L], levels int32[n], energies float64[n] (E of the final codes),
+    # attempts / accepts uint64[R - 1], rounds and, with trace, trace float64[rounds, ladders, R] (E of the walker at each level
+    # before every exchange round)
+    def _sample_tempered(self, fn, ladders, betas, sweeps, swap_interval, seed, first_ladder, first_sweep, initial, initial_levels, trace):
+        M = int(ladders)
+        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        R = int(b.size)
+        n = max(M, 0) * R
+        init = lev = None
+        if initial is not None:
+            init = np.ascontiguousarray(initial, dtype=np.uint8)
+            if init.shape != (n, self.L):
+                raise ValueError("initial must be uint8[%d, %d]" % (n, self.L))
+        if initial_levels is not None:
+            lev = np.ascontiguousarray(initial_levels, dtype=np.int32).reshape(-1)
+            if lev.size != n:
+                raise ValueError("initial_levels must hold ladders x levels = %d values, not %d" % (n, lev.size))
+        sweeps, swap_interval, first_sweep = int(sweeps), int(swap_interval), int(first_sweep)
+        rounds = (first_sweep + sweeps) // swap_interval - first_sweep // swap_interval if swap_interval > 0 and sweeps >= 0 else 0
+        args = PtArgs(M, R, b.ctypes.data if R else None, sweeps, swap_interval, int(seed), int(first_ladder), first_sweep,
+                      init.ctypes.data if init is not None and n else None, lev.ctypes.data if lev is not None and n else None)
+        out = np.zeros((n, self.L), dtype=np.uint8)
+        levels = np.zeros(n, dtype=np.int32)
+        energies = np.zeros(n, dtype=np.float64)
+        attempts = np.zeros(max(R - 1, 0), dtype=np.uint64)
+        accepts = np.zeros(max(R - 1, 0), dtype=np.uint64)
+        tr = np.zeros((max(rounds, 0), max(M, 0), R), dtype=np.float64) if trace else None
+        done = C.c_int(0)
+        check(fn(self._h, C.byref(args), _ptr(out) if n else None, _ptr(levels) if n else None, _ptr(energies) if n else None,
+                 _ptr(attempts) if attempts.size else None, _ptr(accepts) if accepts.size else None,
+                 _ptr(tr) if tr is not None and tr.size else None, C.byref(done)))
+        res = {"codes": out, "levels": levels, "energies": energies, "attempts": attempts, "accepts": accepts, "rounds": int(done.value)}
+        if trace:
+            res["trace"] = tr
+        return res
+
+    def plm_sample_tempered(self, ladders, betas, sweeps, swap_interval=1, seed=0, first_ladder=0, first_sweep=0, initial=None,
+                            initial_levels=None, trace=False):
+        return self._sample_tempered(self._l.dca_plm_sample_tempered, ladders, betas, sweeps, swap_interval, seed, first_ladder,
+                                     first_sweep, initial, initial_levels, trace)
+
+    def mf_sample_tempered(self, ladders, betas, sweeps, swap_interval=1, seed=0, first_ladder=0, first_sweep=0, initial=None,
+                           initial_levels=None, trace=False):
+        return self._sample_tempered(self._l.dca_mf_sample_tempered, ladders, betas, sweeps, swap_interval, seed, first_ladder,
+                                     first_sweep, initial, initial_levels, trace)
 
     # ---- greedy ascent to local maxima (ascent.hip): every row of X (uint8[n, L]) climbs by the best single mutation of a free
     # site (free_sites strictly ascending, every other site keeps the row's code) until none gains more than min_gain or max_steps

@@ -120,6 +120,76 @@ def sampling_beta(temperature, exc_type):
     return 1.0 / t
 
 
+def temperature_ladder(t_min, t_max, num):
+    """A geometric ladder of `num` temperatures from t_min to t_max (both included; finite, 0 < t_min <= t_max): neighbours keep
+    the ratio (t_max / t_min)^(1 / (num - 1)), the usual first choice for replica exchange -> float64[num], ascending.  num = 1
+    gives [t_min].  ValueError otherwise.  Needs no device."""
+    if isinstance(num, (bool, np.bool_)) or not isinstance(num, (int, np.integer)) or int(num) < 1:
+        raise ValueError('num must be an integer >= 1, not {!r}'.format(num))
+    lo, hi = float(t_min), float(t_max)
+    if not (0.0 < lo <= hi < float('inf')):
+        raise ValueError('the ladder needs finite temperatures with 0 < t_min <= t_max, not {!r} and {!r}'.format(t_min, t_max))
+    num = int(num)
+    if num == 1:
+        return np.array([lo])
+    if lo == hi:
+        raise ValueError('{} distinct temperatures need t_min < t_max'.format(num))
+    t = lo * (hi / lo) ** (np.arange(num, dtype=np.float64) / (num - 1))
+    t[0], t[-1] = lo, hi
+    return t
+
+
+def tempered_options(num_sequences, temperatures, num_sweeps, swap_interval, seed, burn_in_sweeps, exc_type):
+    """Checks the arguments of sample_sequences_tempered (host only) -> dict: n, temperatures float64[T] (the caller's order),
+    betas float64[R] (the distinct 1 / T, ascending; 0 for T = inf), level int64[T] (each temperature's index into betas),
+    num_sweeps, swap_interval, seed, burn_in (None: num_sweeps // 2)."""
+    def count(name, v, low):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or int(v) < low:
+            raise exc_type('{} must be an integer >= {}, not {!r}'.format(name, low, v))
+        return int(v)
+    opts = dict(n=count('num_sequences', num_sequences, 0), num_sweeps=count('num_sweeps', num_sweeps, 0),
+                swap_interval=count('swap_interval', swap_interval, 0), seed=count('seed', seed, 0))
+    opts['burn_in'] = opts['num_sweeps'] // 2 if burn_in_sweeps is None else count('burn_in_sweeps', burn_in_sweeps, 0)
+    try:
+        t = np.array([float(v) for v in temperatures], dtype=np.float64)
+    except (TypeError, ValueError):
+        raise exc_type('temperatures must be a sequence of numbers, not {!r}'.format(temperatures))
+    if t.size < 1:
+        raise exc_type('temperatures must hold at least one value')
+    if np.isnan(t).any() or not (t > 0.0).all():
+        raise exc_type('every temperature must be finite and > 0, or inf (beta = 0), not {}'.format(t.tolist()))
+    betas, level = np.unique(np.where(np.isinf(t), 0.0, 1.0 / np.where(np.isinf(t), 1.0, t)), return_inverse=True)
+    if opts['n'] * betas.size > 1 << 24:
+        raise exc_type('num_sequences x distinct temperatures must be <= 2^24 walkers, not {} x {}'.format(opts['n'], betas.size))
+    opts.update(temperatures=t, betas=betas, level=np.asarray(level, dtype=np.int64).reshape(-1))
+    return opts
+
+
+def tempered_result(opts, res, text):
+    """The dict of sample_sequences_tempered from the checked options, the dict of Context.{plm,mf}_sample_tempered (with its
+    trace) and text(codes) -> sequences.  Level k's sample of ladder m is the walker sitting at level k at the end."""
+    n, betas, level = opts['n'], opts['betas'], opts['level']
+    R = betas.size
+    at = np.argsort(np.asarray(res['levels']).reshape(n, R), axis=1)               # at[m, k]: the walker of ladder m at level k
+    rows = np.arange(n)[:, None] * R + at                                           # ... its row
+    codes = np.asarray(res['codes'])[rows]                                          # [m, k, L]
+    energies = np.asarray(res['energies'])[rows]                                    # [m, k]
+    attempts = np.asarray(res['attempts'], dtype=np.uint64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        acceptance = np.where(attempts > 0, np.asarray(res['accepts'], dtype=np.float64) / attempts.astype(np.float64), np.nan)
+    trace = np.asarray(res['trace'])                                                # [round, m, k]; round j ends sweep (j + 1) I - 1
+    keep = (np.arange(trace.shape[0]) + 1) * opts['swap_interval'] > opts['burn_in']
+    mean = np.full(R, np.nan)
+    cap = np.full(R, np.nan)
+    if n and keep.any():
+        e = trace[keep].reshape(-1, R)
+        mean = e.mean(axis=0)
+        cap = betas * betas * e.var(axis=0)
+    return {'temperatures': opts['temperatures'], 'sequences': [text(codes[:, k]) for k in level],
+            'energies': np.ascontiguousarray(energies.T[level]), 'swap_acceptance': acceptance, 'swap_attempts': attempts,
+            'mean_energy': mean[level], 'heat_capacity': cap[level], 'num_rounds': int(res['rounds'])}
+
+
 def state_letters(biomolecule):
     """Letter of every 0-based state (gap last), for the CLI's mutation-effect rows and sampled sequences."""
     return list('ACDEFGHIKLMNPQRSTVWY-') if biomolecule == _lib.DCA_BIOMOLECULE_PROTEIN else list('ACGU-')
@@ -187,7 +257,8 @@ def log_likelihood(energies, weights, meff, log_z):
 
 
 POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences', 'compute_log_likelihood',
-                     'compute_pseudo_log_likelihood', 'compare_sequences', 'compute_pca', 'sample_conditional', 'find_local_maxima')
+                     'compute_pseudo_log_likelihood', 'compare_sequences', 'compute_pca', 'sample_conditional', 'find_local_maxima',
+                     'sample_tempered')
 
 
 def pll_flag(per_site, exc_type):
@@ -252,7 +323,7 @@ def basins(codes, converged, energies):
 
 class PottsModel:
     """The fitted model of PlmDCA and MeanFieldDCA as a sequence model: energies, single-mutant effects, Gibbs samples, log Z and
-    pseudo-log-likelihoods, local maxima (DESIGN.md sections 11, 12, 14, 15, 23 and 24; no reference counterpart).  E includes the gap state for PlmDCA
+    pseudo-log-likelihoods, local maxima, replica exchange (DESIGN.md sections 11, 12, 14, 15, 23, 24 and 25; no reference counterpart).  E includes the gap state for PlmDCA
     (after fit_boltzmann: the refined model); under MeanFieldDCA couplings and fields are zero on the gap state, and the
     couplings of the current pseudocount are computed first if none are there yet.
 
@@ -327,6 +398,35 @@ class PottsModel:
             return codes
         letters = state_letters(bio)
         return [''.join(letters[c] for c in row) for row in codes]
+
+    def sample_sequences_tempered(self, num_sequences, temperatures, num_sweeps=1000, swap_interval=1, seed=0, initial=None,
+                                  burn_in_sweeps=None, return_codes=False):
+        """Draws num_sequences sequences at every temperature of a ladder by replica-exchange (parallel-tempering) Gibbs sampling
+        on the GPU (DESIGN.md section 25): num_sequences independent ladders, each with one walker per distinct temperature;
+        every walker does the sweep of sample_sequences under its current temperature, and after every swap_interval sweeps
+        walkers at neighbouring temperatures exchange temperatures by the Metropolis rule, so that the cold samples inherit the
+        mixing of the hot ones (swap_interval 0: no exchange, independent chains).  temperatures: finite values > 0, or inf
+        (beta = 0), in any order; the result follows that order.  initial: as in sample_sequences; record m starts every walker
+        of ladder m.  burn_in_sweeps (None: num_sweeps // 2): the exchange rounds up to that sweep are left out of the averages.
+        -> {'temperatures', 'sequences' (per temperature num_sequences aligned strings, or uint8[n, L] codes with return_codes:
+        the walkers sitting at that temperature at the end, in ladder order), 'energies' (float64[T, n], E of those sequences),
+        'swap_acceptance' (float64[R - 1], between neighbours of the ladder in ascending beta over the R distinct temperatures;
+        NaN where nothing was attempted), 'swap_attempts', 'mean_energy' and 'heat_capacity' (float64[T]: <E> and
+        C = beta^2 Var E over all ladders and the rounds past burn-in, NaN without such rounds), 'num_rounds'}."""
+        opts = tempered_options(num_sequences, temperatures, num_sweeps, swap_interval, seed, burn_in_sweeps, self._potts_exc)
+        self._one_gpu('sample_sequences_tempered')
+        bio, L, _q = self._potts_dims()
+        n, R = opts['n'], opts['betas'].size
+        X0 = initial_codes(initial, n, bio, L, self._potts_table, self._potts_exc)
+        self._potts_logger.info('\n\tReplica-exchange Gibbs sampling: {} ladders of {} temperatures, {} sweeps, exchange every {}'.format(
+            n, R, opts['num_sweeps'], opts['swap_interval']))
+        res = self._potts_call('sample_tempered', n, opts['betas'], opts['num_sweeps'], swap_interval=opts['swap_interval'],
+                               seed=opts['seed'], initial=None if X0 is None else np.repeat(X0, R, axis=0), trace=True)
+        letters = state_letters(bio)
+
+        def text(codes):
+            return np.ascontiguousarray(codes) if return_codes else [''.join(letters[c] for c in row) for row in codes]
+        return tempered_result(opts, res, text)
 
     def find_local_maxima(self, sequences=None, free_sites=None, fixed_sites=None, max_steps=None, min_gain=0.0, return_paths=False):
         """Greedy ascent of every sequence to a local maximum of E (as in compute_sequence_energies) on the GPU: a chain
@@ -486,6 +586,56 @@ def run_sample_conditional(instance, prefix, msa_file, output_dir, biomolecule, 
     return path
 
 
+def add_tempered_arguments(p):
+    """The options of the sample_tempered sub-command (plmdca and mfdca command lines)."""
+    p.add_argument('--num_sequences', type=int, required=True, help='sequences per temperature (independent ladders) (addition)')
+    p.add_argument('--temperatures', required=True, help='the ladder, comma separated, such as 0.5,0.7,1,1.5 (inf allowed) (addition)')
+    p.add_argument('--num_sweeps', type=int, default=1000, help='Gibbs sweeps over all sites per walker (addition)')
+    p.add_argument('--swap_interval', type=int, default=1, help='sweeps between exchange rounds; 0: no exchange (addition)')
+    p.add_argument('--seed', type=int, default=0, help='seed of the counter-based generator (addition)')
+    p.add_argument('--initial_file', help='FASTA file with 1 or num_sequences aligned starting sequences (default: random) (addition)')
+
+
+TEMPERED_OPTIONS = ('num_sequences', 'temperatures', 'num_sweeps', 'swap_interval', 'seed', 'initial_file')
+
+
+def parse_temperatures(text, exc_type):
+    """'0.5,0.7,1,1.5' -> [0.5, 0.7, 1.0, 1.5] ('inf' allowed; tempered_options checks the values)."""
+    try:
+        return [float(part) for part in str(text).split(',')]
+    except ValueError:
+        raise exc_type('temperatures are written like 0.5,0.7,1,1.5, not {!r}'.format(text))
+
+
+def run_sample_tempered(instance, prefix, msa_file, output_dir, metadata, biomolecule, exc_type, opts):
+    """sample_tempered of the plmdca and mfdca command lines -> the paths of <output_dir>/<prefix>_tempered_samples_<alignment
+    base>.fa (per temperature, then per sample: a record whose name carries both and the energy) and <prefix>_tempered_sampling_
+    <alignment base>.txt (one row per temperature: T, mean energy, heat capacity, acceptance to the next colder temperature)."""
+    from .dca_utilities import dca_utilities
+    opts = dict(opts or {})
+    if opts.get('num_sequences') is None or opts.get('temperatures') is None:
+        raise exc_type('sample_tempered needs --num_sequences and --temperatures')
+
+    def opt(name, default):
+        return default if opts.get(name) is None else opts[name]
+    temps = parse_temperatures(opts['temperatures'], exc_type)
+    dca_utilities.create_directories(output_dir)
+    res = instance.sample_sequences_tempered(opts['num_sequences'], temps, num_sweeps=opt('num_sweeps', 1000),
+                                             swap_interval=opt('swap_interval', 1), seed=opt('seed', 0),
+                                             initial=opts.get('initial_file'), return_codes=True)
+    letters = state_letters(biomolecule)
+    seqs = [[''.join(letters[c] for c in row) for row in codes] for codes in res['sequences']]
+    # each temperature's level on the ladder of distinct temperatures (descending T is ascending beta), then its acceptance
+    t = np.asarray(res['temperatures'], dtype=np.float64)
+    level = np.asarray(np.unique(-t, return_inverse=True)[1]).reshape(-1)
+    acc = np.append(np.asarray(res['swap_acceptance'], dtype=np.float64), np.nan)
+    fa = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_tempered_samples_', postfix='.fa')
+    txt = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_tempered_sampling_', postfix='.txt')
+    dca_utilities.write_tempered_samples(fa, res['temperatures'], seqs, res['energies'])
+    dca_utilities.write_tempered_summary(txt, res, acc[level], metadata=metadata)
+    return fa, txt
+
+
 def add_ascent_arguments(p):
     """The options of the find_local_maxima sub-command (plmdca and mfdca command lines)."""
     p.add_argument('--query_file', help='FASTA file of aligned starting sequences (default: the records of msa_file) (addition)')
@@ -552,7 +702,7 @@ def run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, opts):
 
 def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata, biomolecule, table, exc_type,
                    query_file=None, wildtype_file=None, sampling=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None,
-                   conditional=None, ascent=None):
+                   conditional=None, ascent=None, tempered=None):
     """compute_energies / compute_mutation_effects / sample_sequences / compute_pseudo_log_likelihood / compare_sequences of the
     plmdca and mfdca command lines -> the path of the file written: <output_dir>/<prefix>_energies_<alignment base>.txt,
     <prefix>_mutation_effects_<alignment base>.txt, <prefix>_samples_<alignment base>.fa,
@@ -564,6 +714,8 @@ def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata
         return run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, ais)
     if the_command == 'sample_conditional':
         return run_sample_conditional(instance, prefix, msa_file, output_dir, biomolecule, exc_type, conditional)
+    if the_command == 'sample_tempered':        # tempered: its options (TEMPERED_OPTIONS; run_sample_tempered)
+        return run_sample_tempered(instance, prefix, msa_file, output_dir, metadata, biomolecule, exc_type, tempered)
     if the_command == 'find_local_maxima':      # ascent: its options (ASCENT_OPTIONS; run_find_local_maxima)
         return run_find_local_maxima(instance, prefix, msa_file, output_dir, metadata, exc_type, query_file, ascent)
     if the_command == 'compare_sequences':

@@ -573,6 +573,16 @@ int dca_plm_ascend(dca_ctx* ctx, const uint8_t* X, int n, const int32_t* free_si
     return dca_potts_ascend(ctx, ps, X, n, free_sites, num_free, max_steps, min_gain, out, steps_out, converged_out, gain_out, path_out,
                             path_gain_out);
 }
+// replica-exchange Gibbs sampling (tempered.hip) under the plm engine's x; one GPU only
+int dca_plm_sample_tempered(dca_ctx* ctx, const dca_pt_args* args, uint8_t* out, int32_t* levels_out, double* energies_out,
+                            uint64_t* attempts_out, uint64_t* accepts_out, double* energy_trace_out, int* rounds_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    PottsSource ps;
+    DCA_TRY(ctx->plm->potts_source(&ps, true));
+    return dca_potts_sample_tempered(ctx, ps, args, out, levels_out, energies_out, attempts_out, accepts_out, energy_trace_out, rounds_out);
+}
 // annealed importance sampling (ais.hip) of the plm engine's x
 int dca_plm_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
 {
@@ -874,6 +884,15 @@ int dca_mf_ascend(dca_ctx* ctx, const uint8_t* X, int n, const int32_t* free_sit
     DCA_TRY(m.get(ctx));
     return dca_potts_ascend(ctx, m.ps, X, n, free_sites, num_free, max_steps, min_gain, out, steps_out, converged_out, gain_out, path_out,
                             path_gain_out);
+}
+int dca_mf_sample_tempered(dca_ctx* ctx, const dca_pt_args* args, uint8_t* out, int32_t* levels_out, double* energies_out,
+                           uint64_t* attempts_out, uint64_t* accepts_out, double* energy_trace_out, int* rounds_out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_mf(ctx));
+    MfPotts m;
+    DCA_TRY(m.get(ctx));
+    return dca_potts_sample_tempered(ctx, m.ps, args, out, levels_out, energies_out, attempts_out, accepts_out, energy_trace_out, rounds_out);
 }
 int dca_mf_ais(dca_ctx* ctx, const dca_ais_args* args, double* log_weights_out, double* log_z0_out, uint8_t* chains_out)
 {

@@ -267,7 +267,8 @@ int dca_potts_ascend(dca_ctx* ctx, const PottsSource& ps, const uint8_t* X, int 
 
 // Philox4x32-10 of the samplers (sample.hip, ais.hip): key = (seed lo, seed hi), counter = (chain, sweep, site, tag), each
 // word the value mod 2^32; U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  Tags: 0 Gibbs draw, 1 random start, 2 AIS start,
-// 3 ancestral draw of the autoregressive sampler (ardca.hip, counter (chain, 0, site, 3)).
+// 3 ancestral draw of the autoregressive sampler (ardca.hip, counter (chain, 0, site, 3)), 4 the start vectors of the PCA
+// (pca.hip), 5 the exchange decision of replica exchange (tempered.hip, counter (ladder, round, lower level, 5)).
 static __host__ __device__ __forceinline__ void philox4x32_10(const uint32_t in[4], const uint32_t k[2], uint32_t out[4])
 {
     uint32_t c0 = in[0], c1 = in[1], c2 = in[2], c3 = in[3], k0 = k[0], k1 = k[1];
@@ -293,18 +294,27 @@ static __device__ __forceinline__ double philox_uniform(uint64_t seed, uint64_t 
 // swept too and never read).  dca_chains_start: tag-1 random starts of chains first_chain + c, or the host rows `initial`
 // (n x L codes < q, checked by the caller).  dca_chains_sweeps: `sweeps` launches numbered first_sweep.., one per sweep, under
 // the tag "sample"; with dBase (L x q device doubles) the sweeps draw from the AIS interpolation h0 + bk * (u - h0) instead
-// (beta unused).  dca_chains_read: the n x L rows to the host (synchronises).  Any nS that is a multiple of 64 works (ais.hip
-// uses multiples of 128, the energy kernels' stride).
+// (beta unused); with dBetas (nS device doubles) chain c sweeps under its own dBetas[c] in the place of beta (tempered.hip).
+// dca_chains_read: the n x L rows to the host (synchronises).  Any nS that is a multiple of 64 works (ais.hip and tempered.hip
+// use multiples of 128, the energy kernels' stride: `stride` of dca_chains_start).
 struct DcaChains { int n = 0, L = 0, nS = 0; DevBuf<uint8_t> dState; };
-int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial);
+int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial,
+                     int stride = 64);
 int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const PottsSource& ps, int sweeps, uint64_t seed, uint64_t first_chain,
-                      uint64_t first_sweep, double beta, const double* dBase = nullptr, double bk = 0.0);
+                      uint64_t first_sweep, double beta, const double* dBase = nullptr, double bk = 0.0,
+                      const double* dBetas = nullptr);
 int dca_chains_read(dca_ctx* ctx, const DcaChains& ch, uint8_t* out);
 
 // ---- ais.hip : annealed importance sampling of log Z under the same sources (dca_plm_ais / dca_mf_ais; arguments checked here)
 int dca_potts_ais(dca_ctx* ctx, const PottsSource& ps, const dca_ais_args* args, double* log_weights_out, double* log_z0_out,
                   uint8_t* chains_out);
 double dca_ais_log_z0(const double* h0, int L, int q);    // host, L x q base fields
+
+// ---- tempered.hip : replica-exchange Gibbs sampling on a temperature ladder under the same sources (dca_plm_sample_tempered /
+// dca_mf_sample_tempered; arguments checked here)
+int dca_potts_sample_tempered(dca_ctx* ctx, const PottsSource& ps, const dca_pt_args* args, uint8_t* out, int32_t* levels_out,
+                              double* energies_out, uint64_t* attempts_out, uint64_t* accepts_out, double* energy_trace_out,
+                              int* rounds_out);
 
 // ---- boltzmann.hip : Boltzmann machine learning of the plm vector (dca_plm_bm_*).  The run lives in ctx->bm; dca_bm_free ends
 // it (alignment, weights, configure, L-BFGS begin, engine release, destroy).  x: the plm engine's device vector (PlmEngineBase::

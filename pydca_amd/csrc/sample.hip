@@ -10,8 +10,9 @@
 // (ascending sums), or the largest a with p_a > 0 if rounding leaves none.  U = Philox4x32-10 of
 //   key = (seed lo, seed hi), counter = (chain, sweep, site, tag) (each word the value mod 2^32), tag 0: Gibbs draw,
 //   tag 1: initial state (sweep word 0, s_i = floor(U * q)); U = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53.  (Tag 2 is the AIS
-//   start draw, ais.hip.)  The INTERP instantiations draw from the AIS interpolation c(a) = h0_i(a) + bk (u(a) - h0_i(a)) instead
-//   of beta * u(a); the others compile to the plain sweep.
+//   start draw, ais.hip; tag 5 the exchange decision, tempered.hip.)  The kSweepInterp instantiations draw from the AIS
+//   interpolation c(a) = h0_i(a) + bk (u(a) - h0_i(a)) instead of beta * u(a); the kSweepTempered ones (tempered.hip) are the
+//   plain sweep with chain c's own beta_c, read from a device array, in the place of beta; the others compile to the plain sweep.
 //
 // Geometry: one workgroup of 4 waves holds 64 chains (lane = chain) in lockstep over the sites.  Wave w sums the j = w
 // (mod 4) terms; the partials meet in LDS in ascending w and wave 0 draws.  Row i of J (L blocks of q x q) streams through
@@ -57,14 +58,19 @@ __global__ void initial_state_kernel(int n, int L, int q, int nS, uint64_t seed,
 
 // One sweep.  grid: nS / 64 workgroups.  LDS: two chunk buffers (CJ blocks of q x QM values of S each), the partial
 // buffer (QM x 64 doubles), and with RES the chain codes (L x 64 bytes, site-major).  R: chunk elements per thread.
-// INTERP (annealed importance sampling, ais.hip): wave 0 draws from c(a) = h0_i(a) + bk * (u(a) - h0_i(a)),
-// p_a = exp(c(a) - max_b c(b)), with h0 the L x q base fields (device); beta is not used.  Without it h0 and bk are not read.
-template <typename S, int QM, bool RES, int R, bool INTERP>
+// MODE kSweepInterp (annealed importance sampling, ais.hip): wave 0 draws from c(a) = h0_i(a) + bk * (u(a) - h0_i(a)),
+// p_a = exp(c(a) - max_b c(b)), with aux = h0, the L x q base fields (device); beta is not used.  MODE kSweepTempered (replica
+// exchange, tempered.hip): p_a = exp(beta_c * (u(a) - m)) with beta_c = aux[c], one value per chain of the state buffer (nS
+// doubles, device); beta and bk are not used.  MODE kSweepPlain reads neither aux nor bk.
+constexpr int kSweepPlain = 0, kSweepInterp = 1, kSweepTempered = 2;
+
+template <typename S, int QM, bool RES, int R, int MODE>
 __global__ __launch_bounds__(kSThreads)
 void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __restrict__ mfh, int L, int q, int ld, int CJ,
                         uint8_t* __restrict__ state, int nS, uint64_t seed, uint64_t first_chain, uint64_t sweep, double beta,
-                        const double* __restrict__ h0, double bk)
+                        const double* __restrict__ aux, double bk)
 {
+    constexpr bool INTERP = MODE == kSweepInterp;
     extern __shared__ __attribute__((aligned(16))) unsigned char sample_smem[];
     const int blk = q * QM;                                   // values of one staged block
     const int bufVals = CJ * blk;
@@ -79,6 +85,8 @@ void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __res
     const int nch = (L + CJ - 1) / CJ;
     const int steps = L * nch;
     const int chunkVals = CJ * qq;
+    double betaC = beta;
+    if constexpr (MODE == kSweepTempered) betaC = aux[c0 + lane];
 
     for (int e = tid; e < 2 * bufVals; e += kSThreads) buf0[e] = (S)0;      // the row padding stays zero
     if (RES)
@@ -160,7 +168,7 @@ void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __res
 #pragma unroll
                     for (int a = 0; a < QM; ++a)
                         if (a < q) {
-                            const double b0 = h0[(size_t)i * q + a];
+                            const double b0 = aux[(size_t)i * q + a];
                             u[a] = b0 + bk * (u[a] - b0);
                         }
                 }
@@ -171,7 +179,7 @@ void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __res
 #pragma unroll
                 for (int a = 0; a < QM; ++a) {
                     if constexpr (INTERP) u[a] = a < q ? exp(u[a] - m) : 0.0;
-                    else u[a] = a < q ? exp(beta * (u[a] - m)) : 0.0;
+                    else u[a] = a < q ? exp(betaC * (u[a] - m)) : 0.0;
                     T += u[a];
                 }
                 const double r = philox_uniform(seed, chain, sweep, i, 0) * T;
@@ -197,39 +205,41 @@ void gibbs_sweep_kernel(const S* __restrict__ src, int kind, const double* __res
 }
 
 // what one sweep launch takes besides the model
-struct SweepArgs { uint8_t* dState; int nS; uint64_t seed, first_chain, sweep; double beta; const double* h0; double bk; };
+// (h0: the interpolated sweep; betas: the tempered one; neither: the plain one)
+struct SweepArgs { uint8_t* dState; int nS; uint64_t seed, first_chain, sweep; double beta; const double* h0; double bk; const double* betas; };
 
-template <typename S, int QM, bool RES, bool INTERP>
+template <typename S, int QM, bool RES, int MODE>
 hipError_t launch_sweep(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
     constexpr int R = sample_regs(sizeof(S));
-    auto kern = gibbs_sweep_kernel<S, QM, RES, R, INTERP>;
+    auto kern = gibbs_sweep_kernel<S, QM, RES, R, MODE>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sg.lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(a.nS / kSChains), dim3(kSThreads), sg.lds, ctx->stream, pv.src, pv.kind, pv.mfh, pv.L, pv.q, pv.ld,
-                       sg.CJ, a.dState, a.nS, a.seed, a.first_chain, a.sweep, a.beta, a.h0, a.bk);
+                       sg.CJ, a.dState, a.nS, a.seed, a.first_chain, a.sweep, a.beta, MODE == kSweepTempered ? a.betas : a.h0, a.bk);
     return hipGetLastError();
 }
 
-template <typename S, int QM, bool INTERP>
+template <typename S, int QM, int MODE>
 hipError_t dispatch_res(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
-    if (sg.res) return launch_sweep<S, QM, true, INTERP>(ctx, sg, pv, a);
-    return launch_sweep<S, QM, false, INTERP>(ctx, sg, pv, a);
+    if (sg.res) return launch_sweep<S, QM, true, MODE>(ctx, sg, pv, a);
+    return launch_sweep<S, QM, false, MODE>(ctx, sg, pv, a);
 }
 
-template <typename S, bool INTERP>
+template <typename S, int MODE>
 hipError_t dispatch_qm(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
-    return with_qm(pv.q, [&](auto qm) { return dispatch_res<S, decltype(qm)::value, INTERP>(ctx, sg, pv, a); });
+    return with_qm(pv.q, [&](auto qm) { return dispatch_res<S, decltype(qm)::value, MODE>(ctx, sg, pv, a); });
 }
 
-// h0 NULL: the plain sweep under beta; otherwise the interpolated one (INTERP above)
+// betas: the tempered sweep; else h0: the interpolated one; neither: the plain sweep under beta (MODE above)
 template <typename S>
 hipError_t dispatch_sweep(dca_ctx* ctx, const SampleGeom& sg, const PottsView<S>& pv, const SweepArgs& a)
 {
-    if (a.h0) return dispatch_qm<S, true>(ctx, sg, pv, a);
-    return dispatch_qm<S, false>(ctx, sg, pv, a);
+    if (a.betas) return dispatch_qm<S, kSweepTempered>(ctx, sg, pv, a);
+    if (a.h0) return dispatch_qm<S, kSweepInterp>(ctx, sg, pv, a);
+    return dispatch_qm<S, kSweepPlain>(ctx, sg, pv, a);
 }
 
 }  // namespace
@@ -249,11 +259,12 @@ hipError_t dca_sites_to_rows(dca_ctx* ctx, const uint8_t* dSites, int n, int L, 
 }
 
 // ---- device-resident chains (dca_internal.h): the sampler's state between calls
-int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial)
+int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t seed, uint64_t first_chain, const uint8_t* initial,
+                     int stride)
 {
     *ch = DcaChains();
     ch->n = n; ch->L = L;
-    ch->nS = (int)round_up((size_t)n, kSChains);
+    ch->nS = (int)round_up((size_t)n, (size_t)stride);
     const size_t sites = (size_t)L * ch->nS;
     DevBuf<uint8_t> dRows;
     HIP_TRY_AS(ch->dState.alloc(sites, false), "sample");
@@ -270,14 +281,14 @@ int dca_chains_start(dca_ctx* ctx, DcaChains* ch, int n, int L, int q, uint64_t 
 }
 
 int dca_chains_sweeps(dca_ctx* ctx, const DcaChains& ch, const PottsSource& ps, int sweeps, uint64_t seed, uint64_t first_chain,
-                      uint64_t first_sweep, double beta, const double* dBase, double bk)
+                      uint64_t first_sweep, double beta, const double* dBase, double bk, const double* dBetas)
 {
     const hipError_t e = with_source_type(ps, [&](auto pv) {
         const SampleGeom sg = sample_geometry(pv.L, pv.q, sizeof(*pv.src));
         hipError_t e = hipSuccess;
         for (int t = 0; t < sweeps && e == hipSuccess; ++t) {       // one launch per sweep
             ScopedKernelClock kc(ctx, "sample");
-            e = dispatch_sweep(ctx, sg, pv, SweepArgs{ch.dState, ch.nS, seed, first_chain, first_sweep + (uint64_t)t, beta, dBase, bk});
+            e = dispatch_sweep(ctx, sg, pv, SweepArgs{ch.dState, ch.nS, seed, first_chain, first_sweep + (uint64_t)t, beta, dBase, bk, dBetas});
         }
         return e;
     });

@@ -154,6 +154,28 @@ def write_sampled_sequences(file_name, sequences, energies, header=None):
     _stream(file_name, list(header or []), rows, 'sampled sequences')
 
 
+def write_tempered_samples(file_name, temperatures, sequences, energies):
+    """FASTA of sample_sequences_tempered: per temperature (the caller's order), then per sample, one record
+    '>sample_<k> temperature=<T> energy=<E>' (k from 1 within its temperature; T and E written with %.17g), the aligned
+    sequence on one line.  No reference counterpart."""
+    rows = ('>sample_{} temperature={} energy={}\n{}'.format(k + 1, '%.17g' % float(t), '%.17g' % float(e), seq)
+            for t, seqs, es in zip(temperatures, sequences, energies) for k, (seq, e) in enumerate(zip(seqs, es)))
+    _stream(file_name, [], rows, 'tempered samples')
+
+
+def write_tempered_summary(file_name, result, colder_acceptance, metadata=None):
+    """One row per temperature of sample_sequences_tempered (the caller's order): T, the mean energy and the heat capacity over
+    the exchange rounds past burn-in, and the acceptance of exchanges with the next colder temperature of the ladder (nan for
+    the coldest and where nothing was attempted), each written with %.17g (no reference counterpart)."""
+    header = [_RULE] + list(metadata or [])
+    header += ['#\tExchange rounds: {}'.format(int(result['num_rounds'])),
+               '# Columns: temperature T, mean energy <E>, heat capacity C = Var(E) / T^2 (both over all ladders and the exchange',
+               '# rounds past burn-in) and the accepted fraction of exchanges with the next colder temperature', _RULE]
+    rows = ('{} {} {} {}'.format(*('%.17g' % float(v) for v in rec))
+            for rec in zip(result['temperatures'], result['mean_energy'], result['heat_capacity'], colder_acceptance))
+    _stream(file_name, header, rows, 'tempered sampling summary')
+
+
 def write_local_maxima_sequences(file_name, sequences, energies):
     """FASTA of the final sequences of find_local_maxima: one record '>maximum_of_<k> energy=<E>' per input record k (from 1,
     input order; E written with %.17g), the aligned sequence on one line.  No reference counterpart."""

@@ -21,7 +21,7 @@ def configure_logging():
 def execute_from_command_line(msa_file=None, biomolecule=None, seqid=None, pseudocount=None, the_command=None,
                               refseq_file=None, verbose=False, output_dir=None, apc=False, ranked_by=None,
                               linear_dist=None, num_site_pairs=None, device=0, devices=None, query_file=None, wildtype_file=None, sampling=None,
-                              ais=None, three_site=0, three_site_no_gaps=False, pca=None, conditional=None, ascent=None):
+                              ais=None, three_site=0, three_site_no_gaps=False, pca=None, conditional=None, ascent=None, tempered=None):
     if verbose:
         configure_logging()
     mfdca_instance = meanfield_dca.MeanFieldDCA(msa_file, biomolecule, pseudocount=pseudocount, seqid=seqid, device=device, devices=devices)
@@ -39,7 +39,7 @@ def execute_from_command_line(msa_file=None, biomolecule=None, seqid=None, pseud
         return _potts.run_subcommand(mfdca_instance, the_command.strip(), 'MFDCA', msa_file, output_dir, param_metadata, bio, 1,
                                      meanfield_dca.MeanFieldDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling,
                                      ais=ais, three_site=three_site, three_site_no_gaps=bool(three_site_no_gaps), pca=pca,
-                                     conditional=conditional, ascent=ascent)
+                                     conditional=conditional, ascent=ascent, tempered=tempered)
     if the_command.strip() == 'compute_params':
         fields, couplings = mfdca_instance.compute_params(seqbackmapper=seqbackmapper, ranked_by=ranked_by, linear_dist=linear_dist,
                                                           num_site_pairs=num_site_pairs)
@@ -130,6 +130,8 @@ def run_meanfield_dca(argv=None):
             _potts.add_conditional_arguments(p)
         if name == 'find_local_maxima':
             _potts.add_ascent_arguments(p)
+        if name == 'sample_tempered':
+            _potts.add_tempered_arguments(p)
         if name == 'compute_log_likelihood':
             _potts.add_ais_arguments(p)
         p.add_argument('--device', type=int, default=0, help='GPU index (addition)')
@@ -153,7 +155,8 @@ def run_meanfield_dca(argv=None):
         three_site=args.get('three_site') or 0, three_site_no_gaps=bool(args.get('three_site_no_gaps')),
         pca={k: args.get(k) for k in ('pca', 'num_components', 'seed')},
         conditional={k: args.get(k) for k in _potts.CONDITIONAL_OPTIONS},
-        ascent={k: args.get(k) for k in _potts.ASCENT_OPTIONS})
+        ascent={k: args.get(k) for k in _potts.ASCENT_OPTIONS},
+        tempered={k: args.get(k) for k in _potts.TEMPERED_OPTIONS})
 
 
 if __name__ == '__main__':
