@@ -22,18 +22,15 @@
 // product.  Instead of one logarithm per (pair, state pair, m) the kernel multiplies the r_m and splits the exponent of the
 // running product off into an integer every 4th step (so 4 consecutive r_m may span 2^+-1000 together before anything
 // overflows); one logarithm at the end: eps = T - (log(mantissa product) + exponent sum * ln 2).  No atomics, no scratch.
+// The product kernel's geometry (tile constants, epistasis_tiles, epi_mstart / epi_steps, epi_npre, epi_lds_bytes) is
+// ar_epistasis_plan.h, host code that tests/ar_epistasis_plan_driver.cpp prints for the element audit.
+#include "ar_epistasis_plan.h"
 #include "site_conditionals.h"
 
 #include <algorithm>
 #include <cmath>
 
 namespace {
-
-constexpr int kEThreads = 512;
-constexpr int kERows = 4, kECols = 4;                 // elements per thread: rows tr * 4 + i, columns tc + 16 j
-constexpr int kETileR = kEThreads / 16 * kERows;      // 128 flattened rows (k, a) per workgroup
-constexpr int kETileC = 16 * kECols;                  // 64 flattened columns (l, b)
-constexpr int kERescale = 4;                          // steps between exponent splits (a power of two)
 
 __host__ __device__ __forceinline__ size_t v_offset(int m, int qq) { return (size_t)m * (m - 1) / 2 * qq; }
 
@@ -93,26 +90,26 @@ __global__ void epi_single_kernel(const double* __restrict__ cond, const double*
 // is served with bank conflicts; the 4 row groups of a wave read broadcast addresses).
 // eps: the pair blocks in pair order, element a * q + b.
 template <int QM>
-__global__ __launch_bounds__(kEThreads)
+__global__ __launch_bounds__(kEpiThreads)
 void epi_main_kernel(const double* __restrict__ x, const uint8_t* __restrict__ w, const double* __restrict__ V,
-                     const int2* __restrict__ tiles, int L, int q, double* __restrict__ eps)
+                     const EpiTile* __restrict__ tiles, int L, int q, double* __restrict__ eps)
 {
-    constexpr int NPRE = ((kETileR + kETileC) * QM + kEThreads - 1) / kEThreads;
+    constexpr int NPRE = epi_npre(QM);
     extern __shared__ __attribute__((aligned(16))) unsigned char epi_smem[];
     double* buf = reinterpret_cast<double*>(epi_smem);
     const int QP = q;
-    const int bufVals = (kETileR + kETileC) * q;
-    const int nA = kETileR * q;
+    const int bufVals = (kEpiTileR + kEpiTileC) * q;
+    const int nA = kEpiTileR * q;
     const int tid = threadIdx.x, tr = tid >> 4, tc = tid & 15;
-    const int2 tile = tiles[blockIdx.x];
-    const int R0 = tile.x * kETileR, C0 = tile.y * kETileC;
+    const EpiTile tile = tiles[blockIdx.x];
+    const int R0 = tile.x * kEpiTileR, C0 = tile.y * kEpiTileC;
     const int Lq = L * q, qq = q * q;
-    const int mstart = C0 / q + 1;
-    const int steps = L - mstart;
+    const int mstart = epi_mstart(tile.y, q);
+    const int steps = epi_steps(tile.y, L, q);
 
-    int lcol[kECols];                                  // site of column j; past the table: never joins
+    int lcol[kEpiCols];                                  // site of column j; past the table: never joins
 #pragma unroll
-    for (int j = 0; j < kECols; ++j) {
+    for (int j = 0; j < kEpiCols; ++j) {
         const int C = C0 + tc + 16 * j;
         lcol[j] = C < Lq ? C / q : 0x7fffffff;
     }
@@ -123,7 +120,7 @@ void epi_main_kernel(const double* __restrict__ x, const uint8_t* __restrict__ w
         const int lim = m * qq;                        // rows (k, a) with k < m exist
 #pragma unroll
         for (int i = 0; i < NPRE; ++i) {
-            const int e = tid + i * kEThreads;
+            const int e = tid + i * kEpiThreads;
             const int g = e < nA ? R0 * q + e : C0 * q + (e - nA);
             pre[i] = (e < bufVals && g < lim) ? Vm[g] : 0.0;
         }
@@ -132,17 +129,17 @@ void epi_main_kernel(const double* __restrict__ x, const uint8_t* __restrict__ w
         double* dst = buf + (t & 1) * bufVals;
 #pragma unroll
         for (int i = 0; i < NPRE; ++i) {
-            const int e = tid + i * kEThreads;
+            const int e = tid + i * kEpiThreads;
             if (e < bufVals) dst[e] = pre[i];
         }
     };
 
-    double prod[kERows][kECols];
-    int esum[kERows][kECols];
+    double prod[kEpiRows][kEpiCols];
+    int esum[kEpiRows][kEpiCols];
 #pragma unroll
-    for (int i = 0; i < kERows; ++i)
+    for (int i = 0; i < kEpiRows; ++i)
 #pragma unroll
-        for (int j = 0; j < kECols; ++j) { prod[i][j] = 1.0; esum[i][j] = 0; }
+        for (int j = 0; j < kEpiCols; ++j) { prod[i][j] = 1.0; esum[i][j] = 0; }
 
     if (steps > 0) {
         load(mstart);
@@ -153,37 +150,37 @@ void epi_main_kernel(const double* __restrict__ x, const uint8_t* __restrict__ w
     for (int t = 0; t < steps; ++t) {
         const int m = mstart + t;
         if (t + 1 < steps) load(m + 1);
-        const double* A = buf + (t & 1) * bufVals + (tr * kERows) * QP;
-        const double* B = buf + (t & 1) * bufVals + (kETileR + tc) * QP;
-        double r[kERows][kECols];
+        const double* A = buf + (t & 1) * bufVals + (tr * kEpiRows) * QP;
+        const double* B = buf + (t & 1) * bufVals + (kEpiTileR + tc) * QP;
+        double r[kEpiRows][kEpiCols];
 #pragma unroll
-        for (int i = 0; i < kERows; ++i)
+        for (int i = 0; i < kEpiRows; ++i)
 #pragma unroll
-            for (int j = 0; j < kECols; ++j) r[i][j] = 0.0;
+            for (int j = 0; j < kEpiCols; ++j) r[i][j] = 0.0;
 #pragma unroll 1
         for (int c = 0; c < q; ++c) {
-            double av[kERows], bv[kECols];
+            double av[kEpiRows], bv[kEpiCols];
 #pragma unroll
-            for (int i = 0; i < kERows; ++i) av[i] = A[i * QP + c];
+            for (int i = 0; i < kEpiRows; ++i) av[i] = A[i * QP + c];
 #pragma unroll
-            for (int j = 0; j < kECols; ++j) bv[j] = B[16 * j * QP + c];
+            for (int j = 0; j < kEpiCols; ++j) bv[j] = B[16 * j * QP + c];
 #pragma unroll
-            for (int i = 0; i < kERows; ++i)
+            for (int i = 0; i < kEpiRows; ++i)
 #pragma unroll
-                for (int j = 0; j < kECols; ++j) r[i][j] = fma(av[i], bv[j], r[i][j]);
+                for (int j = 0; j < kEpiCols; ++j) r[i][j] = fma(av[i], bv[j], r[i][j]);
         }
 #pragma unroll
-        for (int j = 0; j < kECols; ++j) {
+        for (int j = 0; j < kEpiCols; ++j) {
             if (m > lcol[j]) {
 #pragma unroll
-                for (int i = 0; i < kERows; ++i) prod[i][j] *= r[i][j];
+                for (int i = 0; i < kEpiRows; ++i) prod[i][j] *= r[i][j];
             }
         }
-        if ((t & (kERescale - 1)) == kERescale - 1) {
+        if ((t & (kEpiRescale - 1)) == kEpiRescale - 1) {
 #pragma unroll
-            for (int i = 0; i < kERows; ++i)
+            for (int i = 0; i < kEpiRows; ++i)
 #pragma unroll
-                for (int j = 0; j < kECols; ++j) {
+                for (int j = 0; j < kEpiCols; ++j) {
                     const long long bits = __double_as_longlong(prod[i][j]);
                     esum[i][j] += (int)((bits >> 52) & 0x7ff) - 1023;
                     prod[i][j] = __longlong_as_double((bits & 0x800fffffffffffffLL) | 0x3ff0000000000000LL);
@@ -195,12 +192,12 @@ void epi_main_kernel(const double* __restrict__ x, const uint8_t* __restrict__ w
 
     const double* J = x + (size_t)Lq;
 #pragma unroll
-    for (int i = 0; i < kERows; ++i) {
-        const int R = R0 + tr * kERows + i;
+    for (int i = 0; i < kEpiRows; ++i) {
+        const int R = R0 + tr * kEpiRows + i;
         if (R >= Lq) continue;
         const int k = R / q, a = R - k * q, wk = w[k];
 #pragma unroll
-        for (int j = 0; j < kECols; ++j) {
+        for (int j = 0; j < kEpiCols; ++j) {
             const int C = C0 + tc + 16 * j;
             if (C >= Lq) continue;
             const int l = lcol[j], b = C - l * q;
@@ -219,40 +216,28 @@ void epi_main_kernel(const double* __restrict__ x, const uint8_t* __restrict__ w
 }
 
 template <int QM>
-hipError_t launch_main(dca_ctx* ctx, const double* x, const uint8_t* w, const double* V, const int2* tiles, int ntiles,
+hipError_t launch_main(dca_ctx* ctx, const double* x, const uint8_t* w, const double* V, const EpiTile* tiles, int ntiles,
                        int L, int q, double* eps)
 {
     auto kern = epi_main_kernel<QM>;
-    const size_t lds = (size_t)2 * (kETileR + kETileC) * q * sizeof(double);
+    const size_t lds = epi_lds_bytes(q);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(kEThreads), lds, ctx->stream, x, w, V, tiles, L, q, eps);
+    hipLaunchKernelGGL(kern, dim3(ntiles), dim3(kEpiThreads), lds, ctx->stream, x, w, V, tiles, L, q, eps);
     return hipGetLastError();
-}
-
-// the tiles that hold a pair k < l, heaviest (most later sites to stream: the lowest column tile) first
-std::vector<int2> epistasis_tiles(int L, int q)
-{
-    const int Lq = L * q;
-    std::vector<int2> tiles;
-    for (int ct = 0; ct * kETileC < Lq; ++ct) {
-        const int lmax = std::min(Lq - 1, ct * kETileC + kETileC - 1) / q;
-        for (int rt = 0; rt * kETileR < Lq && rt * kETileR / q < lmax; ++rt) tiles.push_back(make_int2(rt, ct));
-    }
-    return tiles;
 }
 
 struct EpiBuffers {
     DevBuf<uint8_t> dW;
     DevBuf<double> dCond, dPm, dSpm, dTerm, dV, dD, dVec;
-    DevBuf<int2> dTiles;
+    DevBuf<EpiTile> dTiles;
 };
 
 // B.dVec <- L q zeros, then eps in pair order (the plm layout scoring.hip reads); B.dD <- d.  Everything stays on the device.
 int epistasis_device(dca_ctx* ctx, const double* dx, int L, int q, const uint8_t* wildtype, EpiBuffers& B)
 {
     const size_t Lq = (size_t)L * q, pairs = (size_t)L * (L - 1) / 2, qq = (size_t)q * q;
-    const std::vector<int2> tiles = epistasis_tiles(L, q);
+    const std::vector<EpiTile> tiles = epistasis_tiles(L, q);
     if (B.dW.alloc((size_t)L, false) != hipSuccess || B.dCond.alloc(Lq, false) != hipSuccess || B.dPm.alloc(Lq, false) != hipSuccess ||
         B.dSpm.alloc(Lq, false) != hipSuccess || B.dD.alloc(Lq, false) != hipSuccess || B.dTerm.alloc(pairs * q, false) != hipSuccess ||
         B.dV.alloc(pairs * qq, false) != hipSuccess || B.dVec.alloc(Lq + pairs * qq, false) != hipSuccess ||
@@ -263,7 +248,7 @@ int epistasis_device(dca_ctx* ctx, const double* dx, int L, int q, const uint8_t
     }
     DCA_TRY(dca_ar_engine_conditionals(ctx->ar, wildtype, B.dCond));
     HIP_TRY(hipMemcpyAsync(B.dW, wildtype, (size_t)L, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(B.dTiles, tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(B.dTiles, tiles.data(), tiles.size() * sizeof(EpiTile), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(B.dVec, 0, Lq * sizeof(double), ctx->stream));
     static const char* who = "arDCA epistasis";
     {
