@@ -22,14 +22,11 @@
 #include <string>
 
 #include "dca_internal.h"
+#include "cholinv_plan.h"      // MASK_*, WALK_*, and every launch decision that is host arithmetic
 
 namespace {
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
-
-enum { MASK_NONE = 0, MASK_LOWER = 1 /* k <= row */, MASK_UPPER = 2 /* k >= row */ };
-
-enum { WALK_ROWS = 0, WALK_ROWS_REVERSED = 1 /* lower triangular A */, WALK_COLUMNS_REVERSED = 2 /* lower triangular B; grid transposed */ };
 
 constexpr int BM = 64, BN = 64;
 
@@ -55,159 +52,15 @@ struct GemmArgs {
     const double* Cin = nullptr; int ldcin = 0;   // beta != 0: the addend is read from here instead of from C (C is then written only)
 };
 
-// The register-staged product on 64 x 64 tiles, instantiated with BK = 64 only (the BK = 16 throughput form gave way to the
-// LDS-DMA kernel below): for the many products of
-// the recursion that are a handful of tiles on an otherwise empty GPU -- their time is a chain of global
-// round trips, one per k-tile, so a four times deeper tile means four times fewer of them (K = 64: one).
-template <int BK>
-constexpr size_t gemm_lds_bytes() { return (size_t)2 * (BM + BN) * (BK + 2) * sizeof(double); }
-
-template <int BK>
-__global__ __launch_bounds__(256)
-void gemm_nt_f64_kernel(GemmArgs g)
-{
-    constexpr int LDS_STRIDE = BK + 2;   // doubles; even: rows stay 16-byte aligned, so a lane's two neighbouring k values are ONE
-                                         // ds_read_b128 / ds_write_b128 (operands of two MFMAs; the k order inside a tile is free as long as A and B agree)
-    constexpr int PG = BK / 16;          // 16-byte pieces per thread and row: the row's BK/2 pieces over 8 threads
-    extern __shared__ __attribute__((aligned(16))) unsigned char dca_gemm_smem[];
-    double* const As = reinterpret_cast<double*>(dca_gemm_smem);      // [2][BM * LDS_STRIDE]
-    double* const Bs = As + 2 * BM * LDS_STRIDE;                      // [2][BN * LDS_STRIDE]
-    const int ti = g.walk == WALK_COLUMNS_REVERSED ? (int)blockIdx.x : g.walk == WALK_ROWS_REVERSED ? (int)(gridDim.y - 1 - blockIdx.y) : (int)blockIdx.y + g.row0;
-    const int tj = g.walk == WALK_COLUMNS_REVERSED ? (int)(gridDim.y - 1 - blockIdx.y) : (int)blockIdx.x;
-    if (g.lowerOnly && tj > ti) return;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-
-    // K range implied by the triangular operands
-    int kLo = 0, kHi = g.K;
-    if (g.maskA == MASK_LOWER) kHi = min(kHi, (ti + 1) * BM);
-    if (g.maskA == MASK_UPPER) kLo = max(kLo, ti * BM);
-    if (g.maskB == MASK_LOWER) kHi = min(kHi, (tj + 1) * BN);
-    if (g.maskB == MASK_UPPER) kLo = max(kLo, tj * BN);
-    kLo = kLo / BK * BK;
-
-    double4_t acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) acc[m][n] = (double4_t){0.0, 0.0, 0.0, 0.0};
-
-    // staging role: 16-byte pieces, thread -> rows sr and sr + 32, doubles sp + 16 * pg, +1 of the k-tile, so that
-    // one wave-wide load covers 8 full 128-byte lines.  global -> registers (raw) -> LDS; the triangular masks are
-    // applied when a tile is WRITTEN to LDS, after the MFMAs of the current tile, so the loads of the next tile
-    // are in flight during those MFMAs instead of being waited for right away.
-    typedef double double2_t __attribute__((ext_vector_type(2)));
-    const int sr = tid >> 3, sp = (tid & 7) * 2;
-    const double* Ap = g.A + (size_t)(ti * BM + sr) * g.lda + sp;
-    const double* Bp = g.B + (size_t)(tj * BN + sr) * g.ldb + sp;
-    const size_t aStep = (size_t)32 * g.lda, bStep = (size_t)32 * g.ldb;
-    double2_t ra[2][PG], rb[2][PG];
-    auto load_tile = [&](int k0) {
-#pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
-#pragma unroll
-            for (int pg = 0; pg < PG; ++pg) {
-                const int kp = k0 + 16 * pg;
-                ra[ps][pg] = *reinterpret_cast<const double2_t*>(Ap + ps * aStep + kp);
-                rb[ps][pg] = *reinterpret_cast<const double2_t*>(Bp + ps * bStep + kp);
-            }
-    };
-    auto store_tile = [&](int buf, int k0) {
-        // only k-tiles that cross the diagonal of a triangular operand's row block need masking (wave-uniform test)
-        const bool diagA = g.maskA != MASK_NONE && k0 + BK > ti * BM && k0 < (ti + 1) * BM;
-        const bool diagB = g.maskB != MASK_NONE && k0 + BK > tj * BN && k0 < (tj + 1) * BN;
-        if (diagA || diagB) {
-#pragma unroll
-            for (int ps = 0; ps < 2; ++ps) {
-                // k range in which the operand row is non-zero: lower k <= row, upper k >= row
-                const int aRow = ti * BM + sr + 32 * ps, bRow = tj * BN + sr + 32 * ps;
-                const int aLo = g.maskA == MASK_UPPER ? aRow : INT_MIN, aHi = g.maskA == MASK_LOWER ? aRow : INT_MAX;
-                const int bLo = g.maskB == MASK_UPPER ? bRow : INT_MIN, bHi = g.maskB == MASK_LOWER ? bRow : INT_MAX;
-#pragma unroll
-                for (int pg = 0; pg < PG; ++pg)
-#pragma unroll
-                    for (int u = 0; u < 2; ++u) {
-                        const int k = k0 + 16 * pg + sp + u;
-                        ra[ps][pg][u] = (k < aLo || k > aHi) ? 0.0 : ra[ps][pg][u];
-                        rb[ps][pg][u] = (k < bLo || k > bHi) ? 0.0 : rb[ps][pg][u];
-                    }
-            }
-        }
-#pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
-#pragma unroll
-            for (int pg = 0; pg < PG; ++pg) {
-                double* ad = As + buf * BM * LDS_STRIDE + (sr + 32 * ps) * LDS_STRIDE + 16 * pg + sp;
-                double* bd = Bs + buf * BN * LDS_STRIDE + (sr + 32 * ps) * LDS_STRIDE + 16 * pg + sp;
-                *reinterpret_cast<double2_t*>(ad) = ra[ps][pg];
-                *reinterpret_cast<double2_t*>(bd) = rb[ps][pg];
-            }
-    };
-
-    const int nk = (kHi - kLo + BK - 1) / BK;
-    auto mma_tile = [&](int buf) {
-        const double* as = As + buf * BM * LDS_STRIDE;
-        const double* bs = Bs + buf * BN * LDS_STRIDE;
-#pragma unroll
-        for (int kk = 0; kk < BK / 8; ++kk) {
-            // lane group g = lane >> 4 holds k = 8 kk + 2 g, 8 kk + 2 g + 1: the first MFMA sums the even, the second the odd ones
-            const int kcol = kk * 8 + 2 * (lane >> 4);
-            const double2_t a0 = *reinterpret_cast<const double2_t*>(&as[(wm * 32 + (lane & 15)) * LDS_STRIDE + kcol]);
-            const double2_t a1 = *reinterpret_cast<const double2_t*>(&as[(wm * 32 + 16 + (lane & 15)) * LDS_STRIDE + kcol]);
-            const double2_t b0 = *reinterpret_cast<const double2_t*>(&bs[(wn * 32 + (lane & 15)) * LDS_STRIDE + kcol]);
-            const double2_t b1 = *reinterpret_cast<const double2_t*>(&bs[(wn * 32 + 16 + (lane & 15)) * LDS_STRIDE + kcol]);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[h], b0[h], acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0[h], b1[h], acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[h], b0[h], acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1[h], b1[h], acc[1][1], 0, 0, 0);
-            }
-        }
-    };
-#ifndef DCA_GEMM_ABLATE
-#define DCA_GEMM_ABLATE 0          // tools/experiments/gemm_bench.hip, timing only: 1 no global loads in the loop, 2 no LDS stores, 4 no barrier
-#endif
-    if (nk > 0) {
-        load_tile(kLo);
-        store_tile(0, kLo);
-    }
-    __syncthreads();
-    for (int t = 0; t < nk; ++t) {
-        const int buf = t & 1;
-        if (t + 1 < nk && !(DCA_GEMM_ABLATE & 1)) load_tile(kLo + (t + 1) * BK);
-        mma_tile(buf);
-        if (t + 1 < nk && !(DCA_GEMM_ABLATE & 2)) store_tile(buf ^ 1, kLo + (t + 1) * BK);
-        if (!(DCA_GEMM_ABLATE & 4)) __syncthreads();
-    }
-
-    // epilogue.  f64 16x16x4 accumulator layout: col = lane & 15, row = (lane >> 4) + 4 * reg
-    // (the mirror stores are 8 bytes at stride ldcm; transposing the block through LDS first made no
-    // measurable difference to the inverse)
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = ti * BM + wm * 32 + m * 16 + (lane >> 4) + 4 * r;
-                const int j = tj * BN + wn * 32 + n * 16 + (lane & 15);
-                if (g.lowerOnly && j > i) continue;
-                double v = g.alpha * acc[m][n][r];
-                double* cp = g.C + (size_t)i * g.ldc + j;
-                if (g.beta != 0.0) v += g.beta * (g.Cin ? g.Cin[(size_t)i * g.ldcin + j] : *cp);
-                *cp = v;
-                if (g.Cm && !(g.lowerOnly && i == j)) g.Cm[(size_t)j * g.ldcm + i] = v;
-            }
-}
-
 // The deep-k product on 32 x 32 output tiles, for launches that are far fewer than one 64 x 64 tile per CU: a tile's
 // time is its k loop on the matrix pipe (64 cycles per 16 x 16 x 4 MFMA, one wave per SIMD) and 256 CUs are there, so a
 // quarter of the work per workgroup on four times as many CUs is what shortens the chain of small products in the
 // recursion (plain product of n = 640: 34 -> 21 us, n = 256: 16 -> 8, the 2 x 2-tile products of the 256-nodes 10.6 -> 5.2 us;
-// inverse at n = 10 048: 27.1 -> 24.2 ms, at n = 4000: 4.96 -> 3.95 ms).  Same staging as gemm_nt_f64_kernel<64> (one pass of 32 rows per operand), each wave
-// one 16 x 16 accumulator.
+// inverse at n = 10 048: 27.1 -> 24.2 ms, at n = 4000: 4.96 -> 3.95 ms).  Each wave one 16 x 16 accumulator.
+// Staging: global -> registers (raw) -> LDS in 16-byte pieces, one wave-wide load covering 8 full 128-byte lines; the triangular
+// masks are applied when a tile is WRITTEN to LDS, after the MFMAs of the current tile, so the loads of the next tile are in
+// flight during those MFMAs.  (The register-staged kernel on 64 x 64 tiles that this one descends from sat between two
+// dispatch bounds that were equal in every setting, 400 / 400 and 16 / 16 in the sweep: no size reached it, and it is gone.)
 __device__ __forceinline__ void gemm_nt_f64_small_tile(const GemmArgs& g, int bx, int by, int gy)
 {
     constexpr int TM = 32, BK = 64;
@@ -320,8 +173,8 @@ void gemm_nt_f64_small_pair_kernel(GemmArgs g0, int gx0, int gy0, GemmArgs g1, i
 }
 
 // The same product with the operand tiles brought into LDS by LDS-DMA (global_load_lds_dwordx4: 16 bytes per lane straight
-// from global memory into LDS, no staging registers and no ds_write).  In the kernel above a quarter of the matrix-core
-// time is lost around the register -> LDS stores (tools/experiments/gemm_bench.hip -DDCA_GEMM_ABLATE=2: 59.6 -> 66.2 TF
+// from global memory into LDS, no staging registers and no ds_write).  In a register-staged kernel on the same tiles a quarter of the matrix-core
+// time was lost around the register -> LDS stores (59.6 -> 66.2 TF
 // without them, 67.7 with MFMAs and fragment reads alone, which is the f64 MFMA rate at the sustained clock).
 // A DMA instruction writes the 64 lanes' 16-byte pieces to CONTIGUOUS LDS (1 KiB), so a tile row is exactly its 16
 // doubles (128 bytes, no padding) and bank conflicts are avoided by a swizzle instead: the piece that lies in 16-byte
@@ -739,7 +592,6 @@ int gemm_kernels_prepare(int device)
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_f64_dma_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (128 + 64) * 16 * 8));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_f64_small_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, small));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_f64_small_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, small));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_nt_f64_kernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes<64>()));
     done.push_back(device);
     return DCA_OK;
 }
@@ -753,7 +605,7 @@ int gemm_kernels_prepare(int device)
 int launch_gemm_banded(dca_ctx* ctx, hipStream_t stream, GemmArgs g, int maxWGs)
 {
     const int gx = (g.N + 127) / 128, gy = (g.M + 127) / 128;
-    const int band = std::max(1, maxWGs / gx);
+    const int band = chol_band_rows(g.N, maxWGs);
     for (int r = 0; r < gy; r += band) {
         g.row0 = r;
         hipLaunchKernelGGL(gemm_nt_f64_dma_kernel<4>, dim3(gx, std::min(band, gy - r)), dim3(256), (size_t)6 * 128 * 16 * sizeof(double), stream, g);
@@ -762,22 +614,16 @@ int launch_gemm_banded(dca_ctx* ctx, hipStream_t stream, GemmArgs g, int maxWGs)
     return DCA_OK;
 }
 
-// Products of at most kSmall32Max 64 x 64 tiles run on 32 x 32 tiles, up to kDeepMaxTiles on the deep-k 64 x 64 kernel, the rest by
-// LDS-DMA.  Inverse at n = 10 048 / 4000 by the first bound: 0 -> 27.1 / 4.96 ms, 16 -> 25.8 / 4.36, 128 -> 24.7 / 4.08,
-// 400 -> 24.2 / 3.95, 1200 -> 23.9 / 4.01, 1600 -> 24.8 / 3.99; by the second (under two workgroups per CU: latency bound):
-// 0 -> 37.7, 128 -> 37.0, 400 -> 36.4, 1600 -> 36.9 ms.
-constexpr int kSmall32Max = 400, kDeepMaxTiles = 400;
-// The block sweep's chain runs NEXT TO its update launches: there the few-tile products do better as fewer, larger workgroups
-// (n = 10 048: 21.4 -> 20.6 ms with both bounds at 16), so the sweep lowers the two bounds for the launches it makes
-thread_local int tl_small32_max = -1, tl_deep_max_tiles = -1;
+// The bound on the tiles of a 32 x 32 product (cholinv_plan.h): the block sweep lowers it for the launches it makes
+thread_local int tl_small32_max = -1;
 static int small32_max() { return tl_small32_max >= 0 ? tl_small32_max : kSmall32Max; }
 static dim3 grid64(const GemmArgs& g) { return g.walk == WALK_COLUMNS_REVERSED ? dim3(g.M / BM, g.N / BN) : dim3(g.N / BN, g.M / BM); }
 
 // both products on 32 x 32 tiles in ONE launch when each is small enough for that kernel; false: launch them one by one
 bool launch_gemm_small_pair(dca_ctx* ctx, const GemmArgs& a, const GemmArgs& b)
 {
+    if (!chol_pair_fits(a.M, a.N, b.M, b.N, small32_max())) return false;
     const dim3 ga = grid64(a), gb = grid64(b);
-    if ((long long)ga.x * ga.y > small32_max() || (long long)gb.x * gb.y > small32_max()) return false;
     const size_t lds = (size_t)2 * (32 + 32) * (64 + 2) * sizeof(double);
     const dim3 grid(std::max(ga.x, gb.x) * 2, std::max(ga.y, gb.y) * 2, 2);
     hipLaunchKernelGGL(gemm_nt_f64_small_pair_kernel, grid, dim3(256), lds, ctx->stream, a, (int)ga.x * 2, (int)ga.y * 2, b, (int)gb.x * 2, (int)gb.y * 2);
@@ -787,37 +633,24 @@ bool launch_gemm_small_pair(dca_ctx* ctx, const GemmArgs& a, const GemmArgs& b)
 int launch_gemm_on(hipStream_t stream, const GemmArgs& g)
 {
     const dim3 grid = grid64(g);
-    const int deepMaxTiles = tl_deep_max_tiles >= 0 ? tl_deep_max_tiles : kDeepMaxTiles;
-    if ((long long)grid.x * grid.y <= small32_max()) {       // far fewer tiles than CUs: 32 x 32 tiles on four times as many CUs
+    const int gx = (int)(grid.x + 1) / 2, gy = (int)(grid.y + 1) / 2;
+    switch (chol_product_form(g.M, g.N, g.maskA, g.maskB, g.lowerOnly, g.walk, small32_max())) {
+    case CHOL_SMALL32: {
         dim3 g32(grid.x * 2, grid.y * 2);
         const size_t lds = (size_t)2 * (32 + 32) * (64 + 2) * sizeof(double);
         hipLaunchKernelGGL(gemm_nt_f64_small_kernel, g32, dim3(256), lds, stream, g);
-        return DCA_OK;
+        break;
     }
-    if ((long long)grid.x * grid.y <= deepMaxTiles) {
-        hipLaunchKernelGGL(gemm_nt_f64_kernel<64>, grid, dim3(256), gemm_lds_bytes<64>(), stream, g);
-        return DCA_OK;
-    }
-    // 128 x 128 tiles: 16 instead of 8 flop per operand byte (the 64 x 64 kernel sits at the L2 -> LDS fill limit), but a
-    // quarter of the tiles on half of the slots: taken when the rounds of equal tiles still fill up
-    const long long t64 = g.lowerOnly ? (long long)grid.x * (grid.x + 1) / 2 : (long long)grid.x * grid.y;
-    const int gx = (int)(grid.x + 1) / 2, gy = (int)(grid.y + 1) / 2;
-    const long long t128 = g.lowerOnly ? (long long)gx * (gx + 1) / 2 : (long long)gx * gy;
-    auto fill = [](long long t, long long slots) { return (double)t / (double)(((t + slots - 1) / slots) * slots); };
-    // measured inside the inverse at n = 10 048 (kernel trace, 64 vs 128): SYRK 2.84 -> 2.61 ms, L21 / T^T 2.26 -> 2.19,
-    // X21 2.40 -> 2.29, but X^T X (both operands triangular: the 128-tiles waste work along two diagonals) 6.10 -> 7.05
-    const int masks = (g.maskA != MASK_NONE) + (g.maskB != MASK_NONE);
-    bool use128 = false;
-    if (masks == 0) use128 = t128 >= 512 && fill(t128, 512) * 66.0 > fill(t64, 1024) * 59.0;
-    else if (masks == 1) use128 = t128 >= 1024;
-    if (!use128 && g.walk != WALK_COLUMNS_REVERSED && masks == 2 && (long long)grid.x * grid.y >= 2048) {
-        // two triangular operands: 128 x 64 tiles; grid.y counts 128-row tiles
+    case CHOL_DMA128x64:       // grid.y counts 128-row tiles
         hipLaunchKernelGGL((gemm_nt_f64_dma_kernel<4, 2>), dim3(grid.x, gy), dim3(256), (size_t)2 * (128 + 64) * 16 * sizeof(double), stream, g);
-    } else if (use128) {
+        break;
+    case CHOL_DMA128: {
         dim3 grid128(gx, gy);
         if (g.walk == WALK_COLUMNS_REVERSED) grid128 = dim3((g.M + 127) / 128, (g.N + 127) / 128);
         hipLaunchKernelGGL(gemm_nt_f64_dma_kernel<4>, grid128, dim3(256), (size_t)4 * 128 * 16 * sizeof(double), stream, g);
-    } else {
+        break;
+    }
+    default:
         hipLaunchKernelGGL(gemm_nt_f64_dma_kernel<2>, grid, dim3(256), (size_t)4 * 64 * 16 * sizeof(double), stream, g);
     }
     return DCA_OK;
@@ -866,22 +699,13 @@ void side_set_release(SideSet* S)
     S->busy = false;
 }
 
-// Workgroups per launch of the background product and the smallest first half that forks one.  Measured at n = 10 048 (inverse,
-// ms; 24.4 - 24.6 without): at the top level alone 40 / 80 / 120 / 240 workgroups 32.3 / 26.1 / 24.6 / 23.7 (a slow
-// background product is waited for at the join); any background one or two levels down loses -- their subtrees are chains of
-// few-tile products that share CUs with it (0,40,10: 36.0, 0,0,10: 25.5 without stream priorities) -- so only the top
-// level overlaps: n = 8000: 14.7 -> 14.5, n = 6000: 7.6 -> 7.5, n = 4000: unchanged
-constexpr int kSideWGs = 240, kSideMinN1 = 1024;
-
 // The fused recursion of the head of the file.  side: the set whose first stream takes this node's T^T (the top level of a
 // whole matrix only: the nodes below and the sweep's pivot blocks pass none).
 int cholinv_rec(dca_ctx* ctx, double* M, int ld, int n, int pivotBase, Arena& ws, int* dInfo, SideSet* side)
 {
-    if (n == 64) { hipLaunchKernelGGL(cholinv_leaf16_small_kernel<64>, dim3(1), dim3(512), leaf16_lds_bytes<64>(), ctx->stream, M, ld, pivotBase, dInfo); return DCA_OK; }
-    if (n == 128) { hipLaunchKernelGGL(cholinv_leaf16_small_kernel<128>, dim3(1), dim3(512), leaf16_lds_bytes<128>(), ctx->stream, M, ld, pivotBase, dInfo); return DCA_OK; }
-    // halves in multiples of 128 where possible, so that the recursion ends in 128-leaves (a 64-leaf only where n is an
-    // odd multiple of 64)
-    const int n1 = n >= 256 ? (n / 128 / 2) * 128 : (n / 64 / 2) * 64, n2 = n - n1;
+    if (chol_leaf(n) == 64) { hipLaunchKernelGGL(cholinv_leaf16_small_kernel<64>, dim3(1), dim3(512), leaf16_lds_bytes<64>(), ctx->stream, M, ld, pivotBase, dInfo); return DCA_OK; }
+    if (chol_leaf(n) == 128) { hipLaunchKernelGGL(cholinv_leaf16_small_kernel<128>, dim3(1), dim3(512), leaf16_lds_bytes<128>(), ctx->stream, M, ld, pivotBase, dInfo); return DCA_OK; }
+    const int n1 = chol_split(n), n2 = n - n1;
     double* M11 = M;
     double* M12 = M + n1;
     double* M21 = M + (size_t)n1 * ld;
@@ -901,7 +725,7 @@ int cholinv_rec(dca_ctx* ctx, double* M, int ld, int n, int pivotBase, Arena& ws
     // L21 only, so at the top level it runs on a side stream NEXT TO the A22 subtree, whose chain of leaves and few-tile
     // products leaves the chip idle -- as launches of fewer workgroups than CUs (launch_gemm_banded), which is what makes the
     // overlap work: full-grid launches on a side stream (round 1) and CU-masked streams (round 2) had gained nothing.
-    const bool onSide = !paired && side && n1 >= kSideMinN1;
+    const bool onSide = chol_fork_side(paired, side != nullptr, n1);
     // Once the background product is in flight, NO path may leave this frame without joining it: it writes Tt in the
     // arena, and the caller hands the side set back and may reuse or free the workspace as soon as this returns.  On
     // an error below, the side stream is drained on the host before the error is passed on.
@@ -1350,11 +1174,10 @@ void sweep_update_launch(hipStream_t stream, int G, const SweepArgs& g)
 {
     hipLaunchKernelGGL(sweep_update_kernel<2>, dim3(G), dim3(256), (size_t)2 * 2 * 128 * 16 * sizeof(double), stream, g);
 }
-struct SweepCfg { int minN, wide, narrow, wideMinN, cap, prioCap, factorMaxN; };
 static const SweepCfg& sweep_cfg()
 {
     static const SweepCfg c = [] {
-        SweepCfg v{2560, 512, 256, 7000, 0, 64, 4500};      // measured (ms, sweep / three-phase): n = 2048 1.43 / 1.30, 3072 2.16 / 2.31, 4032 3.41 / 3.55, 6016 6.46 / 7.54, 8000 12.25 / 13.25, 10 048 20.6 / 22.4, 12 032 34.0 / 34.9
+        SweepCfg v = sweep_cfg_defaults();
         // the knobs force the sweep and both of its forms onto test-sized matrices
         if (const char* e = getenv("DCA_SWEEP_PRIO_CAP")) v.prioCap = std::max(8, atoi(e) / 8 * 8);
         if (const char* e = getenv("DCA_SWEEP_FACTOR_MAX_N")) v.factorMaxN = atoi(e);       // below: next pivot block from X (F F^T), P on the side stream
@@ -1382,15 +1205,13 @@ int cholinv_sweep(dca_ctx* ctx, double* A, int n, double* work, int* dInfo, Side
 {
     const SweepCfg& cfg = sweep_cfg();
     DCA_TRY(sweep_kernels_prepare(ctx->device));
-    struct Bounds { Bounds(int n) { if (n >= 6000) { tl_small32_max = 16; tl_deep_max_tiles = 16; } } ~Bounds() { tl_small32_max = -1; tl_deep_max_tiles = -1; } } bounds(n);
+    struct Bounds { Bounds(int n) { tl_small32_max = chol_small32_max_in_sweep(n); } ~Bounds() { tl_small32_max = -1; } } bounds(n);
     static const bool traceOn = getenv("DCA_CHOLINV_TRACE") && atoi(getenv("DCA_CHOLINV_TRACE")) != 0;
     StepTrace tr;
     tr.on = traceOn;
     const int ld = n;
-    const int B = n >= cfg.wideMinN ? cfg.wide : cfg.narrow;
-    std::vector<int> b;
-    for (int c = 0; c < n; c += B) b.push_back(c);
-    b.push_back(n);
+    const int B = sweep_panel_width(n, cfg);
+    const std::vector<int> b = sweep_panels(n, B);
     const int np = (int)b.size() - 1;
     const int nt = (n + 127) / 128;
     EventPool* pool = event_pool_of(side);
@@ -1402,7 +1223,7 @@ int cholinv_sweep(dca_ctx* ctx, double* A, int n, double* work, int* dInfo, Side
     const int capAll = kSweepPerCu * 256;
     const int capRest = cfg.cap > 0 ? cfg.cap : capAll * 3 / 4 / 8 * 8;     // the rest launch leaves room for the side stream's and the chain's kernels
     const int capPrio = cfg.prioCap;
-    const bool factorForm = n < cfg.factorMaxN;
+    const bool factorForm = sweep_factor_form(n, cfg);
     // events of step p: 0 P is there (chain), 1 prio tiles done (side), 2 the chain has read the pivot panel in M (chain), 3 W is there
     // (side), 4 rest done (rest)
     constexpr int EV = 5;
@@ -1417,7 +1238,7 @@ int cholinv_sweep(dca_ctx* ctx, double* A, int n, double* work, int* dInfo, Side
     double* Wn = S[1] + BB;
     Arena chainWs{Wn + BB, 2 * BB};
     int* ctr = reinterpret_cast<int*>(Wn + 3 * BB);                 // [np][2][8]
-    if (4 * NB_ + 7 * BB + (size_t)np * 8 + 8 > (size_t)2 * n * n) { dca_set_error("cholinv sweep: workspace too small"); return DCA_ERR_NOMEM; }
+    if (!sweep_workspace_fits(n, B, np)) { dca_set_error("cholinv sweep: workspace too small"); return DCA_ERR_NOMEM; }
     HIP_TRY(hipMemsetAsync(ctr, 0, (size_t)np * 16 * sizeof(int), chain));
     bool sideInFlight = false;
     int rc = DCA_OK;
@@ -1548,10 +1369,8 @@ int dca_spd_inverse_device(dca_ctx* ctx, double* dA, int n, double* dWork, int* 
         // n >= 2560: the block sweep; below it, or where no side set is to be had, the fused recursion.
         // A set of side streams only where one will be used (the sweep; the recursion's top level from n = 2048); everything they
         // run is joined into ctx->stream before either returns, so the set can go back as soon as the launches are enqueued
-        const int sweepB = n >= sweep_cfg().wideMinN ? sweep_cfg().wide : sweep_cfg().narrow;
-        const bool wantSweep = n >= sweep_cfg().minN && n >= 2 * sweepB &&
-                               (size_t)4 * n * sweepB + (size_t)7 * sweepB * sweepB + (size_t)(n / sweepB + 2) * 8 + 8 <= (size_t)2 * n * n;
-        SideSet* side = (n >= 2048 || wantSweep) ? side_set_acquire(ctx->device) : nullptr;
+        const bool wantSweep = sweep_wanted(n, sweep_cfg());
+        SideSet* side = chol_wants_side_set(n, wantSweep) ? side_set_acquire(ctx->device) : nullptr;
         if (wantSweep && side) {
             // -inv(A) in place
             rc = cholinv_sweep(ctx, dA, n, dWork, dInfo, side);
