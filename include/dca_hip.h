@@ -518,6 +518,50 @@ int dca_plm_bm_chains(dca_ctx* ctx, uint8_t* out);
 /* ends the run (x keeps its refined values); DCA_OK without a run */
 int dca_plm_bm_end(dca_ctx* ctx);
 
+/* ------------------------------------------------------------------ sparse bmDCA: a mask on the couplings and their decimation
+ * (Barrat-Charlaix, Muntoni, Weigt 2021).  A run may carry a mask of pairs*q*q bytes in pair order, 1 =
+ * active; a run starts without one (all active), and a mask ends with its run (dca_plm_bm_end, a new dca_plm_bm_begin, and
+ * everything else that ends a run).  With a mask, the update of an iteration writes exactly +0 to a removed coupling element and
+ * updates the active ones as always; fields are never masked; the record stays defined over all pairs*q^2 elements.  A mask of
+ * all ones gives the bits of a run without one.  dca_plm_set_x during a masked run is allowed and leaves x as given: the next
+ * iteration's update zeroes the removed elements again.
+ *
+ * dca_plm_bm_set_mask installs a mask and writes +0 to x at its zeros.  DCA_ERR_ARG: mask NULL or a value above 1; DCA_ERR_STATE
+ * without a run.  dca_plm_bm_get_mask: the mask, all ones if none was installed (DCA_ERR_ARG: out NULL; DCA_ERR_STATE
+ * without a run).
+ *
+ * dca_plm_bm_decimate scores every active element and removes the `remove` lowest.
+ * Frequencies: p = c_ij(a,b) / n of the chains as they are (the integer counts behind dca_plm_bm_freqs(ctx, 1, ..), one division).
+ * Score: D = the symmetrised Kullback-Leibler divergence between the model and the model with this element set to zero,
+ * J (p - p'), p' = p e^-J / (1 - p + p e^-J), computed in double, J the element widened, in this operation order:
+ *   p == 0 or p == 1 or J == 0:  D = +0
+ *   J > 0:  e = expm1(-J),  D = ((J * (-e)) * (p * (1 - p))) / (1 + p * e)
+ *   J < 0:  e = expm1(J),   D = ((J * e) * (p * (1 - p))) / (1 + (1 - p) * e)
+ * and -0 made +0; D >= +0.  A removed element's score is -1.0 and it takes no part in the selection.
+ * Selection: the `remove` active elements smallest under (D's bit pattern as an unsigned 64-bit integer, then the element's offset
+ * in pair order); exact, and the same for every launch geometry.  They get x = +0 and mask = 0 (the mask is created if absent;
+ * remove == 0 touches neither x nor the mask).  scores_out: the scores the selection ran on.  info: active_before, removed,
+ * active_after, threshold = the largest removed D, removed_sum = the sum of the removed D added one by one in ascending key
+ * order (both +0 when nothing was removed).
+ * DCA_ERR_STATE without a run or before the first iteration; DCA_ERR_ARG for remove < 0 or remove > the active elements.
+ * Profiling tag "bm_decimate". */
+typedef struct { long long active_before, removed, active_after; double threshold, removed_sum; } dca_bm_decimation;
+int dca_plm_bm_set_mask(dca_ctx* ctx, const uint8_t* mask /* pairs*q*q, 0/1 */);
+int dca_plm_bm_get_mask(dca_ctx* ctx, uint8_t* out /* pairs*q*q */);
+int dca_plm_bm_decimate(dca_ctx* ctx, long long remove, double* scores_out /* pairs*q*q or NULL */, dca_bm_decimation* info /* or NULL */);
+
+/* Moves the context's x (fields L*q, then the q x q blocks in pair order) to the zero-sum gauge in place: every block's rows and
+ * columns sum to zero, every site's fields sum to zero, and the energy of every sequence changes by one common constant, which
+ * is not kept.  Every operation in double in this order, rounded once to the storage precision:
+ *   per pair i < j:  r(a) = (sum_b J(a,b)) / q,  c(b) = (sum_a J(a,b)) / q,  m = (sum_a r(a)) / q, each sum from 0.0 in ascending
+ *                    index;  J'(a,b) = ((J(a,b) - r(a)) - c(b)) + m;  the block hands r(a) - m to site i and c(b) - m to site j;
+ *   per site i:      t(a) = h_i(a), then for j = 0 .. L-1 (j != i) in ascending order t(a) += the part pair (i,j) hands to i;
+ *                    u = (sum_a t(a)) / q from 0.0 in ascending a;  h'_i(a) = t(a) - u.
+ * State: as dca_plm_set_x (after dca_plm_configure; an L-BFGS or Boltzmann run in progress continues from the new x), on one GPU
+ * only (DCA_ERR_STATE under column strips, vector sharding, a reduce / comm hook or a native-comm mode), and DCA_ERR_STATE
+ * during a Boltzmann run whose mask has removed elements: the transformation would fill them again.  Profiling tag "gauge". */
+int dca_plm_zero_sum_gauge(dca_ctx* ctx);
+
 /* ------------------------------------------------------------------ log Z by annealed importance sampling (AIS; Neal 2001)
  * Estimates Z = sum_s exp(E(s)) of the current x (E exactly as dca_plm_energies defines it, gap state included).
  * h0: base fields, L*q finite host doubles, or NULL: the model's own fields h.  E0(s) = sum_i h0_i(s_i), in double over
@@ -849,7 +893,7 @@ int dca_pca_project(dca_ctx* ctx, const uint8_t* Q, int nq /* Q == NULL: the con
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
  * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "cond_fields", "sample_cond", "ar_logits", "ar_grad", "ar_sample", "ar_epistasis",
- * "bm_stats", "ais", "hamming", "set_compare", "three_site_scan", "three_site_values", "pca_project", "pca_back", "pca_small"). */
+ * "bm_stats", "bm_decimate", "gauge", "ais", "hamming", "set_compare", "three_site_scan", "three_site_values", "pca_project", "pca_back", "pca_small"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it
  * instead of two per stage (an event record costs the stream ~5 us: 14 per plmDCA iteration are 5 % of config C's step, 0.4 % of

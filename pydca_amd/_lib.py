@@ -42,6 +42,12 @@ class BmArgs(C.Structure):
                 ("pseudocount", C.c_double), ("initial", C.c_void_p)]
 
 
+class BmDecimation(C.Structure):
+    """dca_bm_decimation (include/dca_hip.h)"""
+    _fields_ = [("active_before", C.c_longlong), ("removed", C.c_longlong), ("active_after", C.c_longlong),
+                ("threshold", C.c_double), ("removed_sum", C.c_double)]
+
+
 class AisArgs(C.Structure):
     """dca_ais_args (include/dca_hip.h)"""
     _fields_ = [("chains", C.c_int), ("temperatures", C.c_int), ("betas", C.c_void_p), ("sweeps_per_temperature", C.c_int),
@@ -181,6 +187,10 @@ def lib():
         "dca_plm_bm_freqs": (i, [vp, i, vp, vp]),
         "dca_plm_bm_chains": (i, [vp, vp]),
         "dca_plm_bm_end": (i, [vp]),
+        "dca_plm_bm_set_mask": (i, [vp, vp]),
+        "dca_plm_bm_get_mask": (i, [vp, vp]),
+        "dca_plm_bm_decimate": (i, [vp, C.c_longlong, vp, C.POINTER(BmDecimation)]),
+        "dca_plm_zero_sum_gauge": (i, [vp]),
         "dca_hamming_nearest": (i, [vp, vp, i, vp, i, i, vp, vp, vp]),
         "dca_sequence_statistics": (i, [vp, vp, i, vp, vp, C.POINTER(SetComparison)]),
         "dca_alignment_statistics": (i, [vp, vp, vp]),
@@ -238,6 +248,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_ar_fit", "dca_ar_log_probabilities", "dca_ar_sample", "dca_ar_release",
            "dca_ar_epistasis", "dca_ar_epistatic_scores",
            "dca_plm_bm_begin", "dca_plm_bm_iterate", "dca_plm_bm_freqs", "dca_plm_bm_chains", "dca_plm_bm_end",
+           "dca_plm_bm_set_mask", "dca_plm_bm_get_mask", "dca_plm_bm_decimate", "dca_plm_zero_sum_gauge",
            "dca_plm_ais", "dca_mf_ais", "dca_ais_estimate",
            "dca_hamming_nearest", "dca_sequence_statistics", "dca_alignment_statistics",
            "dca_three_site_values", "dca_three_site_scan", "dca_pca_fit", "dca_pca_project",
@@ -1021,6 +1032,35 @@ class Context:
 
     def plm_bm_end(self):
         check(self._l.dca_plm_bm_end(self._h))
+
+    # ---- sparse bmDCA (decimation.hip): the run's mask on the couplings, their decimation, the zero-sum gauge of x
+    def plm_bm_set_mask(self, mask):
+        """mask: pairs*q*q values 0 / 1 (any shape), 1 = active; x becomes +0 at the zeros"""
+        m = np.ascontiguousarray(mask, dtype=np.uint8).ravel()
+        n = self.L * (self.L - 1) // 2 * self.q * self.q
+        if m.size != n:
+            raise ValueError("mask must hold %d values, not %d" % (n, m.size))
+        check(self._l.dca_plm_bm_set_mask(self._h, _ptr(m)))
+
+    def plm_bm_get_mask(self):
+        """-> uint8[pairs, q, q], all ones if the run has no mask"""
+        out = np.zeros((self.L * (self.L - 1) // 2, self.q, self.q), dtype=np.uint8)
+        check(self._l.dca_plm_bm_get_mask(self._h, _ptr(out)))
+        return out
+
+    def plm_bm_decimate(self, remove, return_scores=False):
+        """Removes the `remove` active coupling elements of lowest score -> dict(active_before, removed, active_after,
+        threshold, removed_sum), with return_scores also 'scores': float64[pairs, q, q] (-1 at removed elements)"""
+        info = BmDecimation()
+        sc = np.zeros((self.L * (self.L - 1) // 2, self.q, self.q), dtype=np.float64) if return_scores else None
+        check(self._l.dca_plm_bm_decimate(self._h, int(remove), _ptr(sc) if sc is not None else None, C.byref(info)))
+        out = {k: getattr(info, k) for k, _t in BmDecimation._fields_}
+        if return_scores:
+            out["scores"] = sc
+        return out
+
+    def plm_zero_sum_gauge(self):
+        check(self._l.dca_plm_zero_sum_gauge(self._h))
 
     # ---- a sequence set against the alignment (distance.hip, set_stats.hip): model-free, nothing of the context changes
     def hamming_nearest(self, Q=None, R=None, skip_same_index=False, return_index=True, return_histogram=True):

@@ -786,6 +786,67 @@ BOLTZMANN_OPTIONS = ('iterations', 'num_chains', 'sweeps_per_iteration', 'equili
                      'bm_lambda_J', 'pseudocount', 'seed', 'init', 'num_samples', 'num_sweeps')
 
 
+def add_decimation_arguments(p):
+    """The options of the plmdca decimate_boltzmann sub-command (PlmDCA.decimate_boltzmann; the L2 weights of the learning are
+    --bm_lambda_h / --bm_lambda_J, as under fit_boltzmann)."""
+    p.add_argument('--target_density', type=float, default=0.02, help='fraction of the coupling elements to keep (addition)')
+    p.add_argument('--drop_fraction', type=float, default=0.01, help='fraction of the active elements removed per round (addition)')
+    p.add_argument('--pearson_target', type=float, default=0.95, help='learn until the connected correlations correlate this well (addition)')
+    p.add_argument('--iterations_per_check', type=int, default=10, help='iterations between two looks at the correlation (addition)')
+    p.add_argument('--max_iterations_per_round', type=int, default=500, help='iterations after a decimation at most (addition)')
+    p.add_argument('--warmup_iterations', type=int, default=500, help='iterations before the first decimation at most (addition)')
+    p.add_argument('--gauge', choices=('zero_sum', 'keep'), default='zero_sum', help='move the model to the zero-sum gauge first (addition)')
+    p.add_argument('--num_chains', type=int, default=1000, help='persistent Gibbs chains (addition)')
+    p.add_argument('--sweeps_per_iteration', type=int, default=10, help='Gibbs sweeps of every chain per iteration (addition)')
+    p.add_argument('--equilibration_sweeps', type=int, default=100, help='sweeps before the first iteration (addition)')
+    p.add_argument('--learning_rate', type=float, default=0.05, help='gradient step of fields and couplings (addition)')
+    p.add_argument('--bm_lambda_h', type=float, default=1e-4, help='L2 weight of the fields in the learning (addition)')
+    p.add_argument('--bm_lambda_J', type=float, default=1e-4, help='L2 weight of the couplings in the learning (addition)')
+    p.add_argument('--pseudocount', type=float, help='pseudocount of the data frequencies (default: 1 / Meff) (addition)')
+    p.add_argument('--seed', type=int, default=0, help='seed of the chains\' counter-based generator (addition)')
+    p.add_argument('--init', choices=('plm', 'zero'), default='plm', help='start from the pseudo-likelihood fit or from zero (addition)')
+    p.add_argument('--num_samples', type=int, help='also draw this many sequences from the sparse model (addition)')
+    p.add_argument('--num_sweeps', type=int, default=1000, help='Gibbs sweeps of each of those samples (addition)')
+
+
+DECIMATION_OPTIONS = ('target_density', 'drop_fraction', 'pearson_target', 'iterations_per_check', 'max_iterations_per_round',
+                      'warmup_iterations', 'gauge', 'num_chains', 'sweeps_per_iteration', 'equilibration_sweeps', 'learning_rate',
+                      'bm_lambda_h', 'bm_lambda_J', 'pseudocount', 'seed', 'init', 'num_samples', 'num_sweeps')
+
+
+def run_decimation(instance, prefix, msa_file, output_dir, metadata, biomolecule, opts):
+    """plmdca decimate_boltzmann -> the paths written: <output_dir>/<prefix>_decimation_<alignment base>.txt (the rounds),
+    <prefix>_decimation_params_<alignment base>.npy (the sparse x), <prefix>_decimation_mask_<alignment base>.npy (bool[pairs, q,
+    q]) and, with num_samples, <prefix>_decimation_samples_<alignment base>.fa (the sample_sequences format)."""
+    from .dca_utilities import dca_utilities
+    import numpy as np
+    opts = dict(opts or {})
+    dca_utilities.create_directories(output_dir)
+    kw = dict(pseudocount=opts.get('pseudocount'))
+    for key in DECIMATION_OPTIONS:
+        name = {'bm_lambda_h': 'lambda_h', 'bm_lambda_J': 'lambda_J'}.get(key, key)
+        if key not in ('pseudocount', 'num_samples', 'num_sweeps') and opts.get(key) is not None:
+            kw[name] = opts[key]
+    fit = instance.decimate_boltzmann(**kw)
+
+    def path(middle, postfix):
+        return dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_decimation_' + middle, postfix=postfix)
+    table, params, mask = path('', '.txt'), path('params_', '.npy'), path('mask_', '.npy')
+    dca_utilities.write_decimation_rounds(table, fit['rounds'], fit['density'], metadata=metadata)
+    np.save(params, fit['fields_and_couplings'])
+    np.save(mask, fit['mask'])
+    paths = [table, params, mask]
+    if opts.get('num_samples'):
+        codes = instance.sample_sequences(int(opts['num_samples']), num_sweeps=opts.get('num_sweeps') or 1000,
+                                          seed=opts.get('seed') or 0, return_codes=True)
+        letters = state_letters(biomolecule)
+        seqs = [''.join(letters[c] for c in row) for row in codes]
+        samples = path('samples_', '.fa')
+        dca_utilities.write_sampled_sequences(samples, seqs, instance.compute_sequence_energies(seqs))
+        paths.append(samples)
+    return tuple(paths)
+
+
 def run_boltzmann(instance, prefix, msa_file, output_dir, metadata, biomolecule, opts):
     """plmdca fit_boltzmann -> the paths written: <output_dir>/<prefix>_boltzmann_<alignment base>.txt (learning curve),
     <prefix>_boltzmann_params_<alignment base>.npy (the refined x) and, with num_samples, <prefix>_boltzmann_samples_

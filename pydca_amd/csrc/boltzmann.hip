@@ -4,31 +4,18 @@
 //
 // One iteration: k sweeps of the chains (sample.hip, tag "sample"), then under the tag "bm_stats"
 //   bm_fields_kernel  one workgroup per site: integer counts c_i(a) in LDS, g_i = c_i / n, field update, max |f^_i - g_i|;
-//   bm_pairs_kernel   one workgroup per TB x TB tile of site pairs: each chain's codes of the tile's 2 TB sites are read once
+//   bm_pairs_kernel   (bm_pairs.h) one workgroup per TB x TB tile of site pairs: each chain's codes of the tile's 2 TB sites are read once
 //                     into registers and counted into an LDS histogram of uint32 (ds_add_u32, exact); the same workgroup then
 //                     reads f^_ij and theta, writes theta', and writes its max |f^_ij - g_ij| and its five Pearson sums to a
 //                     slab of its own;
 //   bm_record_kernel  one workgroup: the slabs and the field maxima reduced in a fixed order, the record of the iteration.
 // No float atomics.  Every sum runs in double in an order fixed by (L, q): thread e of a tile walks the tile's elements
 // e, e + 256, ... in ascending order, the 256 partials meet in a fixed tree; the record kernel does the same over the slabs.
-#include "dca_internal.h"
+#include "bm_pairs.h"
 
-#include <cmath>
 #include <memory>
 
 namespace {
-
-// kBmThreads, kBmSums (slab: max |d|, sum Cd, sum Cm, sum Cd^2, sum Cm^2, sum Cd Cm) and bm_tile: potts_plan.h
-
-// theta' = theta + eta * ((f - g) - mu * theta), every step in double, rounded once to S
-template <typename S>
-__device__ __forceinline__ void bm_update(S* p, double d, double eta, double mu)
-{
-    const double th = (double)*p;
-    const double r = mu * th;
-    const double s = d - r;
-    *p = (S)(th + eta * s);
-}
 
 // grid L.  g_i(a) = c_i(a) / n; UPDATE: fields updated, epsPart[i] = max_a |f^_i(a) - g_i(a)|
 template <typename S, bool UPDATE>
@@ -55,70 +42,6 @@ void bm_fields_kernel(const uint8_t* __restrict__ st, int nS, int n, int q, cons
         }
     }
     if (UPDATE) epsPart[i] = m;
-}
-
-// grid (nb, nb), nb = ceil(L / TB); the tiles (I, J) with I <= J hold the pairs i in block I, j in block J, i < j.
-// UPDATE: couplings updated and slab[tile] written (tile = I nb - I (I - 1) / 2 + J - I); otherwise gij = g_ij (pair order).
-template <typename S, int TB, bool UPDATE>
-__global__ __launch_bounds__(kBmThreads)
-void bm_pairs_kernel(const uint8_t* __restrict__ st, int nS, int n, int L, int q, int nb, const double* __restrict__ fi,
-                     const double* __restrict__ fij, const double* __restrict__ gi, S* __restrict__ x, double eta, double mu,
-                     double* __restrict__ slab, double* __restrict__ gij)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char bm_smem[];
-    uint32_t* hist = reinterpret_cast<uint32_t*>(bm_smem);              // [TB * TB][q * q]
-    __shared__ double red[kBmSums][kBmThreads];
-    static_assert(sizeof(red) == kBmStaticLds, "potts_plan.h holds the static LDS of this kernel");
-    const int I = blockIdx.y, J = blockIdx.x;
-    if (J < I) return;
-    const int t = threadIdx.x, qq = q * q, i0 = I * TB, j0 = J * TB;
-    const int cells = TB * TB * qq;
-    for (int e = t; e < cells; e += kBmThreads) hist[e] = 0u;
-    __syncthreads();
-    for (int c = t; c < n; c += kBmThreads) {
-        int a[TB], b[TB];
-#pragma unroll
-        for (int u = 0; u < TB; ++u) {
-            a[u] = i0 + u < L ? st[(size_t)(i0 + u) * nS + c] : 0;
-            b[u] = j0 + u < L ? st[(size_t)(j0 + u) * nS + c] : 0;
-        }
-#pragma unroll
-        for (int ii = 0; ii < TB; ++ii)
-#pragma unroll
-            for (int jj = 0; jj < TB; ++jj)
-                if (i0 + ii < j0 + jj && j0 + jj < L) atomicAdd(&hist[(ii * TB + jj) * qq + a[ii] * q + b[jj]], 1u);
-    }
-    __syncthreads();
-    double mx = 0.0, sd = 0.0, sm = 0.0, sdd = 0.0, smm = 0.0, sdm = 0.0;
-    const size_t Lq = (size_t)L * q;
-    for (int e = t; e < cells; e += kBmThreads) {
-        const int p = e / qq, ab = e - p * qq;
-        const int i = i0 + p / TB, j = j0 + p % TB;
-        if (i >= j || j >= L) continue;
-        const double g = (double)hist[e] / (double)n;
-        const size_t off = pair_index(L, i, j) * qq + ab;
-        if (!UPDATE) { gij[off] = g; continue; }
-        const int a = ab / q, b = ab - a * q;
-        const double f = fij[off];
-        const double d = f - g;
-        bm_update(x + Lq + off, d, eta, mu);
-        mx = fmax(mx, fabs(d));
-        const double cd = f - fi[(size_t)i * q + a] * fi[(size_t)j * q + b];
-        const double cm = g - gi[(size_t)i * q + a] * gi[(size_t)j * q + b];
-        sd += cd; sm += cm; sdd += cd * cd; smm += cm * cm; sdm += cd * cm;
-    }
-    if (!UPDATE) return;
-    red[0][t] = mx; red[1][t] = sd; red[2][t] = sm; red[3][t] = sdd; red[4][t] = smm; red[5][t] = sdm;
-    __syncthreads();
-    for (int s = kBmThreads / 2; s > 0; s >>= 1) {
-        if (t < s) {
-            red[0][t] = fmax(red[0][t], red[0][t + s]);
-#pragma unroll
-            for (int k = 1; k < kBmSums; ++k) red[k][t] += red[k][t + s];
-        }
-        __syncthreads();
-    }
-    if (t < kBmSums) slab[((size_t)I * nb - (size_t)I * (I - 1) / 2 + (J - I)) * kBmSums + t] = red[t][0];
 }
 
 // one workgroup: thread t reduces the slabs t, t + 256, ... (and the field maxima likewise) in ascending order, the 256
@@ -158,43 +81,6 @@ void bm_record_kernel(const double* __restrict__ slab, int tiles, const double* 
     rec[2] = vv > 0.0 ? cov / sqrt(vv) : 0.0;
 }
 
-}  // namespace
-
-struct BmRun {
-    int L = 0, q = 0, dtype = DCA_F32;
-    int k = 1, E = 0;
-    uint64_t seed = 0;
-    double eta_h = 0, eta_J = 0, mu_h = 0, mu_J = 0;
-    long long t = 0;                       // iterations since begin
-    DcaChains ch;
-    DevBuf<double> dFi, dFij, dGi, dEps, dSlab, dRec;
-    int tb = 0, nb = 0, tiles = 0, recCap = 0;
-};
-
-namespace {
-
-template <typename S, int TB, bool UPDATE>
-hipError_t launch_pairs_tb(dca_ctx* ctx, const BmRun* r, const DcaChains& ch, S* x, double* gi, double* gij)
-{
-    auto kern = bm_pairs_kernel<S, TB, UPDATE>;
-    const size_t lds = bm_lds(TB, r->q);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(r->nb, r->nb), dim3(kBmThreads), lds, ctx->stream, ch.dState.get(), ch.nS, ch.n, r->L, r->q, r->nb,
-                       r->dFi.get(), r->dFij.get(), gi, x, r->eta_J, r->mu_J, r->dSlab.get(), gij);
-    return hipGetLastError();
-}
-
-template <typename S, bool UPDATE>
-hipError_t launch_pairs(dca_ctx* ctx, const BmRun* r, const DcaChains& ch, S* x, double* gi, double* gij)
-{
-    switch (r->tb) {
-    case 16: return launch_pairs_tb<S, 16, UPDATE>(ctx, r, ch, x, gi, gij);
-    case 4: return launch_pairs_tb<S, 4, UPDATE>(ctx, r, ch, x, gi, gij);
-    default: return launch_pairs_tb<S, 2, UPDATE>(ctx, r, ch, x, gi, gij);
-    }
-}
-
 // the statistics of the chains ch into gi (and gij); UPDATE: with the update of x and the record written to dRec[slot]
 template <typename S, bool UPDATE>
 hipError_t bm_stats(dca_ctx* ctx, const BmRun* r, const DcaChains& ch, S* x, int slot, double* gi, double* gij)
@@ -203,7 +89,7 @@ hipError_t bm_stats(dca_ctx* ctx, const BmRun* r, const DcaChains& ch, S* x, int
     hipLaunchKernelGGL((bm_fields_kernel<S, UPDATE>), dim3(r->L), dim3(kBmThreads), 0, ctx->stream, ch.dState.get(), ch.nS, ch.n, r->q,
                        r->dFi.get(), gi, x, r->eta_h, r->mu_h, r->dEps.get());
     HIP_PASS(hipGetLastError());
-    HIP_PASS((launch_pairs<S, UPDATE>(ctx, r, ch, x, gi, gij)));
+    HIP_PASS((launch_pairs<S, UPDATE ? kBmUpdate : kBmCount>(ctx, r, ch, x, gi, gij)));
     if (UPDATE) {
         const double M = (double)((size_t)r->L * (r->L - 1) / 2) * (double)(r->q * r->q);
         hipLaunchKernelGGL(bm_record_kernel, dim3(1), dim3(kBmThreads), 0, ctx->stream, r->dSlab.get(), r->tiles, r->dEps.get(), r->L, M,
@@ -258,6 +144,7 @@ int dca_bm_begin_impl(dca_ctx* ctx, void* dx, int dtype, const dca_bm_args* a)
     r->tb = bm_tile(q);
     r->nb = ceil_div(L, r->tb);
     r->tiles = r->nb * (r->nb + 1) / 2;
+    r->active = (long long)L * (L - 1) / 2 * q * q;
     const size_t Lq = (size_t)L * q, pairs = (size_t)L * (L - 1) / 2;
     if (r->dFi.alloc(Lq, false) != hipSuccess || r->dFij.alloc(pairs * q * q, false) != hipSuccess || r->dGi.alloc(Lq) != hipSuccess ||
         r->dEps.alloc((size_t)L) != hipSuccess || r->dSlab.alloc((size_t)r->tiles * kBmSums) != hipSuccess) {

@@ -614,6 +614,36 @@ int dca_plm_bm_iterate(dca_ctx* ctx, int iterations, dca_bm_record* records_out)
 int dca_plm_bm_freqs(dca_ctx* ctx, int which, double* fi_out, double* fij_out) { CHECK_CTX(ctx); return dca_bm_freqs_impl(ctx, which, fi_out, fij_out); }
 int dca_plm_bm_chains(dca_ctx* ctx, uint8_t* out) { CHECK_CTX(ctx); return dca_bm_chains_impl(ctx, out); }
 int dca_plm_bm_end(dca_ctx* ctx) { CHECK_CTX(ctx); dca_bm_free(ctx); return DCA_OK; }
+// the mask, the decimation and the gauge (decimation.hip)
+int dca_plm_bm_set_mask(dca_ctx* ctx, const uint8_t* mask)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->bm || !ctx->plm) { dca_set_error("dca_plm_bm_begin first"); return DCA_ERR_STATE; }
+    void* dx = nullptr;
+    DCA_TRY(ctx->plm->bm_source(&dx));
+    return dca_bm_set_mask_impl(ctx, dx, mask);
+}
+int dca_plm_bm_get_mask(dca_ctx* ctx, uint8_t* out) { CHECK_CTX(ctx); return dca_bm_get_mask_impl(ctx, out); }
+int dca_plm_bm_decimate(dca_ctx* ctx, long long remove, double* scores_out, dca_bm_decimation* info)
+{
+    CHECK_CTX(ctx);
+    if (!ctx->bm || !ctx->plm) { dca_set_error("dca_plm_bm_begin first"); return DCA_ERR_STATE; }
+    void* dx = nullptr;
+    DCA_TRY(ctx->plm->bm_source(&dx));
+    return dca_bm_decimate_impl(ctx, dx, remove, scores_out, info);
+}
+int dca_plm_zero_sum_gauge(dca_ctx* ctx)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    if (dca_bm_has_removed(ctx)) {
+        dca_set_error("dca_plm_zero_sum_gauge: the Boltzmann run's mask has removed elements, which the transformation would fill again");
+        return DCA_ERR_STATE;
+    }
+    void* dx = nullptr;
+    DCA_TRY(ctx->plm->transform_source(&dx));
+    return dca_zero_sum_gauge_impl(ctx, dx, ctx->precision == DCA_F64 ? DCA_F64 : DCA_F32);
+}
 
 // ------------------------------------------------------------------ sequence sets against the alignment (distance.hip, set_stats.hip)
 int dca_hamming_nearest(dca_ctx* ctx, const uint8_t* Q, int nq, const uint8_t* R, int nr, int skip_same_index,

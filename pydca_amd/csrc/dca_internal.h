@@ -211,6 +211,9 @@ struct PlmEngineBase {
     // the device x a Boltzmann-learning run updates in place; DCA_ERR_STATE (with the reason) unconfigured, during an L-BFGS
     // run, under column strips, vector sharding, a reduce / comm hook or a native-comm mode
     virtual int bm_source(void** dx) = 0;
+    // the device x for a transformation in place (dca_plm_zero_sum_gauge): dca_plm_set_x's rules (configured; an L-BFGS run in
+    // progress continues from the new x), on one GPU only as bm_source
+    virtual int transform_source(void** dx) = 0;
     virtual int set_vector_sharding(int rank, int world, dca_comm_hook hook, void* user) = 0;
     dca_reduce_hook hook = nullptr;
     void* hook_user = nullptr;
@@ -325,6 +328,14 @@ int dca_bm_iterate_impl(dca_ctx* ctx, void* dx, int iterations, dca_bm_record* r
 int dca_bm_freqs_impl(dca_ctx* ctx, int which, double* fi_out, double* fij_out);
 int dca_bm_chains_impl(dca_ctx* ctx, uint8_t* out);
 void dca_bm_free(dca_ctx* ctx);
+
+// ---- decimation.hip : the mask of a Boltzmann-learning run, the decimation of its couplings (dca_plm_bm_set_mask / get_mask /
+// decimate; the run's checks here) and the zero-sum gauge of the plm vector dx (dca_plm_zero_sum_gauge)
+int dca_bm_set_mask_impl(dca_ctx* ctx, void* dx, const uint8_t* mask);
+int dca_bm_get_mask_impl(dca_ctx* ctx, uint8_t* out);
+int dca_bm_decimate_impl(dca_ctx* ctx, void* dx, long long remove, double* scores_out, dca_bm_decimation* info);
+bool dca_bm_has_removed(const dca_ctx* ctx);       // a run whose mask has removed elements
+int dca_zero_sum_gauge_impl(dca_ctx* ctx, void* dx, int dtype);
 
 // the chains' unweighted frequencies by the UPDATE = false instantiations of the statistics kernels (exact integer LDS
 // histograms): dGi (L*q) and dGij (pairs*q*q, pair order), device.  Under the tag "bm_stats"; no run is needed or touched.

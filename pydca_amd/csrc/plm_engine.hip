@@ -588,6 +588,17 @@ struct PlmEngine : PlmEngineBase {
         *x = dx;
         return DCA_OK;
     }
+    int transform_source(void** x) override
+    {
+        if (!configured) { dca_set_error("dca_plm_configure first"); return DCA_ERR_STATE; }
+        if (strips || native_mode == 4 || comm || hook || native_mode != 0) {
+            dca_set_error("the gauge transformation runs on one GPU: column strips, vector sharding, a reduce / comm hook or a native-comm mode is set");
+            return DCA_ERR_STATE;
+        }
+        o.trial_ready = false;
+        *x = dx;
+        return DCA_OK;
+    }
     // the current x for energy.hip, pll.hip, sample.hip, sample_conditional.hip, ascent.hip and ais.hip; an L-BFGS run in progress is
     // allowed.  Column strips gather x first, as scores() does; one_gpu_only (AIS, conditional sampling, ascent) refuses them instead
     int potts_source(PottsSource* out, bool one_gpu_only) override

@@ -1,7 +1,7 @@
 // Launch geometry of the kernels that read the fitted Potts model as a sequence model: the pair tiles of the energies
 // (energy.hip), the chunking of the site conditionals (site_conditionals.h: pll.hip, ardca.hip), the chunking of the Gibbs sweep
-// (sample.hip, ais.hip; sample_conditional.hip at its F free sites) and the pair tiles of the bmDCA statistics (boltzmann.hip),
-// each from (L, q, element size) alone.
+// (sample.hip, ais.hip; sample_conditional.hip at its F free sites), the pair tiles of the bmDCA statistics (boltzmann.hip,
+// bm_pairs.h) and the chunks of the decimation's selection (decimation.hip), each from (L, q, element size) alone.
 // Host code only, no HIP header: a host compiler builds it, and tests/potts_plan_driver.cpp prints it for
 // tests/test_potts_audit_host.py, which holds the audit's case table to these numbers.  Included from dca_internal.h.
 #pragma once
@@ -137,3 +137,13 @@ inline int bm_tile(int q) { return q <= 8 ? 16 : q <= 24 ? 4 : 2; }
 // dynamic LDS of the pair kernel (the histogram) and its static LDS (the reduction buffer)
 inline size_t bm_lds(int TB, int q) { return (size_t)TB * TB * q * q * sizeof(unsigned); }
 constexpr size_t kBmStaticLds = (size_t)kBmSums * kBmThreads * sizeof(double);
+
+// ---- decimation.hip: dec_hist_kernel, dec_count_kernel / dec_apply_kernel, gauge_pairs_kernel
+constexpr int kDecThreads = 256;
+constexpr int kDecChunk = 16 * kDecThreads;        // consecutive elements per workgroup of the count and apply passes
+constexpr int kDecHistBlocks = 2048;               // grid of a histogram pass at most (grid-stride; 8 workgroups per CU)
+constexpr int kGaugeThreads = 256;
+constexpr int kGaugeMaxQ = 32;                     // states per site the gauge kernels hold in static LDS (dca_set_msa's limit)
+
+inline size_t dec_chunks(size_t n) { return (n + kDecChunk - 1) / kDecChunk; }
+inline int dec_hist_blocks(size_t n) { return (int)std::max<size_t>(1, std::min<size_t>((n + kDecThreads - 1) / kDecThreads, kDecHistBlocks)); }

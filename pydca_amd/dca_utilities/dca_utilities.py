@@ -209,6 +209,19 @@ def write_boltzmann_history(file_name, history, metadata=None):
     _stream(file_name, header, rows, 'Boltzmann learning curve')
 
 
+def write_decimation_rounds(file_name, rounds, density, metadata=None):
+    """Rounds of PlmDCA.decimate_boltzmann: one row per decimation with the iteration index it came after, the active coupling
+    elements before it, the number removed, the density after it, the largest removed score and the Pearson correlation before
+    it; the reals written with %.17g (no reference counterpart)."""
+    header = [_RULE] + list(metadata or []) + [
+        '#\tFinal density of the couplings: {}'.format('%.17g' % float(density)),
+        '# Columns: iterations run before the decimation, active coupling elements before it, elements removed, density after it,',
+        '# threshold = the largest removed symmetrised Kullback-Leibler score, Pearson correlation of the connected correlations',
+        '# of the data and of the model chains before it', _RULE]
+    rows = ('{} {} {} {} {} {}'.format(int(r[0]), int(r[1]), int(r[2]), *('%.17g' % float(v) for v in r[3:])) for r in rounds)
+    _stream(file_name, header, rows, 'decimation rounds')
+
+
 def write_log_likelihood(file_name, result, log_likelihood, log_probabilities, options, metadata=None):
     """log Z by annealed importance sampling and the log-likelihood of the training alignment (compute_log_likelihood
     sub-command): a header with log Z, its stderr, the ESS, log Z0 and the schedule, the line 'average_log_likelihood <value>',

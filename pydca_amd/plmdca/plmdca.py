@@ -52,6 +52,39 @@ def _boltzmann_options(iterations, num_chains, sweeps_per_iteration, equilibrati
     return opts
 
 
+def _decimation_options(target_density, drop_fraction, pearson_target, iterations_per_check, max_iterations_per_round,
+                        warmup_iterations, gauge, num_chains, sweeps_per_iteration, equilibration_sweeps, learning_rate, lambda_h,
+                        lambda_J, pseudocount, init):
+    """Checks the arguments of PlmDCA.decimate_boltzmann (host only) -> dict of the checked values."""
+    opts = _boltzmann_options(1, num_chains, sweeps_per_iteration, equilibration_sweeps, learning_rate, lambda_h, lambda_J,
+                              pseudocount, init)
+    del opts['iterations']
+
+    def real(name, v, ok, what):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise PlmDCAException('{} must be a number, not {!r}'.format(name, v))
+        if isinstance(v, bool) or not ok(v):
+            raise PlmDCAException('{} must lie in {}, not {!r}'.format(name, what, v))
+        return v
+
+    def count(name, v, low):
+        if isinstance(v, bool) or int(v) != v or int(v) < low:
+            raise PlmDCAException('{} must be an integer >= {}, not {!r}'.format(name, low, v))
+        return int(v)
+    opts.update(target_density=real('target_density', target_density, lambda v: 0.0 <= v <= 1.0, '[0, 1]'),
+                drop_fraction=real('drop_fraction', drop_fraction, lambda v: 0.0 < v <= 1.0, '(0, 1]'),
+                pearson_target=real('pearson_target', pearson_target, lambda v: -1.0 <= v <= 1.0, '[-1, 1]'),
+                iterations_per_check=count('iterations_per_check', iterations_per_check, 1),
+                max_iterations_per_round=count('max_iterations_per_round', max_iterations_per_round, 1),
+                warmup_iterations=count('warmup_iterations', warmup_iterations, 1))
+    if gauge not in ('zero_sum', 'keep'):
+        raise PlmDCAException("gauge must be 'zero_sum' or 'keep', not {!r}".format(gauge))
+    opts['gauge'] = gauge
+    return opts
+
+
 class PlmDCA(_potts.PottsModel, _compare.SequenceComparison):
     """plmdca.py:25-104.  Extra keyword arguments (not in the reference): device,
     precision (32: float storage as the reference; 64: float64 checking mode) and
@@ -406,6 +439,76 @@ class PlmDCA(_potts.PottsModel, _compare.SequenceComparison):
         if history.shape[0]:
             logger.info('\n\tLast iteration: eps_h {:.3g}, eps_J {:.3g}, pearson {:.4f}'.format(*history[-1]))
         return {'history': history, 'fields_and_couplings': ctx.plm_get_x(dt)}
+
+    def decimate_boltzmann(self, target_density=0.02, drop_fraction=0.01, pearson_target=0.95, iterations_per_check=10,
+                           max_iterations_per_round=500, warmup_iterations=500, gauge='zero_sum', num_chains=1000,
+                           sweeps_per_iteration=10, equilibration_sweeps=100, learning_rate=0.05, lambda_h=1e-4, lambda_J=1e-4,
+                           pseudocount=None, seed=0, init='plm'):
+        """Sparse Boltzmann machine learning (Barrat-Charlaix, Muntoni, Weigt 2021): learns as
+        fit_boltzmann does until the model's connected correlations reach pearson_target against the data's (checked every
+        iterations_per_check iterations, at most warmup_iterations the first time and max_iterations_per_round later), then
+        removes the fraction drop_fraction of the still-active coupling elements whose removal changes the model least
+        (symmetrised Kullback-Leibler divergence), learns again, and repeats down to round(target_density * pairs * q^2) active
+        elements; one more convergence round ends it.  gauge='zero_sum' moves the starting model to the zero-sum gauge
+        first, in which a zero coupling means no interaction; 'keep' leaves it as it is.  The other arguments are
+        fit_boltzmann's.  The instance holds the sparse model afterwards.
+        -> {'history': float64[iterations, 3], 'rounds': float64[decimations, 6] of (iteration index, active before, removed,
+        density after, threshold, pearson before), 'mask': bool[pairs, q, q], 'density', 'fields_and_couplings': x}"""
+        if self.__devices and len(self.__devices) > 1:
+            logger.error('\n\tBoltzmann learning runs on one GPU; devices={}'.format(self.__devices))
+            raise PlmDCAException('decimate_boltzmann runs on one GPU, not on devices {}'.format(self.__devices))
+        opts = _decimation_options(target_density, drop_fraction, pearson_target, iterations_per_check, max_iterations_per_round,
+                                   warmup_iterations, gauge, num_chains, sweeps_per_iteration, equilibration_sweeps, learning_rate,
+                                   lambda_h, lambda_J, pseudocount, init)
+        if opts['init'] == 'plm':
+            ctx = self._fitted_context()
+        else:
+            ctx = self.__ctx if self.__ctx is not None else self._unfitted_context()
+        self.__ctx = ctx
+        ctx.plm_lbfgs_end()
+        dt = np.float64 if self.__precision == _lib.DCA_F64 else np.float32
+        if opts['init'] == 'zero':
+            ctx.plm_set_x(np.zeros(ctx.num_params(), dtype=dt))
+        if opts['gauge'] == 'zero_sum':
+            ctx.plm_zero_sum_gauge()
+        lam = 1.0 / ctx.meff() if opts['pseudocount'] is None else opts['pseudocount']
+        L, q = self.__seqs_len, self.__num_site_states
+        total = L * (L - 1) // 2 * q * q
+        target = max(int(round(opts['target_density'] * total)), 0)
+        ctx.plm_bm_begin(opts['num_chains'], opts['sweeps_per_iteration'], opts['equilibration_sweeps'], seed=int(seed),
+                         eta_h=opts['learning_rate'], eta_J=opts['learning_rate'], mu_h=opts['lambda_h'], mu_J=opts['lambda_J'],
+                         pseudocount=lam)
+        history, rounds = [], []
+        done = [0]
+
+        def converge(cap):
+            ran = 0
+            while ran < cap:
+                block = ctx.plm_bm_iterate(min(opts['iterations_per_check'], cap - ran))
+                history.append(block)
+                ran += block.shape[0]
+                done[0] += block.shape[0]
+                if block[-1, 2] >= opts['pearson_target']:
+                    break
+            return float(history[-1][-1, 2])
+        try:
+            pearson = converge(opts['warmup_iterations'])
+            active = total
+            while active > target:
+                remove = min(int(np.ceil(opts['drop_fraction'] * active)), active - target)
+                info = ctx.plm_bm_decimate(remove)
+                active = info['active_after']
+                rounds.append((done[0], info['active_before'], info['removed'], active / float(total), info['threshold'], pearson))
+                pearson = converge(opts['max_iterations_per_round'])
+                logger.info('\n\tDecimation {}: {} active elements (density {:.4g}) after {} iterations, pearson {:.4f}'.format(
+                    len(rounds), active, active / float(total), done[0], pearson))
+            if rounds:
+                logger.info('\n\t{} decimations to density {:.4g}, pearson {:.4f}'.format(len(rounds), active / float(total), pearson))
+            mask = ctx.plm_bm_get_mask().astype(bool)
+        finally:
+            ctx.plm_bm_end()
+        return {'history': np.concatenate(history), 'rounds': np.array(rounds, dtype=np.float64).reshape(-1, 6), 'mask': mask,
+                'density': active / float(total) if total else 0.0, 'fields_and_couplings': ctx.plm_get_x(dt)}
 
     def compute_seqs_weight(self):
         """plmdca.py:565-591: weights of the PYTHON reader's alignment (float64 comparison,

@@ -13,6 +13,7 @@ from .sequence_backmapper.sequence_backmapper import SequenceBackmapper
 logger = logging.getLogger(__name__)
 DCA_COMPUTATION_SUBCOMMANDS = ('compute_fn', 'compute_di', 'compute_params')
 BOLTZMANN_SUBCOMMAND = 'fit_boltzmann'
+DECIMATION_SUBCOMMAND = 'decimate_boltzmann'
 
 
 def configure_logging():
@@ -23,7 +24,8 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
                               lambda_J=None, max_iterations=None, apc=False, verbose=False, output_dir=None,
                               num_threads=None, ranked_by=None, linear_dist=None, num_site_pairs=None, device=0,
                               exact_gradient=False, precision=32, devices=None, query_file=None, wildtype_file=None, sampling=None,
-                              boltzmann=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None, conditional=None, ascent=None, tempered=None):
+                              boltzmann=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None, conditional=None, ascent=None, tempered=None,
+                              decimation=None):
     if verbose:
         configure_logging()
     plmdca_instance = plmdca.PlmDCA(msa_file, biomolecule, seqid=seqid, lambda_h=lambda_h, lambda_J=lambda_J,
@@ -44,6 +46,12 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
         return _potts.run_boltzmann(plmdca_instance, 'PLMDCA', msa_file, output_dir, dca_utilities.plmdca_param_metadata(plmdca_instance),
                                     _lib.DCA_BIOMOLECULE_PROTEIN if plmdca_instance.biomolecule == 'PROTEIN' else _lib.DCA_BIOMOLECULE_RNA,
                                     boltzmann)
+    if the_command == DECIMATION_SUBCOMMAND:
+        if not output_dir:
+            output_dir = 'PLMDCA_output_' + os.path.splitext(os.path.basename(msa_file))[0]
+        return _potts.run_decimation(plmdca_instance, 'PLMDCA', msa_file, output_dir, dca_utilities.plmdca_param_metadata(plmdca_instance),
+                                     _lib.DCA_BIOMOLECULE_PROTEIN if plmdca_instance.biomolecule == 'PROTEIN' else _lib.DCA_BIOMOLECULE_RNA,
+                                     decimation)
     if the_command in DCA_COMPUTATION_SUBCOMMANDS:
         param_metadata = dca_utilities.plmdca_param_metadata(plmdca_instance)
         if not output_dir:
@@ -99,7 +107,7 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
 def run_plm_dca(argv=None):
     parser = ArgumentParser(prog='plmdca')
     subparsers = parser.add_subparsers(dest='subcommand_name')
-    for name in DCA_COMPUTATION_SUBCOMMANDS + _potts.POTTS_SUBCOMMANDS + (BOLTZMANN_SUBCOMMAND,):
+    for name in DCA_COMPUTATION_SUBCOMMANDS + _potts.POTTS_SUBCOMMANDS + (BOLTZMANN_SUBCOMMAND, DECIMATION_SUBCOMMAND):
         p = subparsers.add_parser(name)
         p.add_argument('biomolecule', help='protein or rna (case insensitive)')
         p.add_argument('msa_file', help='FASTA formatted multiple sequence alignment, one sequence per line')
@@ -139,6 +147,8 @@ def run_plm_dca(argv=None):
             _potts.add_ais_arguments(p)
         if name == BOLTZMANN_SUBCOMMAND:
             _potts.add_boltzmann_arguments(p)
+        if name == DECIMATION_SUBCOMMAND:
+            _potts.add_decimation_arguments(p)
         p.add_argument('--output_dir')
         p.add_argument('--device', type=int, default=0, help='GPU index (addition)')
         p.add_argument('--devices', help='comma-separated GPU indices, e.g. 0,1,2,3,4,5,6,7: one rank per GPU, sequences (or sites) '
@@ -168,7 +178,8 @@ def run_plm_dca(argv=None):
         pca={k: args.get(k) for k in ('pca', 'num_components', 'seed')},
         conditional={k: args.get(k) for k in _potts.CONDITIONAL_OPTIONS},
         ascent={k: args.get(k) for k in _potts.ASCENT_OPTIONS},
-        tempered={k: args.get(k) for k in _potts.TEMPERED_OPTIONS})
+        tempered={k: args.get(k) for k in _potts.TEMPERED_OPTIONS},
+        decimation={k: args.get(k) for k in _potts.DECIMATION_OPTIONS})
 
 
 if __name__ == '__main__':
