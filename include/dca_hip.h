@@ -674,6 +674,44 @@ int dca_mf_sample_tempered(dca_ctx* ctx, const dca_pt_args* args, uint8_t* out /
                            double* energies_out /* M*R or NULL: E of the final codes */, uint64_t* attempts_out,
                            uint64_t* accepts_out /* R-1 each, or NULL */, double* energy_trace_out /* rounds x M x R, or NULL */,
                            int* rounds_out /* or NULL */);
+/* Inter-protein interaction energies of a model fitted on a concatenated alignment: sites [0, split)
+ * are protein A (LA = split), sites [split, L) protein B (LB = L - LA).  XA: nA x LA codes, XB: nB x LB codes.  Group g (a
+ * species) holds the rows offsets_a[g] .. offsets_a[g+1] of XA and offsets_b[g] .. offsets_b[g+1] of XB; the offsets (G + 1
+ * each) are non-decreasing, start at 0 and end at nA and nB; a group may be empty on either side.  out: the concatenation of
+ * the G row-major blocks nA_g x nB_g (sum_g nA_g * nB_g doubles); all-against-all is G = 1.
+ * The rule, every term widened to double and no contraction.  For i < LA <= j, Jt_ij(a, b) is
+ *   gauge 0: the stored J_ij(a, b) as dca_plm_energies reads it (the mean-field model is zero on the gap state);
+ *   gauge 1: its zero-sum form over all q states, kept in double and never rounded back to the storage type:
+ *            r(a) = (sum_b J(a, b)) / q, c(b) = (sum_a J(a, b)) / q, m = (sum_a r(a)) / q, every sum from 0.0 in ascending
+ *            index, Jt = ((J - r(a)) - c(b)) + m.
+ *   phi_m(j, b) = sum over i = 0 .. LA-1, ascending, of Jt_{i, LA+j}(a^m_i, b): one sequential double sum from 0.0;
+ *   E(m, n)     = sum over j = 0 .. LB-1, ascending, of phi_m(j, b^n_j):        one sequential double sum from 0.0.
+ * No fields enter.  Higher E is the more favourable pair (the sign of dca_plm_energies).  E(m, n) depends only on the model,
+ * the split, the gauge and the two rows: the same bits in any grouping, batch, block split or call.
+ * phi (LB x q doubles per A-row) and the device output are bounded at 1 GiB each by running blocks of A-rows one after
+ * another (DCA_CROSS_PASS caps the rows of a block).
+ * DCA_ERR_ARG: split outside [1, L-1], negative counts, G < 1, offsets NULL or malformed, gauge not 0 or 1, XA, XB or out NULL
+ * with energies to form, a code >= q; no energies to form is DCA_OK.  DCA_ERR_STATE: before dca_plm_configure; under column
+ * strips, vector sharding, a reduce / comm hook or a native-comm mode (one GPU only, like dca_plm_sample_conditional).  An
+ * L-BFGS or Boltzmann-learning run in progress is allowed; the alignment, the weights, x, g, the optimiser and the bmDCA chains
+ * are not touched.  Profiling tags: "cross_fields" (phi, one launch per block), "cross_energy" (the pairs, one launch per
+ * block).  No reference counterpart. */
+int dca_plm_interaction_energies(dca_ctx* ctx, int split /* LA */, const uint8_t* XA /* nA x LA */, int nA,
+                                 const uint8_t* XB /* nB x LB */, int nB, const int32_t* offsets_a /* G+1 */,
+                                 const int32_t* offsets_b /* G+1 */, int G, int gauge /* 0: as stored, 1: zero-sum */,
+                                 double* out /* sum_g nA_g * nB_g */);
+/* The same under the mean-field model (J as in dca_mf_energies; zero on the gap state).  DCA_ERR_STATE before
+ * dca_mf_couplings. */
+int dca_mf_interaction_energies(dca_ctx* ctx, int split, const uint8_t* XA, int nA, const uint8_t* XB, int nB,
+                                const int32_t* offsets_a, const int32_t* offsets_b, int G, int gauge, double* out);
+/* Maximum-weight matching of size min(nr, nc) in the nr x nc matrix E (row-major; rectangular allowed) by shortest augmenting
+ * paths, on the host (no device, no context, no threads, deterministic).  col_of_row[r]: the column of row r, -1 if unassigned.
+ * total_out (or NULL): the matching's total.  gap_out (or NULL; nr): for an assigned row, total - (the best total of a matching
+ * of the same size that may not use (r, col_of_row[r])), >= 0, +inf where no such matching exists (a 1 x 1 block); 0 for an
+ * unassigned row.  The gaps take one augmentation each from the optimal potentials.  Under exact ties any optimal matching may
+ * come back (the total and the gaps are the same for all of them).  DCA_ERR_ARG: a negative size, a non-finite entry, E or
+ * col_of_row NULL where needed; nr == 0 or nc == 0 is DCA_OK with total 0. */
+int dca_assign_partners(const double* E, int nr, int nc, int32_t* col_of_row /* nr */, double* total_out, double* gap_out);
 /* The counter-based generator of the samplers, on the host: Philox4x32-10 (Salmon et al., SC 2011; 10 rounds, multipliers
  * 0xD2511F53 / 0xCD9E8D57, key bumps 0x9E3779B9 / 0xBB67AE85).  Needs no device. */
 int dca_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);

@@ -169,6 +169,9 @@ def lib():
         "dca_plm_ascend": (i, [vp, vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp]),
         "dca_mf_ascend": (i, [vp, vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp]),
         "dca_philox4x32_10": (i, [vp, vp, vp]),
+        "dca_plm_interaction_energies": (i, [vp, i, vp, i, vp, i, vp, vp, i, i, vp]),
+        "dca_mf_interaction_energies": (i, [vp, i, vp, i, vp, i, vp, vp, i, i, vp]),
+        "dca_assign_partners": (i, [vp, i, i, vp, vp, vp]),
         "dca_ar_configure": (i, [vp, d, d]),
         "dca_ar_num_params": (sz, [i, i]),
         "dca_ar_init_x": (i, [vp]),
@@ -244,6 +247,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_plm_pseudo_likelihood", "dca_mf_pseudo_likelihood",
            "dca_plm_sample", "dca_mf_sample", "dca_plm_sample_conditional", "dca_mf_sample_conditional",
            "dca_plm_sample_tempered", "dca_mf_sample_tempered", "dca_plm_ascend", "dca_mf_ascend", "dca_philox4x32_10",
+           "dca_plm_interaction_energies", "dca_mf_interaction_energies", "dca_assign_partners",
            "dca_ar_configure", "dca_ar_num_params", "dca_ar_init_x", "dca_ar_set_x", "dca_ar_get_x", "dca_ar_gradient", "dca_ar_get_g",
            "dca_ar_fit", "dca_ar_log_probabilities", "dca_ar_sample", "dca_ar_release",
            "dca_ar_epistasis", "dca_ar_epistatic_scores",
@@ -487,6 +491,25 @@ def philox4x32_10(ctr, key):
     out = np.zeros(4, dtype=np.uint32)
     check(lib().dca_philox4x32_10(_ptr(c), _ptr(k), _ptr(out)))
     return out
+
+
+GAUGES = {"as_stored": 0, "zero_sum": 1}
+
+
+def assign_partners(E):
+    """Maximum-weight matching of size min(nr, nc) in the 2-D array E with gaps (dca_assign_partners; host only) ->
+    (col_of_row int32[nr], -1 = unassigned; total; gaps float64[nr]: +inf where the pair cannot be replaced, 0 for an
+    unassigned row).  Under exact ties any optimal matching may come back."""
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    if E.ndim != 2:
+        raise ValueError("E must be a 2-D array")
+    nr, nc = E.shape
+    col = np.full(nr, -1, dtype=np.int32)
+    gap = np.zeros(nr, dtype=np.float64)
+    total = C.c_double(0.0)
+    check(lib().dca_assign_partners(_ptr(E) if E.size else None, nr, nc, _ptr(col) if nr else None, C.byref(total),
+                                    _ptr(gap) if nr else None))
+    return col, total.value, gap
 
 
 class Context:
@@ -843,6 +866,41 @@ class Context:
     def mf_sample_conditional(self, initial, free_sites, sweeps, seed=0, beta=1.0, random_start=True, first_chain=0, first_sweep=0):
         return self._sample_conditional(self._l.dca_mf_sample_conditional, initial, free_sites, sweeps, seed, beta, random_start,
                                         first_chain, first_sweep)
+
+    # ---- inter-protein energies (interaction.hip): sites [0, split) are protein A, the rest protein B; XA uint8[nA, split],
+    # XB uint8[nB, L - split]; group g holds the rows offsets_a[g] .. offsets_a[g+1] of XA and offsets_b[g] .. offsets_b[g+1] of XB
+    # -> a list of float64[nA_g, nB_g] blocks; with no offsets one dense float64[nA, nB]
+    def _interaction_energies(self, fn, XA, XB, split, offsets_a, offsets_b, gauge):
+        if gauge not in GAUGES:
+            raise ValueError("gauge must be one of %s" % sorted(GAUGES))
+        split = int(split)
+        XA = np.ascontiguousarray(XA, dtype=np.uint8)
+        XB = np.ascontiguousarray(XB, dtype=np.uint8)
+        if XA.ndim != 2 or XB.ndim != 2 or (0 < split < self.L and (XA.shape[1] != split or XB.shape[1] != self.L - split)):
+            raise ValueError("XA must be uint8[nA, %d] and XB uint8[nB, %d]" % (split, self.L - split))
+        if (offsets_a is None) != (offsets_b is None):
+            raise ValueError("give both offsets or neither")
+        dense = offsets_a is None
+        oa = np.array([0, XA.shape[0]], dtype=np.int32) if dense else np.ascontiguousarray(offsets_a, dtype=np.int32).reshape(-1)
+        ob = np.array([0, XB.shape[0]], dtype=np.int32) if dense else np.ascontiguousarray(offsets_b, dtype=np.int32).reshape(-1)
+        if oa.size != ob.size:
+            raise ValueError("offsets_a and offsets_b must have the same length")
+        G = oa.size - 1
+        na, nb = np.diff(oa).astype(np.int64), np.diff(ob).astype(np.int64)
+        sizes = na * nb if G >= 1 and (na >= 0).all() and (nb >= 0).all() else np.zeros(max(G, 0), dtype=np.int64)
+        out = np.zeros(int(sizes.sum()), dtype=np.float64)
+        check(fn(self._h, split, _ptr(XA) if XA.size else None, XA.shape[0], _ptr(XB) if XB.size else None, XB.shape[0],
+                 _ptr(oa), _ptr(ob), G, GAUGES[gauge], _ptr(out) if out.size else None))
+        if dense:
+            return out.reshape(XA.shape[0], XB.shape[0])
+        ends = np.cumsum(sizes)
+        return [out[e - z:e].reshape(int(a), int(b)) for e, z, a, b in zip(ends, sizes, na, nb)]
+
+    def plm_interaction_energies(self, XA, XB, split, offsets_a=None, offsets_b=None, gauge="zero_sum"):
+        return self._interaction_energies(self._l.dca_plm_interaction_energies, XA, XB, split, offsets_a, offsets_b, gauge)
+
+    def mf_interaction_energies(self, XA, XB, split, offsets_a=None, offsets_b=None, gauge="zero_sum"):
+        return self._interaction_energies(self._l.dca_mf_interaction_energies, XA, XB, split, offsets_a, offsets_b, gauge)
 
     # ---- replica-exchange Gibbs sampling (tempered.hip): `ladders` ladders of len(betas) walkers, walker r of ladder m at row
     # m R + r; betas strictly increasing -> dict: codes uint8[n, L], levels int32[n], energies float64[n] (E of the final codes),

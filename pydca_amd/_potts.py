@@ -258,7 +258,7 @@ def log_likelihood(energies, weights, meff, log_z):
 
 POTTS_SUBCOMMANDS = ('compute_energies', 'compute_mutation_effects', 'sample_sequences', 'compute_log_likelihood',
                      'compute_pseudo_log_likelihood', 'compare_sequences', 'compute_pca', 'sample_conditional', 'find_local_maxima',
-                     'sample_tempered')
+                     'sample_tempered', 'compute_interaction_energies')
 
 
 def pll_flag(per_site, exc_type):
@@ -321,6 +321,59 @@ def basins(codes, converged, energies):
     return rows[order], basin, counts[order].astype(np.int64)
 
 
+def group_species(labels):
+    """species labels (arbitrary hashables, one per row) -> (species in order of first appearance, their row-index arrays);
+    stable: a species' rows keep their order"""
+    order, rows = [], {}
+    for k, s in enumerate(labels):
+        if s not in rows:
+            rows[s] = []
+            order.append(s)
+        rows[s].append(k)
+    return order, [np.asarray(rows[s], dtype=np.int64) for s in order]
+
+
+def species_blocks(species_a, species_b, nA, nB, exc_type):
+    """-> (species present on both sides, rows_a, rows_b, species dropped because one side lacks them); None, None: one block
+    of all rows"""
+    if species_a is None and species_b is None:
+        return [None], [np.arange(nA, dtype=np.int64)], [np.arange(nB, dtype=np.int64)], []
+    if species_a is None or species_b is None:
+        raise exc_type('give the species labels of both proteins or of neither')
+    species_a, species_b = list(species_a), list(species_b)
+    if len(species_a) != nA or len(species_b) != nB:
+        raise exc_type('{} and {} species labels for {} and {} sequences'.format(len(species_a), len(species_b), nA, nB))
+    order_a, rows_a = group_species(species_a)
+    order_b, rows_b = group_species(species_b)
+    in_b = dict(zip(order_b, rows_b))
+    in_a = set(order_a)
+    both = [s for s in order_a if s in in_b]
+    dropped = [s for s in order_a if s not in in_b] + [s for s in order_b if s not in in_a]
+    return both, [r for s, r in zip(order_a, rows_a) if s in in_b], [in_b[s] for s in both], dropped
+
+
+def grouped_rows(XA, XB, rows_a, rows_b):
+    """the rows of every species gathered side by side -> (XA', XB', offsets_a, offsets_b)"""
+    ia = np.concatenate(rows_a) if rows_a else np.zeros(0, dtype=np.int64)
+    ib = np.concatenate(rows_b) if rows_b else np.zeros(0, dtype=np.int64)
+    oa = np.concatenate([[0], np.cumsum([len(r) for r in rows_a])]).astype(np.int32)
+    ob = np.concatenate([[0], np.cumsum([len(r) for r in rows_b])]).astype(np.int32)
+    return np.ascontiguousarray(XA[ia]), np.ascontiguousarray(XB[ib]), oa, ob
+
+
+def rank_matches(blocks, rows_a, rows_b, species):
+    """dca_assign_partners on every species' block -> the assigned pairs of all species ranked by gap (descending; equal gaps in
+    ascending A index): dict of pairs int64[n, 2] (A row, B row), energies, gaps float64[n], species (list)"""
+    found = []
+    for E, ra, rb, s in zip(blocks, rows_a, rows_b, species):
+        cols, _total, gaps = _lib.assign_partners(E)
+        found += [(int(ra[k]), int(rb[cols[k]]), float(E[k, cols[k]]), float(gaps[k]), s) for k in range(len(ra)) if cols[k] >= 0]
+    found.sort(key=lambda t: (-t[3], t[0]))
+    return dict(pairs=np.array([(t[0], t[1]) for t in found], dtype=np.int64).reshape(-1, 2),
+                energies=np.array([t[2] for t in found], dtype=np.float64), gaps=np.array([t[3] for t in found], dtype=np.float64),
+                species=[t[4] for t in found])
+
+
 class PottsModel:
     """The fitted model of PlmDCA and MeanFieldDCA as a sequence model: energies, single-mutant effects, Gibbs samples, log Z and
     pseudo-log-likelihoods, local maxima, replica exchange (DESIGN.md sections 11, 12, 14, 15, 23, 24 and 25; no reference counterpart).  E includes the gap state for PlmDCA
@@ -350,6 +403,52 @@ class PottsModel:
         X = self._query(sequences)
         self._potts_logger.info('\n\tStatistical energies of {} sequences'.format(X.shape[0]))
         return self._potts_call('energies', X)
+
+    def _interaction_inputs(self, sequences_a, sequences_b, split, species_a, species_b, gauge):
+        bio, L, _q = self._potts_dims()
+        split = operator.index(split)
+        if not 1 <= split <= L - 1:
+            raise self._potts_exc('split must lie in [1, {}], not {}'.format(L - 1, split))
+        if gauge not in _lib.GAUGES:
+            raise self._potts_exc('gauge must be one of {}'.format(sorted(_lib.GAUGES)))
+        XA = query_codes(sequences_a, bio, split, self._potts_table, self._potts_exc)
+        XB = query_codes(sequences_b, bio, L - split, self._potts_table, self._potts_exc)
+        species, rows_a, rows_b, dropped = species_blocks(species_a, species_b, XA.shape[0], XB.shape[0], self._potts_exc)
+        if dropped:
+            self._potts_logger.warning('\n\tSpecies on one side only are left out: {}'.format(dropped))
+        return split, XA, XB, species, rows_a, rows_b, dropped
+
+    def compute_interaction_energies(self, sequences_a, sequences_b, split, species_a=None, species_b=None, gauge='zero_sum'):
+        """Inter-protein interaction energies under a model fitted on a concatenated alignment: sites [0, split) are protein A,
+        the rest protein B; E(m, n) = sum over A sites i and B sites j of J_ij(a^m_i, b^n_j), no fields, higher is more
+        favourable.  sequences_a / sequences_b: FASTA paths or lists of aligned strings of lengths split and L - split (nothing
+        is de-duplicated).  gauge: 'zero_sum' (the couplings' zero-sum form over all states) or 'as_stored'.
+        Without species labels -> float64[nA, nB], all against all.  With one label per sequence (arbitrary hashables) -> a
+        dict: species (in order of first appearance, those present on both sides), rows_a / rows_b (their row indices, in
+        order), energies (one float64[nA_s, nB_s] per species) and dropped (species on one side only)."""
+        self._one_gpu('compute_interaction_energies')
+        split, XA, XB, species, rows_a, rows_b, dropped = self._interaction_inputs(sequences_a, sequences_b, split, species_a,
+                                                                                      species_b, gauge)
+        self._potts_logger.info('\n\tInteraction energies of {} x {} sequences in {} blocks'.format(XA.shape[0], XB.shape[0], len(species)))
+        if species == [None]:
+            return self._potts_call('interaction_energies', XA, XB, split, gauge=gauge)
+        GA, GB, oa, ob = grouped_rows(XA, XB, rows_a, rows_b)
+        blocks = self._potts_call('interaction_energies', GA, GB, split, oa, ob, gauge=gauge)
+        return dict(species=species, rows_a=rows_a, rows_b=rows_b, energies=blocks, dropped=dropped)
+
+    def match_partners(self, sequences_a, sequences_b, split, species_a=None, species_b=None, gauge='zero_sum'):
+        """Pairs every A sequence with a B sequence of its species: one maximum-weight assignment of the interaction energies per
+        species (compute_interaction_energies; dca_assign_partners).  -> dict: pairs int64[n, 2] (A row, B row), energies and
+        gaps float64[n] (the loss in a species' total when the pair is forbidden; +inf in a 1 x 1 species), species (per pair),
+        ranked by gap (descending; equal gaps in ascending A index), and dropped."""
+        self._one_gpu('match_partners')
+        split, XA, XB, species, rows_a, rows_b, dropped = self._interaction_inputs(sequences_a, sequences_b, split, species_a,
+                                                                                      species_b, gauge)
+        GA, GB, oa, ob = grouped_rows(XA, XB, rows_a, rows_b)
+        blocks = self._potts_call('interaction_energies', GA, GB, split, oa, ob, gauge=gauge)
+        res = rank_matches(blocks, rows_a, rows_b, species)
+        res['dropped'] = dropped
+        return res
 
     def compute_single_mutant_effects(self, wildtype):
         """dE(i, a) = E(wildtype with site i set to state a) - E(wildtype) for every site and state (gap last)
@@ -668,6 +767,59 @@ def run_find_local_maxima(instance, prefix, msa_file, output_dir, metadata, exc_
     return fa, txt
 
 
+def add_interaction_arguments(p):
+    """The options of the compute_interaction_energies sub-command (plmdca and mfdca command lines): msa_file is the
+    concatenated alignment the model is fitted on."""
+    p.add_argument('--query_file_a', required=True, help='FASTA file of aligned protein-A sequences (addition)')
+    p.add_argument('--query_file_b', required=True, help='FASTA file of aligned protein-B sequences (addition)')
+    p.add_argument('--split', type=int, required=True, help='number of protein-A sites: the first --split columns of msa_file (addition)')
+    p.add_argument('--species_a', help='file with one species label per record of --query_file_a, in file order (addition)')
+    p.add_argument('--species_b', help='the same for --query_file_b (addition)')
+    p.add_argument('--gauge', choices=sorted(_lib.GAUGES), default='zero_sum', help='gauge of the inter-protein couplings (addition)')
+
+
+INTERACTION_OPTIONS = ('query_file_a', 'query_file_b', 'split', 'species_a', 'species_b', 'gauge')
+
+
+def read_labels(path):
+    """one label per non-empty line"""
+    with open(path) as fh:
+        return [ln.strip() for ln in fh if ln.strip()]
+
+
+def run_interaction_energies(instance, prefix, msa_file, output_dir, metadata, exc_type, opts):
+    """compute_interaction_energies of the plmdca and mfdca command lines -> the path of <output_dir>/<prefix>_interaction_energies_
+    <alignment base>.txt: one line per within-species pair (A record, B record, 1-based, species, energy)."""
+    from .dca_utilities import dca_utilities
+    opts = dict(opts or {})
+    for k in ('query_file_a', 'query_file_b', 'split'):
+        if opts.get(k) is None:
+            raise exc_type('compute_interaction_energies needs --{}'.format(k))
+    if (opts.get('species_a') is None) != (opts.get('species_b') is None):
+        raise exc_type('give both --species_a and --species_b or neither')
+    sa = read_labels(opts['species_a']) if opts.get('species_a') else None
+    sb = read_labels(opts['species_b']) if opts.get('species_b') else None
+    gauge = opts.get('gauge') or 'zero_sum'
+    res = instance.compute_interaction_energies(opts['query_file_a'], opts['query_file_b'], opts['split'], sa, sb, gauge=gauge)
+    if sa is None:
+        res = dict(species=['all'], rows_a=[np.arange(res.shape[0])], rows_b=[np.arange(res.shape[1])], energies=[res], dropped=[])
+    dca_utilities.create_directories(output_dir)
+    path = dca_utilities.get_dca_output_file_path(output_dir, msa_file, prefix=prefix + '_interaction_energies_', postfix='.txt')
+    with open(path, 'w') as fh:
+        fh.write('# Inter-protein interaction energies ({} gauge); split {}\n'.format(gauge, opts['split']))
+        for line in metadata or []:
+            fh.write('{}\n'.format(line))
+        fh.write('# A records: {}\n# B records: {}\n'.format(opts['query_file_a'], opts['query_file_b']))
+        if res['dropped']:
+            fh.write('# Species on one side only (left out): {}\n'.format(', '.join(str(s) for s in res['dropped'])))
+        fh.write('# A record\tB record\tspecies\tenergy\n')
+        for s, ra, rb, E in zip(res['species'], res['rows_a'], res['rows_b'], res['energies']):
+            for k, a in enumerate(ra):
+                for l, b in enumerate(rb):
+                    fh.write('{}\t{}\t{}\t{!r}\n'.format(int(a) + 1, int(b) + 1, s, float(E[k, l])))
+    return path
+
+
 def add_ais_arguments(p):
     """The options of the compute_log_likelihood sub-command (plmdca and mfdca command lines)."""
     p.add_argument('--num_chains', type=int, default=1000, help='AIS chains (addition)')
@@ -702,7 +854,7 @@ def run_log_likelihood(instance, prefix, msa_file, output_dir, metadata, opts):
 
 def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata, biomolecule, table, exc_type,
                    query_file=None, wildtype_file=None, sampling=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None,
-                   conditional=None, ascent=None, tempered=None):
+                   conditional=None, ascent=None, tempered=None, interaction=None):
     """compute_energies / compute_mutation_effects / sample_sequences / compute_pseudo_log_likelihood / compare_sequences of the
     plmdca and mfdca command lines -> the path of the file written: <output_dir>/<prefix>_energies_<alignment base>.txt,
     <prefix>_mutation_effects_<alignment base>.txt, <prefix>_samples_<alignment base>.fa,
@@ -718,6 +870,8 @@ def run_subcommand(instance, the_command, prefix, msa_file, output_dir, metadata
         return run_sample_tempered(instance, prefix, msa_file, output_dir, metadata, biomolecule, exc_type, tempered)
     if the_command == 'find_local_maxima':      # ascent: its options (ASCENT_OPTIONS; run_find_local_maxima)
         return run_find_local_maxima(instance, prefix, msa_file, output_dir, metadata, exc_type, query_file, ascent)
+    if the_command == 'compute_interaction_energies':      # interaction: its options (INTERACTION_OPTIONS)
+        return run_interaction_energies(instance, prefix, msa_file, output_dir, metadata, exc_type, interaction)
     if the_command == 'compare_sequences':
         from . import _compare
         return _compare.run_compare(instance, prefix, msa_file, output_dir, metadata, query_file, exc_type, three_site=int(three_site or 0),

@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "dca_internal.h"
+#include "assignment.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -562,6 +563,16 @@ int dca_plm_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, u
     return dca_potts_sample_conditional(ctx, ps, n, sweeps, seed, first_chain, first_sweep, beta, free_sites, num_free, initial,
                                         random_start, out);
 }
+// inter-protein energies (interaction.hip) under the plm engine's x; one GPU only
+int dca_plm_interaction_energies(dca_ctx* ctx, int split, const uint8_t* XA, int nA, const uint8_t* XB, int nB, const int32_t* offsets_a,
+                                 const int32_t* offsets_b, int G, int gauge, double* out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_plm(ctx));
+    PottsSource ps;
+    DCA_TRY(ctx->plm->potts_source(&ps, true));
+    return dca_potts_interaction_energies(ctx, ps, split, XA, nA, XB, nB, offsets_a, offsets_b, G, gauge, out);
+}
 // greedy ascent to local maxima (ascent.hip) under the plm engine's x; one GPU only
 int dca_plm_ascend(dca_ctx* ctx, const uint8_t* X, int n, const int32_t* free_sites, int num_free, int max_steps, double min_gain,
                    uint8_t* out, int32_t* steps_out, uint8_t* converged_out, double* gain_out, int32_t* path_out, double* path_gain_out)
@@ -904,6 +915,23 @@ int dca_mf_sample_conditional(dca_ctx* ctx, int n, int sweeps, uint64_t seed, ui
     DCA_TRY(m.get(ctx));
     return dca_potts_sample_conditional(ctx, m.ps, n, sweeps, seed, first_chain, first_sweep, beta, free_sites, num_free, initial,
                                         random_start, out);
+}
+int dca_mf_interaction_energies(dca_ctx* ctx, int split, const uint8_t* XA, int nA, const uint8_t* XB, int nB, const int32_t* offsets_a,
+                                const int32_t* offsets_b, int G, int gauge, double* out)
+{
+    CHECK_CTX(ctx);
+    DCA_TRY(need_mf(ctx));
+    MfPotts m;
+    DCA_TRY(m.get(ctx));
+    return dca_potts_interaction_energies(ctx, m.ps, split, XA, nA, XB, nB, offsets_a, offsets_b, G, gauge, out);
+}
+int dca_assign_partners(const double* E, int nr, int nc, int32_t* col_of_row, double* total_out, double* gap_out)
+{
+    if (assign_partners_host(E, nr, nc, col_of_row, total_out, gap_out) != 0) {
+        dca_set_error("assign_partners: a negative size, a NULL array or a non-finite entry");
+        return DCA_ERR_ARG;
+    }
+    return DCA_OK;
 }
 int dca_mf_ascend(dca_ctx* ctx, const uint8_t* X, int n, const int32_t* free_sites, int num_free, int max_steps, double min_gain,
                   uint8_t* out, int32_t* steps_out, uint8_t* converged_out, double* gain_out, int32_t* path_out, double* path_gain_out)

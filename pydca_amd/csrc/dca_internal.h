@@ -262,6 +262,11 @@ int dca_potts_sample_conditional(dca_ctx* ctx, const PottsSource& ps, int n, int
                                  uint64_t first_sweep, double beta, const int32_t* free_sites, int num_free,
                                  const uint8_t* initial /* host n*L */, int random_start, uint8_t* out /* host n*L */);
 
+// ---- interaction.hip : inter-protein energies of host rows XA (nA x split) and XB (nB x (L - split)) in G groups
+// (dca_plm_interaction_energies semantics; all arguments checked here).  out: host.
+int dca_potts_interaction_energies(dca_ctx* ctx, const PottsSource& ps, int split, const uint8_t* XA, int nA, const uint8_t* XB, int nB,
+                                   const int32_t* offsets_a, const int32_t* offsets_b, int G, int gauge, double* out);
+
 // ---- ascent.hip : greedy ascent of host rows X (n x L codes < q) to local maxima of E over the free sites (dca_plm_ascend
 // semantics; all arguments checked here).  All outputs on the host; gain_out, path_out and path_gain_out may be NULL.
 int dca_potts_ascend(dca_ctx* ctx, const PottsSource& ps, const uint8_t* X, int n, const int32_t* free_sites, int num_free, int max_steps,

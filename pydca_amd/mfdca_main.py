@@ -5,7 +5,7 @@ import os
 import sys
 from argparse import ArgumentParser
 
-from . import _compare, _lib, _potts
+from . import _compare, _lib, _potts, pairing
 from .dca_utilities import dca_utilities
 from .meanfield_dca import meanfield_dca
 from .sequence_backmapper.sequence_backmapper import SequenceBackmapper
@@ -21,7 +21,8 @@ def configure_logging():
 def execute_from_command_line(msa_file=None, biomolecule=None, seqid=None, pseudocount=None, the_command=None,
                               refseq_file=None, verbose=False, output_dir=None, apc=False, ranked_by=None,
                               linear_dist=None, num_site_pairs=None, device=0, devices=None, query_file=None, wildtype_file=None, sampling=None,
-                              ais=None, three_site=0, three_site_no_gaps=False, pca=None, conditional=None, ascent=None, tempered=None):
+                              ais=None, three_site=0, three_site_no_gaps=False, pca=None, conditional=None, ascent=None, tempered=None,
+                              interaction=None):
     if verbose:
         configure_logging()
     mfdca_instance = meanfield_dca.MeanFieldDCA(msa_file, biomolecule, pseudocount=pseudocount, seqid=seqid, device=device, devices=devices)
@@ -39,7 +40,7 @@ def execute_from_command_line(msa_file=None, biomolecule=None, seqid=None, pseud
         return _potts.run_subcommand(mfdca_instance, the_command.strip(), 'MFDCA', msa_file, output_dir, param_metadata, bio, 1,
                                      meanfield_dca.MeanFieldDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling,
                                      ais=ais, three_site=three_site, three_site_no_gaps=bool(three_site_no_gaps), pca=pca,
-                                     conditional=conditional, ascent=ascent, tempered=tempered)
+                                     conditional=conditional, ascent=ascent, tempered=tempered, interaction=interaction)
     if the_command.strip() == 'compute_params':
         fields, couplings = mfdca_instance.compute_params(seqbackmapper=seqbackmapper, ranked_by=ranked_by, linear_dist=linear_dist,
                                                           num_site_pairs=num_site_pairs)
@@ -130,6 +131,8 @@ def run_meanfield_dca(argv=None):
             _potts.add_conditional_arguments(p)
         if name == 'find_local_maxima':
             _potts.add_ascent_arguments(p)
+        if name == 'compute_interaction_energies':
+            _potts.add_interaction_arguments(p)
         if name == 'sample_tempered':
             _potts.add_tempered_arguments(p)
         if name == 'compute_log_likelihood':
@@ -141,8 +144,13 @@ def run_meanfield_dca(argv=None):
             p.add_argument('--ranked_by', choices=('FN', 'FN_APC', 'DI', 'DI_APC', 'fn', 'fn_apc', 'di', 'di_apc'))
             p.add_argument('--linear_dist', type=int)
             p.add_argument('--num_site_pairs', type=int)
+    pairing.add_pair_partners_parser(subparsers)
     argv = sys.argv[1:] if argv is None else argv
     args = vars(parser.parse_args(args=argv if argv else ['--help']))
+    if args.get('subcommand_name') == pairing.PAIR_SUBCOMMAND:
+        if args.get('verbose'):
+            configure_logging()
+        return pairing.run_pair_partners(args)
     return execute_from_command_line(
         biomolecule=args.get('biomolecule'), msa_file=args.get('msa_file'), seqid=args.get('seqid'),
         pseudocount=args.get('pseudocount'), the_command=args.get('subcommand_name'), refseq_file=args.get('refseq_file'),
@@ -156,7 +164,8 @@ def run_meanfield_dca(argv=None):
         pca={k: args.get(k) for k in ('pca', 'num_components', 'seed')},
         conditional={k: args.get(k) for k in _potts.CONDITIONAL_OPTIONS},
         ascent={k: args.get(k) for k in _potts.ASCENT_OPTIONS},
-        tempered={k: args.get(k) for k in _potts.TEMPERED_OPTIONS})
+        tempered={k: args.get(k) for k in _potts.TEMPERED_OPTIONS},
+        interaction={k: args.get(k) for k in _potts.INTERACTION_OPTIONS})
 
 
 if __name__ == '__main__':

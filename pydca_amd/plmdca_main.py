@@ -25,7 +25,7 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
                               num_threads=None, ranked_by=None, linear_dist=None, num_site_pairs=None, device=0,
                               exact_gradient=False, precision=32, devices=None, query_file=None, wildtype_file=None, sampling=None,
                               boltzmann=None, ais=None, three_site=0, three_site_no_gaps=False, pca=None, conditional=None, ascent=None, tempered=None,
-                              decimation=None):
+                              decimation=None, interaction=None):
     if verbose:
         configure_logging()
     plmdca_instance = plmdca.PlmDCA(msa_file, biomolecule, seqid=seqid, lambda_h=lambda_h, lambda_J=lambda_J,
@@ -39,7 +39,7 @@ def execute_from_command_line(biomolecule, msa_file, the_command=None, refseq_fi
                                      _lib.DCA_BIOMOLECULE_PROTEIN if plmdca_instance.biomolecule == 'PROTEIN' else _lib.DCA_BIOMOLECULE_RNA, 0,
                                      plmdca.PlmDCAException, query_file=query_file, wildtype_file=wildtype_file, sampling=sampling,
                                      ais=ais, three_site=three_site, three_site_no_gaps=bool(three_site_no_gaps), pca=pca,
-                                     conditional=conditional, ascent=ascent, tempered=tempered)
+                                     conditional=conditional, ascent=ascent, tempered=tempered, interaction=interaction)
     if the_command == BOLTZMANN_SUBCOMMAND:
         if not output_dir:
             output_dir = 'PLMDCA_output_' + os.path.splitext(os.path.basename(msa_file))[0]
@@ -141,6 +141,8 @@ def run_plm_dca(argv=None):
             _potts.add_conditional_arguments(p)
         if name == 'find_local_maxima':
             _potts.add_ascent_arguments(p)
+        if name == 'compute_interaction_energies':
+            _potts.add_interaction_arguments(p)
         if name == 'sample_tempered':
             _potts.add_tempered_arguments(p)
         if name == 'compute_log_likelihood':
@@ -179,6 +181,7 @@ def run_plm_dca(argv=None):
         conditional={k: args.get(k) for k in _potts.CONDITIONAL_OPTIONS},
         ascent={k: args.get(k) for k in _potts.ASCENT_OPTIONS},
         tempered={k: args.get(k) for k in _potts.TEMPERED_OPTIONS},
+        interaction={k: args.get(k) for k in _potts.INTERACTION_OPTIONS},
         decimation={k: args.get(k) for k in _potts.DECIMATION_OPTIONS})
 
 
