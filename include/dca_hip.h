@@ -926,12 +926,54 @@ int dca_pca_fit(dca_ctx* ctx, int k, double tol, int max_iterations, uint64_t se
 int dca_pca_project(dca_ctx* ctx, const uint8_t* Q, int nq /* Q == NULL: the context's alignment */, int k,
                     const double* components /* k*L*q, host */, const double* offsets /* k */, double* proj_out /* nq*k */);
 
+/* ------------------------------------------------------------------ redundancy filter and identity clusters
+ * Preprocessing of a raw alignment: model-free and stateless, the alignment, the weights and any fitted
+ * model stay untouched; one GPU.  L and q are those of the context's alignment, so dca_set_msa comes first (DCA_ERR_STATE
+ * otherwise).  X: n x L host codes < q, or NULL: the context's alignment, already on the device (n is ignored).
+ *
+ * ident(m, n) = #{i : X_mi = X_ni}, the gap state counting like any other (as dca_compute_weights counts it).  Two rows are
+ * SIMILAR iff ident >= min_identical, an integer number of sites in 1 .. L + 1 (L + 1: nothing is similar to anything, not
+ * even a row to itself).  No floating-point rule enters: the caller turns an identity fraction into the count.
+ *
+ * dca_identity_filter: the sequential greedy filter.  order (n entries, a permutation of 0 .. n-1; NULL: ascending row index)
+ * gives the priority; rows are visited in that order and a row is KEPT iff no row kept before it is similar to it.
+ * keep_out[r] = 1 / 0; rep_out[r] = r for a kept row, else the kept row similar to r that comes EARLIEST IN THE ORDER.  The
+ * device returns exactly that: blocks of rank positions (DCA_FILTER_BLOCK, a positive count read per call, rounded up to a
+ * multiple of 64, at most 8192; 2048 when unset) are compared with the compact list of the rows kept so far (a 32-bit unsigned
+ * atomicMin of rank positions: a minimum, so arrival order cannot show) and resolved in ascending order by one workgroup; the
+ * count of kept rows stays on the device between blocks and the call synchronises once, at its end.  The result does not
+ * depend on the block size.  info (may be NULL): kept = number of kept rows, blocks and block_rows = the block plan,
+ * tile_pairs = the 64 x 64 tiles the launches covered (the cover pass is launched for the worst case).
+ *
+ * dca_identity_clusters: the connected components of the graph of similar pairs (single linkage).  label_out[r] = the SMALLEST
+ * row index of r's component; degree_out[r] (may be NULL) = #{m : ident(r, m) >= min_identical}, r itself included -- with the
+ * strict threshold of dca_compute_weights these are the integers of dca_get_weight_counts.  The n x ceil(n / 32)-dword
+ * similarity matrix stays on the device while n * ceil(n / 32) * 4 bytes <= DCA_CLUSTER_BITS_MAX (bytes, read per call; 8 GiB
+ * when unset); above it every round recomputes the compares from the bit planes and nothing is stored.  Both paths return the
+ * same labels and degrees.  Rounds of hook (atomicMin on labels) and pointer jumping repeat until one passes without a change;
+ * the fixpoint is unique (every label its component's smallest index), so the atomics' order cannot show.  info (may be NULL):
+ * clusters = number of components, largest = rows of the largest, rounds = rounds run (the last, unchanged one included),
+ * stored_bits = 1: the bits were kept, 0: recomputed per round.
+ *
+ * DCA_ERR_ARG: a NULL context, keep_out / label_out NULL, n < 1 with X, a code >= q, min_identical outside 1 .. L + 1, an order
+ * that is not a permutation.  Profiling tags "identity_filter", "identity_clusters" (the whole call; its parts under
+ * "identity_clusters_bits", "identity_clusters_degrees", "identity_clusters_rounds").  No reference counterpart. */
+typedef struct { int32_t kept, blocks, block_rows; int64_t tile_pairs; } dca_filter_info;
+typedef struct { int32_t clusters, largest, rounds, stored_bits /* 1: adjacency kept as bits, 0: recomputed per round */; } dca_cluster_info;
+
+int dca_identity_filter(dca_ctx* ctx, const uint8_t* X /* n x L, or NULL: the context's alignment */, int n, int min_identical,
+                        const int32_t* order /* n, or NULL */, uint8_t* keep_out /* n */, int32_t* rep_out /* n, may be NULL */,
+                        dca_filter_info* info /* may be NULL */);
+int dca_identity_clusters(dca_ctx* ctx, const uint8_t* X, int n, int min_identical, int32_t* label_out /* n */,
+                          int32_t* degree_out /* n, may be NULL */, dca_cluster_info* info /* may be NULL */);
+
 /* ------------------------------------------------------------------ timing
  * When profiling is on, selected kernels are bracketed with HIP events on the
  * context's stream.  dca_get_kernel_time returns accumulated ms and launch count
  * for a kernel tag ("weights", "plm_logits", "plm_softmax", "plm_scatter", "plm_expand",
  * "plm_fold", "lbfgs_vec", "mf_counts", "mf_inverse", "scores", "energies", "mutation_scan", "pll", "sample", "cond_fields", "sample_cond", "ar_logits", "ar_grad", "ar_sample", "ar_epistasis",
- * "bm_stats", "bm_decimate", "gauge", "ais", "hamming", "set_compare", "three_site_scan", "three_site_values", "pca_project", "pca_back", "pca_small"). */
+ * "bm_stats", "bm_decimate", "gauge", "ais", "hamming", "set_compare", "three_site_scan", "three_site_values", "pca_project", "pca_back", "pca_small",
+ * "identity_filter", "identity_clusters"). */
 int dca_set_profiling(dca_ctx* ctx, int on);
 /* Only the stage of this name ("plm_scatter", "plm_logits", "mf_inverse", ...) is bracketed -- two event records per launch of it
  * instead of two per stage (an event record costs the stream ~5 us: 14 per plmDCA iteration are 5 % of config C's step, 0.4 % of

@@ -72,6 +72,16 @@ class SetComparison(C.Structure):
     _fields_ = [(k, C.c_double * 3) for k in ("pearson", "slope", "max_abs_diff", "sxx", "syy", "sxy", "terms")]
 
 
+class FilterInfo(C.Structure):
+    """dca_filter_info (include/dca_hip.h)"""
+    _fields_ = [("kept", C.c_int32), ("blocks", C.c_int32), ("block_rows", C.c_int32), ("tile_pairs", C.c_int64)]
+
+
+class ClusterInfo(C.Structure):
+    """dca_cluster_info (include/dca_hip.h)"""
+    _fields_ = [("clusters", C.c_int32), ("largest", C.c_int32), ("rounds", C.c_int32), ("stored_bits", C.c_int32)]
+
+
 AR_CONVERGED, AR_MAX_ITERATIONS, AR_LINE_SEARCH_FAILED = 0, 1, 2
 
 COMM_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
@@ -197,6 +207,8 @@ def lib():
         "dca_hamming_nearest": (i, [vp, vp, i, vp, i, i, vp, vp, vp]),
         "dca_sequence_statistics": (i, [vp, vp, i, vp, vp, C.POINTER(SetComparison)]),
         "dca_alignment_statistics": (i, [vp, vp, vp]),
+        "dca_identity_filter": (i, [vp, vp, i, i, vp, vp, vp, C.POINTER(FilterInfo)]),
+        "dca_identity_clusters": (i, [vp, vp, i, i, vp, vp, C.POINTER(ClusterInfo)]),
         "dca_three_site_values": (i, [vp, vp, i, vp, i, vp, vp, vp, vp]),
         "dca_three_site_scan": (i, [vp, vp, i, i, i, vp, vp, vp, C.POINTER(i)]),
         "dca_pca_fit": (i, [vp, i, d, i, C.c_uint64, vp, vp, vp, vp, C.POINTER(d), C.POINTER(i), C.POINTER(i)]),
@@ -255,6 +267,7 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_plm_bm_set_mask", "dca_plm_bm_get_mask", "dca_plm_bm_decimate", "dca_plm_zero_sum_gauge",
            "dca_plm_ais", "dca_mf_ais", "dca_ais_estimate",
            "dca_hamming_nearest", "dca_sequence_statistics", "dca_alignment_statistics",
+           "dca_identity_filter", "dca_identity_clusters",
            "dca_three_site_values", "dca_three_site_scan", "dca_pca_fit", "dca_pca_project",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
@@ -1155,6 +1168,37 @@ class Context:
         fij = np.zeros((self.L * (self.L - 1) // 2, self.q, self.q), dtype=np.float64)
         check(self._l.dca_alignment_statistics(self._h, _ptr(fi), _ptr(fij)))
         return fi, fij
+
+    # ---- redundancy filter and identity clusters (redundancy.hip): model-free, nothing of the context changes
+    def _identity_rows(self, X):
+        x_ = None if X is None else np.ascontiguousarray(X, dtype=np.uint8).reshape(-1, self.L)
+        return x_, (self.N if x_ is None else x_.shape[0])
+
+    def identity_filter(self, min_identical, X=None, order=None, return_representatives=True):
+        """The sequential greedy filter at `min_identical` identical sites over the rows X (uint8[n, L]; None: the context's
+        alignment) visited in `order` (a permutation; None: ascending) -> (uint8[n] keep, int32[n] representative or None,
+        dict of the dca_filter_info fields)"""
+        x_, n = self._identity_rows(X)
+        o_ = None if order is None else np.ascontiguousarray(order, dtype=np.int32).reshape(-1)
+        if o_ is not None and o_.size != n:
+            raise ValueError("order must hold %d entries, not %d" % (n, o_.size))
+        keep = np.zeros(n, dtype=np.uint8)
+        rep = np.zeros(n, dtype=np.int32) if return_representatives else None
+        info = FilterInfo()
+        check(self._l.dca_identity_filter(self._h, None if x_ is None else _ptr(x_), int(n), int(min_identical),
+                                          None if o_ is None else _ptr(o_), _ptr(keep), None if rep is None else _ptr(rep), C.byref(info)))
+        return keep, rep, {k: int(getattr(info, k)) for k, _t in FilterInfo._fields_}
+
+    def identity_clusters(self, min_identical, X=None, return_degrees=True):
+        """Connected components of the similar pairs (single linkage) -> (int32[n] labels: the smallest row index of the
+        component, int32[n] degrees (the row itself included) or None, dict of the dca_cluster_info fields)"""
+        x_, n = self._identity_rows(X)
+        label = np.zeros(n, dtype=np.int32)
+        degree = np.zeros(n, dtype=np.int32) if return_degrees else None
+        info = ClusterInfo()
+        check(self._l.dca_identity_clusters(self._h, None if x_ is None else _ptr(x_), int(n), int(min_identical), _ptr(label),
+                                            None if degree is None else _ptr(degree), C.byref(info)))
+        return label, degree, {k: int(getattr(info, k)) for k, _t in ClusterInfo._fields_}
 
     # ---- three-site connected correlations (three_site.hip): integer counts, quantised alignment weights (include/dca_hip.h)
     def three_site_values(self, elements, Q=None):

@@ -686,6 +686,34 @@ int dca_alignment_statistics(dca_ctx* ctx, double* fi_out, double* fij_out)
     return dca_set_statistics_impl(ctx, nullptr, 0, fi_out, fij_out, nullptr);
 }
 
+// ------------------------------------------------------------------ redundancy filter and identity clusters (redundancy.hip)
+static int identity_arguments(dca_ctx* ctx, const char* who, const uint8_t* X, int n, int min_identical)
+{
+    if (!ctx->dX) { dca_set_error("%s: dca_set_msa first (the alignment gives L and q, and is the row set when X is NULL)", who); return DCA_ERR_STATE; }
+    if (X && n < 1) { dca_set_error("%s: n %d must be >= 1", who, n); return DCA_ERR_ARG; }
+    if (min_identical < 1 || min_identical > ctx->L + 1) {
+        dca_set_error("%s: min_identical %d is outside 1 .. L + 1 = %d", who, min_identical, ctx->L + 1);
+        return DCA_ERR_ARG;
+    }
+    return DCA_OK;
+}
+int dca_identity_filter(dca_ctx* ctx, const uint8_t* X, int n, int min_identical, const int32_t* order, uint8_t* keep_out,
+                        int32_t* rep_out, dca_filter_info* info)
+{
+    CHECK_CTX(ctx);
+    if (!keep_out) { dca_set_error("dca_identity_filter: keep_out is NULL"); return DCA_ERR_ARG; }
+    DCA_TRY(identity_arguments(ctx, "dca_identity_filter", X, n, min_identical));
+    return dca_identity_filter_impl(ctx, X, n, min_identical, order, keep_out, rep_out, info);
+}
+int dca_identity_clusters(dca_ctx* ctx, const uint8_t* X, int n, int min_identical, int32_t* label_out, int32_t* degree_out,
+                          dca_cluster_info* info)
+{
+    CHECK_CTX(ctx);
+    if (!label_out) { dca_set_error("dca_identity_clusters: label_out is NULL"); return DCA_ERR_ARG; }
+    DCA_TRY(identity_arguments(ctx, "dca_identity_clusters", X, n, min_identical));
+    return dca_identity_clusters_impl(ctx, X, n, min_identical, label_out, degree_out, info);
+}
+
 static int three_site_state(dca_ctx* ctx, const char* who, const uint8_t* Q, int nq)
 {
     if (!ctx->dX) { dca_set_error("%s: dca_set_msa first", who); return DCA_ERR_STATE; }

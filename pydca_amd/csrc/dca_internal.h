@@ -353,6 +353,13 @@ int dca_hamming_nearest_impl(dca_ctx* ctx, const uint8_t* Q, int nq, const uint8
                              int32_t* index_out, uint64_t* hist_out);
 int dca_set_statistics_impl(dca_ctx* ctx, const uint8_t* Q, int nq, double* fi_out, double* fij_out, dca_set_comparison* cmp_out);
 
+// ---- redundancy.hip : the greedy redundancy filter and the identity clusters (dca_identity_filter, dca_identity_clusters;
+// the state, n, T and the NULL outputs checked in capi.cpp, the codes and the order here)
+int dca_identity_filter_impl(dca_ctx* ctx, const uint8_t* X, int n, int T, const int32_t* order, uint8_t* keep_out, int32_t* rep_out,
+                             dca_filter_info* info);
+int dca_identity_clusters_impl(dca_ctx* ctx, const uint8_t* X, int n, int T, int32_t* label_out, int32_t* degree_out,
+                               dca_cluster_info* info);
+
 // ---- three_site.hip : three-site connected correlations of the alignment (Q == NULL, quantised weights) or of a set, at listed
 // elements and as a scan for the K strongest (dca_three_site_values, dca_three_site_scan; arguments checked in capi.cpp except
 // the elements and the codes)

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "dca_internal.h"
+#include "hamming_planes.h"
 
 namespace {
 
@@ -30,29 +31,7 @@ constexpr int kSuper = 32;     // tiles per super-tile side
 constexpr int kLdsHistMaxL = 12287;        // (L + 1) * 4 bytes <= 48 KiB of dynamic LDS beside the static staging buffers
 constexpr unsigned long long kNoKey = ~0ull;
 
-// rows of `stride` bytes, the first L of them codes -> planes P[(n * G + g) * PLP + p], sites past L as state 0 in every row
-template <int PL>
-__global__ __launch_bounds__(256)
-void nn_bitplanes_kernel(const uint8_t* __restrict__ X, size_t stride, int L, uint32_t* __restrict__ P, int N, int G)
-{
-    constexpr int PLP = (PL + 1) & ~1;
-    const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (idx >= (size_t)N * G) return;
-    const size_t n = idx / G;
-    const int g = (int)(idx % G);
-    const uint8_t* row = X + n * stride;
-    uint32_t planes[PL];
-#pragma unroll
-    for (int p = 0; p < PL; ++p) planes[p] = 0;
-    for (int k = 0; k < 32; ++k) {
-        const int j = g * 32 + k;
-        const uint32_t st = j < L ? row[j] : 0u;
-#pragma unroll
-        for (int p = 0; p < PL; ++p) planes[p] |= ((st >> p) & 1u) << k;
-    }
-#pragma unroll
-    for (int p = 0; p < PLP; ++p) P[idx * PLP + p] = p < PL ? planes[p] : 0u;
-}
+// nn_bitplanes_kernel: hamming_planes.h (shared with redundancy.hip)
 
 __global__ void nn_fill_keys_kernel(unsigned long long* __restrict__ keys, int n)
 {
