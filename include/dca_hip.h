@@ -114,6 +114,35 @@ int dca_sw_scores(const char* ref, int lref, const char* seqs, const int* offset
 int dca_sw_align(const char* a, int la, const char* b, int lb, const int* sub, int gap_open, int gap_extend,
                  int* score_out, int* start_a, int* start_b, char* aligned_a, char* aligned_b, int* aligned_len);
 
+/* ------------------------------------------------------------------ profile alignment (device)
+ * Aligns n sequences to a profile of Lp columns over A codes, one wave64 lane per sequence.  Integers only:
+ *     D[i][j] = max(D[i-1][j] + del_extend[i], H[i-1][j] + del_open[i])         column i deleted
+ *     I[i][j] = max(I[i][j-1] + ins_extend,    H[i][j-1] + ins_open)            residue j inserted
+ *     H[i][j] = max(H[i-1][j-1] + match[i][s_j], D[i][j], I[i][j])              DCA_ALIGN_LOCAL: also 0
+ * match: Lp x A; del_open, del_extend: Lp, each <= 0; ins_open, ins_extend <= 0.  seqs: codes < A, sequence k =
+ * seqs[offsets[k] .. offsets[k+1]), 0 .. 32767 residues.  DCA_ALIGN_LOCAL is Smith-Waterman (score: the maximum over all cells,
+ * the end cell the first maximum in row-major order, i outer); DCA_ALIGN_GLOCAL accounts for every column and lets the query
+ * overhang for free (H[0][j] = 0, H[i][0] = D[i][0] = del_open[1] + sum_{k=2..i} del_extend[k]; score: max_j H[Lp][j] at the
+ * smallest such j).  The traceback is dca_sw_align's: in H the diagonal, then D, then I (local: stop at H = 0); in D or I back
+ * to H whenever "open" is co-optimal with "extend".  residue_at_out (n x Lp, or NULL for scores only): the 0-based index in
+ * the sequence of the residue matched to column i, or -1.  Needs a context, no alignment.  DCA_ERR_ARG: Lp outside 1..8192, A
+ * outside 2..32, a positive penalty, (max|match| + max|penalty|) * (Lp + 32767) >= 2^28, a sequence longer than 32767, a code
+ * >= A (the message names the record).  The scratch of a call stays within 1 GiB by running the queries in passes;
+ * DCA_ALIGN_PASS caps the queries per pass; the results do not depend on the split.
+ * dca_profile_align_last_scratch: bytes of edge columns and pointer bits the largest pass of the context's last call took.
+ * dca_sw_scores_device: dca_sw_scores on the device, the same integers -- the profile match[i][b] = sub[ref_i][b] over 26
+ * letters plus "other" (-4 against everything), local mode, scores only.  lref 1..8192, gap penalties <= 0. */
+#define DCA_ALIGN_LOCAL 0
+#define DCA_ALIGN_GLOCAL 1
+int dca_profile_align(dca_ctx* ctx, const int32_t* match, int Lp, int A, const int32_t* del_open, const int32_t* del_extend,
+                      int ins_open, int ins_extend, int mode, const uint8_t* seqs, const int64_t* offsets, int n,
+                      int32_t* score_out /* n */, int32_t* residue_at_out /* n*Lp or NULL */);
+int dca_profile_align_last_scratch(dca_ctx* ctx, unsigned long long* bytes_out);
+/* the context's alignment as dca_set_msa received it: N x L codes (what a profile is built from) */
+int dca_get_msa(dca_ctx* ctx, uint8_t* out);
+int dca_sw_scores_device(dca_ctx* ctx, const char* ref, int lref, const char* seqs, const int* offsets, int nseq,
+                         const int* sub, int gap_open, int gap_extend, int* scores_out);
+
 /* ------------------------------------------------------------------ context */
 int dca_create(dca_ctx** out, int device, int precision /* DCA_F32 | DCA_F64 */);
 void dca_destroy(dca_ctx* ctx);

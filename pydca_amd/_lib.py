@@ -231,6 +231,10 @@ def lib():
         "dca_sw_scores": (i, [C.c_char_p, i, C.c_char_p, vp, i, vp, i, i, vp]),
         "dca_sw_align": (i, [C.c_char_p, i, C.c_char_p, i, vp, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.c_char_p,
                              C.c_char_p, C.POINTER(i)]),
+        "dca_profile_align": (i, [vp, vp, i, i, vp, vp, i, i, i, vp, vp, i, vp, vp]),
+        "dca_profile_align_last_scratch": (i, [vp, C.POINTER(C.c_ulonglong)]),
+        "dca_get_msa": (i, [vp, vp]),
+        "dca_sw_scores_device": (i, [vp, C.c_char_p, i, C.c_char_p, vp, i, vp, i, i, vp]),
         "dca_set_profiling": (i, [vp, i]),
         "dca_set_profiling_only": (i, [vp, C.c_char_p]),
         "dca_get_kernel_time": (i, [vp, C.c_char_p, C.POINTER(d), C.POINTER(i)]),
@@ -271,7 +275,8 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_three_site_values", "dca_three_site_scan", "dca_pca_fit", "dca_pca_project",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
-           "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
+           "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_profile_align",
+           "dca_profile_align_last_scratch", "dca_get_msa", "dca_sw_scores_device", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
            "dca_reset_kernel_times", "dca_plm_run", "plmdcaBackend", "freeFieldsAndCouplings"]
 
 
@@ -1200,6 +1205,44 @@ class Context:
                                             None if degree is None else _ptr(degree), C.byref(info)))
         return label, degree, {k: int(getattr(info, k)) for k, _t in ClusterInfo._fields_}
 
+    # ---- profile alignment (align.hip): needs the context only, no alignment
+    def profile_align(self, match, del_open, del_extend, ins_open, ins_extend, mode, seqs, traceback=True):
+        """match: int32[Lp, A]; del_open, del_extend: int32[Lp]; seqs: a list of uint8 code arrays (codes < A) ->
+        (int32[n] scores, int32[n, Lp] residue_at or None without traceback).  mode: DCA_ALIGN_LOCAL or DCA_ALIGN_GLOCAL."""
+        m = np.ascontiguousarray(match, dtype=np.int32)
+        if m.ndim != 2:
+            raise ValueError("match must be a 2-D array (Lp x A)")
+        Lp, A = m.shape
+        do, de = np.ascontiguousarray(del_open, dtype=np.int32).reshape(-1), np.ascontiguousarray(del_extend, dtype=np.int32).reshape(-1)
+        if do.size != Lp or de.size != Lp:
+            raise ValueError("del_open and del_extend must hold Lp = %d entries" % Lp)
+        rows = [np.ascontiguousarray(r, dtype=np.uint8).reshape(-1) for r in seqs]
+        n = len(rows)
+        offs = np.zeros(n + 1, dtype=np.int64)
+        if n:
+            offs[1:] = np.cumsum([r.size for r in rows])
+        blob = np.concatenate(rows) if n and offs[-1] else np.zeros(1, dtype=np.uint8)
+        score = np.zeros(n, dtype=np.int32)
+        res = np.full((n, Lp), -1, dtype=np.int32) if traceback else None
+        check(self._l.dca_profile_align(self._h, _ptr(m), int(Lp), int(A), _ptr(do), _ptr(de), int(ins_open), int(ins_extend), int(mode),
+                                        _ptr(blob), _ptr(offs), n, _ptr(score), None if res is None else _ptr(res)))
+        return score, res
+
+    def msa(self):
+        """The context's alignment as set_msa received it -> uint8[N, L]"""
+        X = np.zeros((self.N, self.L), dtype=np.uint8)
+        check(self._l.dca_get_msa(self._h, _ptr(X)))
+        return X
+
+    def profile_align_last_scratch(self):
+        b = C.c_ulonglong(0)
+        check(self._l.dca_profile_align_last_scratch(self._h, C.byref(b)))
+        return int(b.value)
+
+    def sw_scores(self, ref, seqs, sub, gap_open, gap_extend):
+        """sw_scores on the device (dca_sw_scores_device): the same integers"""
+        return _sw_scores_call(lambda *a: self._l.dca_sw_scores_device(self._h, *a), ref, seqs, sub, gap_open, gap_extend)
+
     # ---- three-site connected correlations (three_site.hip): integer counts, quantised alignment weights (include/dca_hip.h)
     def three_site_values(self, elements, Q=None):
         """elements: int32[T, 6] rows (i, j, k, a, b, c) in the context's column order; Q: uint8[nq, L] or None (the alignment
@@ -1349,9 +1392,15 @@ class Context:
         return ms.value, n.value
 
 
+DCA_ALIGN_LOCAL, DCA_ALIGN_GLOCAL = 0, 1
+
+
 def sw_scores(ref, seqs, sub, gap_open, gap_extend):
     """Best local alignment score of `ref` against every string of `seqs` (host code in libdca_hip.so)."""
-    L = lib()
+    return _sw_scores_call(lib().dca_sw_scores, ref, seqs, sub, gap_open, gap_extend)
+
+
+def _sw_scores_call(entry, ref, seqs, sub, gap_open, gap_extend):
     enc = [s.encode("ascii") for s in seqs]
     offs = np.zeros(len(enc) + 1, dtype=np.int32)
     offs[1:] = np.cumsum([len(e) for e in enc])
@@ -1359,7 +1408,7 @@ def sw_scores(ref, seqs, sub, gap_open, gap_extend):
     sub = np.ascontiguousarray(sub, dtype=np.int32)
     out = np.zeros(len(enc), dtype=np.int32)
     r = ref.encode("ascii")
-    check(L.dca_sw_scores(r, len(r), blob, _ptr(offs), len(enc), _ptr(sub), int(gap_open), int(gap_extend), _ptr(out)))
+    check(entry(r, len(r), blob, _ptr(offs), len(enc), _ptr(sub), int(gap_open), int(gap_extend), _ptr(out)))
     return out
 
 

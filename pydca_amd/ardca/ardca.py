@@ -11,7 +11,7 @@ import os
 
 import numpy as np
 
-from .. import _compare, _lib, _potts, _ranking
+from .. import _compare, _lib, _potts, _ranking, profile_alignment
 from ..fasta_reader import fasta_reader
 
 logger = logging.getLogger(__name__)
@@ -108,7 +108,7 @@ def file_pair_scores(scores_model, site_order):
     return np.asarray(scores_model)[idx]
 
 
-class ArDCA(_compare.SequenceComparison):
+class ArDCA(_compare.SequenceComparison, profile_alignment.SequenceAlignment):
     """arDCA of a FASTA alignment: ArDCA(msa_file, 'protein' | 'rna', seqid=0.8, lambda_h=1e-6, lambda_J=1e-2,
     max_iterations=1000, epsilon=1e-5, order='entropy', device=0).  lambda_h, lambda_J weigh the L2 penalty against the
     weighted log-likelihood per effective sequence.  order: 'entropy' (ascending entropy of the weighted

@@ -2,6 +2,7 @@
 #include <cstdlib>
 
 #include "dca_internal.h"
+#include "align_plan.h"
 #include "assignment.h"
 
 static thread_local char g_err[1024] = "";
@@ -684,6 +685,88 @@ int dca_alignment_statistics(dca_ctx* ctx, double* fi_out, double* fij_out)
     if (ctx->L < 2) { dca_set_error("dca_alignment_statistics: the alignment needs at least two sites"); return DCA_ERR_STATE; }
     if (!ctx->have_weights) { dca_set_error("dca_alignment_statistics: dca_compute_weights or dca_set_weights first"); return DCA_ERR_STATE; }
     return dca_set_statistics_impl(ctx, nullptr, 0, fi_out, fij_out, nullptr);
+}
+
+// ------------------------------------------------------------------ profile alignment (align.hip)
+int dca_profile_align(dca_ctx* ctx, const int32_t* match, int Lp, int A, const int32_t* del_open, const int32_t* del_extend,
+                      int ins_open, int ins_extend, int mode, const uint8_t* seqs, const int64_t* offsets, int n,
+                      int32_t* score_out, int32_t* residue_at_out)
+{
+    static const char* who = "dca_profile_align";
+    CHECK_CTX(ctx);
+    if (!match || !del_open || !del_extend || !offsets || !score_out || (!seqs && n > 0 && offsets[n] > offsets[0])) {
+        dca_set_error("%s: a required pointer is NULL", who);
+        return DCA_ERR_ARG;
+    }
+    if (Lp < 1 || Lp > kAlignMaxLp) { dca_set_error("%s: Lp %d is outside 1 .. %d", who, Lp, kAlignMaxLp); return DCA_ERR_ARG; }
+    if (A < 2 || A > kAlignMaxA) { dca_set_error("%s: A %d is outside 2 .. %d", who, A, kAlignMaxA); return DCA_ERR_ARG; }
+    if (mode != DCA_ALIGN_LOCAL && mode != DCA_ALIGN_GLOCAL) { dca_set_error("%s: mode %d is neither DCA_ALIGN_LOCAL nor DCA_ALIGN_GLOCAL", who, mode); return DCA_ERR_ARG; }
+    if (n < 0) { dca_set_error("%s: n %d < 0", who, n); return DCA_ERR_ARG; }
+    long long maxMatch = 0, maxPenalty = std::max(std::llabs((long long)ins_open), std::llabs((long long)ins_extend));
+    if (ins_open > 0 || ins_extend > 0) { dca_set_error("%s: ins_open %d and ins_extend %d must be <= 0", who, ins_open, ins_extend); return DCA_ERR_ARG; }
+    for (int i = 0; i < Lp; ++i) {
+        if (del_open[i] > 0 || del_extend[i] > 0) {
+            dca_set_error("%s: del_open %d / del_extend %d of column %d must be <= 0", who, del_open[i], del_extend[i], i);
+            return DCA_ERR_ARG;
+        }
+        maxPenalty = std::max(maxPenalty, std::max(std::llabs((long long)del_open[i]), std::llabs((long long)del_extend[i])));
+    }
+    for (size_t k = 0; k < (size_t)Lp * A; ++k) maxMatch = std::max(maxMatch, std::llabs((long long)match[k]));
+    if (!align_values_in_range(maxMatch, maxPenalty, Lp)) {
+        dca_set_error("%s: (max|match| %lld + max|penalty| %lld) * (Lp + 32767) reaches 2^28: the sums could overflow", who, maxMatch, maxPenalty);
+        return DCA_ERR_ARG;
+    }
+    for (int k = 0; k < n; ++k) {
+        const long long len = offsets[k + 1] - offsets[k];
+        if (len < 0 || len > kAlignMaxLen) { dca_set_error("%s: record %d has %lld residues (0 .. %d)", who, k, len, kAlignMaxLen); return DCA_ERR_ARG; }
+        for (long long j = offsets[k]; j < offsets[k + 1]; ++j)
+            if (seqs[j] >= A) { dca_set_error("%s: code %d >= A at residue %lld of record %d", who, (int)seqs[j], j - offsets[k], k); return DCA_ERR_ARG; }
+    }
+    return dca_profile_align_impl(ctx, match, Lp, A, del_open, del_extend, ins_open, ins_extend, mode, seqs, offsets, n, score_out,
+                                  residue_at_out, &ctx->alignScratchBytes);
+}
+int dca_get_msa(dca_ctx* ctx, uint8_t* out)
+{
+    CHECK_CTX(ctx);
+    if (!out) { dca_set_error("dca_get_msa: out is NULL"); return DCA_ERR_ARG; }
+    if (!ctx->dX) { dca_set_error("dca_get_msa: dca_set_msa first"); return DCA_ERR_STATE; }
+    const uint8_t* X = dca_host_msa(ctx);
+    if (!X) return DCA_ERR_HIP;
+    memcpy(out, X, (size_t)ctx->N * ctx->L);
+    return DCA_OK;
+}
+int dca_profile_align_last_scratch(dca_ctx* ctx, unsigned long long* bytes_out)
+{
+    CHECK_CTX(ctx);
+    if (!bytes_out) { dca_set_error("dca_profile_align_last_scratch: bytes_out is NULL"); return DCA_ERR_ARG; }
+    *bytes_out = ctx->alignScratchBytes;
+    return DCA_OK;
+}
+int dca_sw_scores_device(dca_ctx* ctx, const char* ref, int lref, const char* seqs, const int* offsets, int nseq, const int* sub,
+                         int gap_open, int gap_extend, int* scores_out)
+{
+    CHECK_CTX(ctx);
+    if (!ref || !seqs || !offsets || !sub || !scores_out || nseq < 0) { dca_set_error("dca_sw_scores_device: bad arguments"); return DCA_ERR_ARG; }
+    if (lref < 1 || lref > kAlignMaxLp) { dca_set_error("dca_sw_scores_device: lref %d is outside 1 .. %d", lref, kAlignMaxLp); return DCA_ERR_ARG; }
+    // the query profile: 26 letters plus "other", which scores -4 against everything as sub_score (host_io.cpp) does
+    constexpr int A = 27;
+    const int Lp = lref;
+    std::vector<int32_t> match((size_t)Lp * A, -4), open((size_t)Lp, gap_open), extend((size_t)Lp, gap_extend);
+    for (int i = 0; i < Lp; ++i) {
+        const int ia = (unsigned char)ref[i] - 'A';
+        if (ia < 0 || ia >= 26) continue;
+        for (int b = 0; b < 26; ++b) match[(size_t)i * A + b] = sub[ia * 26 + b];
+    }
+    std::vector<int64_t> offs((size_t)nseq + 1);
+    for (int k = 0; k <= nseq; ++k) offs[k] = offsets[k] - offsets[0];
+    std::vector<uint8_t> codes((size_t)std::max<int64_t>(offs[nseq], 1));
+    for (int64_t j = 0; j < offs[nseq]; ++j) {
+        const int ib = (unsigned char)seqs[offsets[0] + j] - 'A';
+        codes[j] = (uint8_t)(ib < 0 || ib >= 26 ? 26 : ib);
+    }
+    static_assert(sizeof(int) == sizeof(int32_t), "scores_out is filled as int32");
+    return dca_profile_align(ctx, match.data(), Lp, A, open.data(), extend.data(), gap_open, gap_extend, DCA_ALIGN_LOCAL, codes.data(),
+                             offs.data(), nseq, reinterpret_cast<int32_t*>(scores_out), nullptr);
 }
 
 // ------------------------------------------------------------------ redundancy filter and identity clusters (redundancy.hip)

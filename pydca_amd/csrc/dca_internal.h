@@ -89,6 +89,7 @@ struct dca_ctx {
     std::vector<uint8_t> hX;  // host copy, N x L, filled on demand by dca_host_msa()
     double* dLastScores = nullptr;   // most recent score vector (pair order), for dca_scores_order
     int nLastScores = 0;
+    unsigned long long alignScratchBytes = 0;   // edge columns + pointer bits of the largest pass of the last dca_profile_align
 
     // weights
     bool have_weights = false;
@@ -359,6 +360,11 @@ int dca_identity_filter_impl(dca_ctx* ctx, const uint8_t* X, int n, int T, const
                              dca_filter_info* info);
 int dca_identity_clusters_impl(dca_ctx* ctx, const uint8_t* X, int n, int T, int32_t* label_out, int32_t* degree_out,
                                dca_cluster_info* info);
+
+// ---- align.hip : profile alignment, one lane per query (dca_profile_align, dca_sw_scores_device; every argument checked in capi.cpp)
+int dca_profile_align_impl(dca_ctx* ctx, const int32_t* match, int Lp, int A, const int32_t* del_open, const int32_t* del_extend,
+                           int ins_open, int ins_extend, int mode, const uint8_t* seqs, const int64_t* offsets, int n,
+                           int32_t* score_out, int32_t* residue_at_out, unsigned long long* scratch_bytes_out);
 
 // ---- three_site.hip : three-site connected correlations of the alignment (Q == NULL, quantised weights) or of a set, at listed
 // elements and as a scan for the K strongest (dca_three_site_values, dca_three_site_scan; arguments checked in capi.cpp except

@@ -3,7 +3,7 @@
 names.  The remaining `pydca` sub-commands (contact maps, PDB content, plots) are outside the scope
 table (out of scope).  Beside the trimming: filter_by_identity, cluster_sequences and
 split_by_clusters (pydca_amd/redundancy.py; no reference counterpart), with the same output-directory
-convention."""
+convention; and align_sequences (pydca_amd/profile_alignment.py), which aligns raw sequences to an MSA's columns."""
 import logging
 import os
 import sys
@@ -11,7 +11,7 @@ from argparse import ArgumentParser
 
 from .dca_utilities import dca_utilities
 from .msa_trimmer.msa_trimmer import MSATrimmer
-from . import redundancy
+from . import profile_alignment, redundancy
 
 logger = logging.getLogger(__name__)
 MSA_TRIMMING_SUBCOMMANDS = ['trim_by_refseq', 'trim_by_gap_size']
@@ -58,8 +58,14 @@ def run_pydca(argv=None):
     p.add_argument('--verbose', action='store_true')
     p.add_argument('--output_dir')
     redundancy.add_subparsers(subparsers)
+    profile_alignment.add_subparsers(subparsers)
     argv = sys.argv[1:] if argv is None else argv
     args = vars(parser.parse_args(args=argv if argv else ['--help']))
+    if args.get('subcommand_name') in profile_alignment.ALIGN_SUBCOMMANDS:
+        if args.get('verbose'):
+            logging.basicConfig(level=logging.INFO, format='%(levelname)s %(name)s: %(message)s')
+        return profile_alignment.execute(args['msa_file'], args['biomolecule'], args['sequences_file'], mode=args['mode'], a2m=args['a2m'],
+                                         seqid=args['seqid'], device=args['device'], output_dir=args.get('output_dir'))
     if args.get('subcommand_name') in redundancy.REDUNDANCY_SUBCOMMANDS:
         extra = {k: args[k] for k in ('identity', 'priority', 'strict', 'test_fraction', 'seed', 'device') if k in args}
         return execute_from_command_line(msa_file=args['msa_file'], biomolecule=args['biomolecule'], the_command=args['subcommand_name'],

@@ -6,7 +6,7 @@ import time
 
 import numpy as np
 
-from .. import _compare, _lib, _potts, _ranking, multi_gpu
+from .. import _compare, _lib, _potts, _ranking, multi_gpu, profile_alignment
 from ..fasta_reader import fasta_reader
 from . import msa_numerics
 
@@ -25,7 +25,7 @@ def _ranked(scores, L, ctx=None):
     return _ranking.ranked(scores, L, ctx.scores_order() if ctx is not None else None)
 
 
-class MeanFieldDCA(_potts.PottsModel, _compare.SequenceComparison):
+class MeanFieldDCA(_potts.PottsModel, _compare.SequenceComparison, profile_alignment.SequenceAlignment):
     """Mean-field DCA (meanfield_dca.py:43-139)."""
 
     def __init__(self, msa, biomolecule, pseudocount=None, seqid=None, device=0, devices=None):

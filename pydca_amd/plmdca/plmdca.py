@@ -8,7 +8,7 @@ import time
 
 import numpy as np
 
-from .. import _compare, _lib, _potts, _ranking, multi_gpu
+from .. import _compare, _lib, _potts, _ranking, multi_gpu, profile_alignment
 
 logger = logging.getLogger(__name__)
 
@@ -85,7 +85,7 @@ def _decimation_options(target_density, drop_fraction, pearson_target, iteration
     return opts
 
 
-class PlmDCA(_potts.PottsModel, _compare.SequenceComparison):
+class PlmDCA(_potts.PottsModel, _compare.SequenceComparison, profile_alignment.SequenceAlignment):
     """plmdca.py:25-104.  Extra keyword arguments (not in the reference): device,
     precision (32: float storage as the reference; 64: float64 checking mode) and
     exact_gradient (opt-in mathematically exact pseudolikelihood gradient instead of the

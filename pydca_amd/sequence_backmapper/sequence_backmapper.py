@@ -114,12 +114,29 @@ class SequenceBackmapper:
             logger.info('the first row, without its gaps, is the reference sequence: no search needed')
             return [first]
         sub, gap_open, gap_extend = self._scoring()
-        scores = _lib.sw_scores(self.__ref_sequence, [s.replace('-', '') for s in self.__alignment], sub, gap_open, gap_extend)
+        scores = self._search_scores([s.replace('-', '') for s in self.__alignment], sub, gap_open, gap_extend)
         max_score = scores.max()
         best = [self.__alignment[k] for k in range(len(self.__alignment)) if scores[k] == max_score]
         if len(best) > 1:
             logger.warning('{} rows match the reference equally well; the first one is used'.format(len(best)))
         return best
+
+    def _search_scores(self, rows, sub, gap_open, gap_extend):
+        """The local score of the reference against every row: on the GPU (dca_sw_scores_device, one lane per row) when there
+        is one, DCA_SW_DEVICE is not 0 and the sizes are the device aligner's; otherwise the host loop.  The same integers."""
+        ref = self.__ref_sequence
+        on_device = (os.environ.get('DCA_SW_DEVICE', '1') != '0' and 1 <= len(ref) <= 8192 and gap_open <= 0 and gap_extend <= 0
+                     and max(len(r) for r in rows) <= 32767 and _lib.lib().dca_device_count() > 0)
+        if not on_device:
+            return _lib.sw_scores(ref, rows, sub, gap_open, gap_extend)
+        try:
+            ctx = _lib.Context(0, _lib.DCA_F32)
+        except _lib.DcaBackendError:            # a visible device that is not usable (another architecture): the host loop serves
+            return _lib.sw_scores(ref, rows, sub, gap_open, gap_extend)
+        try:
+            return ctx.sw_scores(ref, rows, sub, gap_open, gap_extend)
+        finally:
+            ctx.close()
 
     @staticmethod
     def _thread_through_row(aligned_ref, row_tail, n_template):
