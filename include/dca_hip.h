@@ -761,6 +761,56 @@ int dca_mf_corr_from_freqs(dca_ctx* ctx, const double* reg_fi, const double* reg
 /* test hook / stage API: inverse of a host SPD matrix through the same device path */
 int dca_spd_inverse(dca_ctx* ctx, const double* A, int n, double* Ainv_out);
 
+/* ------------------------------------------------------------------ Hopfield-Potts model
+ * Cocco, Monasson, Weigt, PLoS Comput Biol 9, e1003176 (2013).  With n = L (q - 1), C the matrix of dca_mf_corr_mat at the
+ * context's weights and the given pseudocount and D its block diagonal, the patterns are the solutions of C u = lambda D u with
+ * u^T D u = 1 (the entry of u of largest magnitude positive, ties to the smallest index).  A pattern's likelihood gain is
+ * (lambda - 1 - ln lambda) / 2; it is attractive for lambda > 1 and repulsive for lambda < 1.  The couplings of the selected set
+ * S are J = sum_S (1 - 1 / lambda) u u^T off the diagonal blocks, in the layout of dca_mf_couplings, and the fields are those of
+ * dca_mf_fields on that J.
+ * dca_mf_hopfield_fit: selection DCA_HOPFIELD_LIKELIHOOD takes the num_patterns patterns of largest gain over the whole spectrum
+ * (equal gains go to the attractive side); DCA_HOPFIELD_EXPLICIT the num_attractive largest and num_repulsive smallest
+ * eigenvalues.  Outputs, each of capacity p = num_patterns or num_attractive + num_repulsive, the attractive patterns first in
+ * descending order of lambda, then the repulsive ones in ascending order: eigenvalues, gains, signs (+1 attractive: 1 - 1 /
+ * lambda > 0; -1 repulsive), patterns (p x L (q - 1): xi = |1 - 1 / lambda|^1/2 u, so J = sum sign xi xi^T), residuals
+ * (||Gamma v - lambda v|| with Gamma = R^-1 C R^-T, D = R R^T, v = R^T u, measured on Gamma itself for both ends).  Each end is
+ * found by block subspace iteration with Rayleigh-Ritz on min(n, k + 8) vectors, the attractive end on Gamma and the repulsive end
+ * on its inverse, until every wanted residual is <= tol * (the block's largest Ritz value) or max_iterations is reached; info
+ * reports the iterations and the convergence of each end ([0] attractive, [1] repulsive) and how many patterns each gave.  The
+ * order of every sum is fixed by the shapes alone: the same call gives the same bits.
+ * Afterwards the context holds the Hopfield-Potts J: dca_mf_scores, dca_mf_di_scores, dca_mf_fields, dca_mf_pair_couplings and
+ * every dca_mf_* sequence-model entry serve it until dca_mf_corr_mat, dca_mf_couplings, dca_mf_run, new weights or a new
+ * exchange scheme return the context to the mean-field model.  dca_mf_model_kind tells which model is held;
+ * dca_mf_hopfield_couplings copies J out (n x n; its diagonal blocks are as the sum gives them and mean nothing).
+ * DCA_ERR_ARG: args or an output NULL, a selection that is neither, num_attractive or num_repulsive outside 0 .. 64, no pattern
+ * or more than n asked for, a likelihood selection that needs more than 64 patterns of one end, tol <= 0, max_iterations < 1.
+ * DCA_ERR_STATE: no alignment or weights; a row window, a reduce hook or a native communicator (one GPU only).
+ * DCA_ERR_NOT_SPD: a diagonal block (the message names the site) or Gamma is not positive definite.
+ * Profiling tags "hopfield_whiten", "hopfield_apply", "hopfield_assemble", "pca_small". */
+#define DCA_HOPFIELD_EXPLICIT 0
+#define DCA_HOPFIELD_LIKELIHOOD 1
+#define DCA_MF_MODEL_NONE 0
+#define DCA_MF_MODEL_MEAN_FIELD 1
+#define DCA_MF_MODEL_HOPFIELD 2
+typedef struct dca_hopfield_args {
+    int32_t selection, num_patterns, num_attractive, num_repulsive, max_iterations;
+    double tol;
+    uint64_t seed;
+} dca_hopfield_args;
+typedef struct dca_hopfield_info { int32_t num_attractive, num_repulsive, iterations[2], converged[2]; } dca_hopfield_info;
+int dca_mf_hopfield_fit(dca_ctx* ctx, double pseudocount, const dca_hopfield_args* args, double* eigenvalues_out, double* gains_out,
+                        int32_t* signs_out, double* patterns_out, double* residuals_out, dca_hopfield_info* info_out);
+int dca_mf_model_kind(dca_ctx* ctx, int* kind_out);
+int dca_mf_hopfield_couplings(dca_ctx* ctx, double* out);
+/* Overlaps of sequences with patterns: out[s * p + mu] = sum over the sites i ascending of xi_mu(i, s_i), a gap adding 0: one
+ * chain of doubles per (sequence, pattern), so a sequence has the same bits alone, in any batch and under any DCA_NN_PASS (the
+ * kernel and the passes of dca_pca_project).  Q: nq x L host codes, or NULL for the context's alignment; patterns: p x L (q - 1).
+ * DCA_ERR_ARG: patterns or out NULL, p < 1, nq < 1 with Q, a code >= q.  DCA_ERR_STATE: no alignment. */
+int dca_hopfield_project(dca_ctx* ctx, const uint8_t* Q, int nq, int p, const double* patterns, double* out);
+/* test hook: Y (n x b) = A V for a host A (n rows at stride ld >= n) and a host V (n x b, 1 <= b <= 72) through the operator
+ * kernel of the fit */
+int dca_dense_apply(dca_ctx* ctx, const double* A, int n, int ld, const double* V, int b, double* Y);
+
 /* ------------------------------------------------------------------ autoregressive model (arDCA)
  * Trinquier et al., Nat. Commun. 12, 5800 (2021).  Sites are in model order: the column order of the context's alignment (a
  * caller that wants another order permutes the columns before dca_set_msa).  x has the plm layout and size

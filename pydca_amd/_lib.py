@@ -82,6 +82,21 @@ class ClusterInfo(C.Structure):
     _fields_ = [("clusters", C.c_int32), ("largest", C.c_int32), ("rounds", C.c_int32), ("stored_bits", C.c_int32)]
 
 
+class HopfieldArgs(C.Structure):
+    """dca_hopfield_args (include/dca_hip.h)"""
+    _fields_ = [("selection", C.c_int32), ("num_patterns", C.c_int32), ("num_attractive", C.c_int32), ("num_repulsive", C.c_int32),
+                ("max_iterations", C.c_int32), ("tol", C.c_double), ("seed", C.c_uint64)]
+
+
+class HopfieldInfo(C.Structure):
+    """dca_hopfield_info (include/dca_hip.h)"""
+    _fields_ = [("num_attractive", C.c_int32), ("num_repulsive", C.c_int32), ("iterations", C.c_int32 * 2), ("converged", C.c_int32 * 2)]
+
+
+HOPFIELD_EXPLICIT, HOPFIELD_LIKELIHOOD = 0, 1
+MF_MODEL_NONE, MF_MODEL_MEAN_FIELD, MF_MODEL_HOPFIELD = 0, 1, 2
+HOPFIELD_MAX_PER_END = 64
+
 AR_CONVERGED, AR_MAX_ITERATIONS, AR_LINE_SEARCH_FAILED = 0, 1, 2
 
 COMM_HOOK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_int)
@@ -225,6 +240,11 @@ def lib():
         "dca_mf_run": (i, [vp, d, i, vp, vp]),
         "dca_mf_corr_from_freqs": (i, [vp, vp, vp, i, i, vp]),
         "dca_spd_inverse": (i, [vp, vp, i, vp]),
+        "dca_mf_hopfield_fit": (i, [vp, d, C.POINTER(HopfieldArgs), vp, vp, vp, vp, vp, C.POINTER(HopfieldInfo)]),
+        "dca_mf_model_kind": (i, [vp, C.POINTER(i)]),
+        "dca_mf_hopfield_couplings": (i, [vp, vp]),
+        "dca_hopfield_project": (i, [vp, vp, i, i, vp, vp]),
+        "dca_dense_apply": (i, [vp, vp, i, i, vp, i, vp]),
         "dca_comm_abort": (i, [vp]),
         "dca_plm_run": (i, [vp, vp, i, vp]),
         "dca_scores_order": (i, [vp, vp, i]),
@@ -275,7 +295,8 @@ EXPORTS = ["dca_weights_work", "dca_compute_weights_sharded", "dca_weights_parti
            "dca_three_site_values", "dca_three_site_scan", "dca_pca_fit", "dca_pca_project",
            "dca_mf_single_site_freqs",
            "dca_mf_pair_site_freqs", "dca_mf_corr_mat", "dca_mf_couplings", "dca_mf_scores", "dca_mf_run",
-           "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_sw_scores", "dca_sw_align", "dca_profile_align",
+           "dca_mf_corr_from_freqs", "dca_spd_inverse", "dca_mf_hopfield_fit", "dca_mf_model_kind", "dca_mf_hopfield_couplings",
+           "dca_hopfield_project", "dca_dense_apply", "dca_sw_scores", "dca_sw_align", "dca_profile_align",
            "dca_profile_align_last_scratch", "dca_get_msa", "dca_sw_scores_device", "dca_scores_order", "dca_set_profiling", "dca_set_profiling_only", "dca_get_kernel_time",
            "dca_reset_kernel_times", "dca_plm_run", "plmdcaBackend", "freeFieldsAndCouplings"]
 
@@ -330,6 +351,43 @@ def pca_arguments(num_components, tolerance, max_iterations, seed, L, q):
     if sd < 0 or sd >= 1 << 64:
         raise ValueError("seed must be in 0 .. 2^64 - 1, not %d" % sd)
     return k, tol, it, sd
+
+
+def hopfield_arguments(num_patterns, num_attractive, num_repulsive, tolerance, max_iterations, seed, L, q):
+    """The arguments of dca_mf_hopfield_fit, checked as the library checks them -> (selection, p, a, r, tol, max_iterations, seed);
+    ValueError with the reason otherwise.  Either num_patterns (the likelihood selection) or num_attractive / num_repulsive (one
+    may be left None for 0)."""
+    n = int(L) * (int(q) - 1)
+
+    def count(name, v, lo, hi):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s must be an integer" % name)
+        if not lo <= v <= hi:
+            raise ValueError("%s must be between %d and %d" % (name, lo, hi))
+        return int(v)
+
+    explicit = num_attractive is not None or num_repulsive is not None
+    if explicit and num_patterns is not None:
+        raise ValueError("give num_patterns or num_attractive / num_repulsive, not both")
+    if not explicit and num_patterns is None:
+        raise ValueError("give num_patterns or num_attractive / num_repulsive")
+    if explicit:
+        a = count("num_attractive", 0 if num_attractive is None else num_attractive, 0, HOPFIELD_MAX_PER_END)
+        r = count("num_repulsive", 0 if num_repulsive is None else num_repulsive, 0, HOPFIELD_MAX_PER_END)
+        if not 1 <= a + r <= n:
+            raise ValueError("num_attractive + num_repulsive must be between 1 and L (q - 1) = %d" % n)
+        sel, p = HOPFIELD_EXPLICIT, 0
+    else:
+        p = count("num_patterns", num_patterns, 1, min(2 * HOPFIELD_MAX_PER_END, n))
+        sel, a, r = HOPFIELD_LIKELIHOOD, 0, 0
+    if isinstance(tolerance, (bool, str)) or not isinstance(tolerance, (int, float, np.integer, np.floating)) \
+            or not (np.isfinite(tolerance) and tolerance > 0):
+        raise ValueError("tolerance must be a finite number > 0")
+    if isinstance(max_iterations, bool) or not isinstance(max_iterations, (int, np.integer)) or max_iterations < 1:
+        raise ValueError("max_iterations must be >= 1")
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2^64)")
+    return sel, p, a, r, float(tolerance), int(max_iterations), int(seed)
 
 
 def ais_schedule(temperatures, betas=None):
@@ -1367,6 +1425,63 @@ class Context:
         n = L * (q - 1)
         out = np.zeros((n, n), dtype=np.float64)
         check(self._l.dca_mf_corr_from_freqs(self._h, _ptr(reg_fi), _ptr(reg_fij), int(L), int(q), _ptr(out)))
+        return out
+
+    # ---- Hopfield-Potts model (hopfield.hip): afterwards the mf_* entries serve its couplings
+    def mf_hopfield_fit(self, pseudocount, num_patterns=None, num_attractive=None, num_repulsive=None, tol=1e-10, max_iterations=1000,
+                        seed=0):
+        """dca_mf_hopfield_fit -> dict: eigenvalues, gains, residuals float64[p], signs int32[p], patterns float64[p, L, q - 1] (the
+        attractive ones first, descending eigenvalue, then the repulsive ones, ascending), num_attractive, num_repulsive,
+        iterations (attractive, repulsive), converged (bool, bool)."""
+        explicit = num_patterns is None
+        a, r = int(num_attractive or 0), int(num_repulsive or 0)
+        cap = max(a + r if explicit else int(num_patterns), 1)
+        args = HopfieldArgs(HOPFIELD_EXPLICIT if explicit else HOPFIELD_LIKELIHOOD, 0 if explicit else int(num_patterns), a, r,
+                            int(max_iterations), float(tol), int(seed))
+        lam, gain, res = np.zeros(cap), np.zeros(cap), np.zeros(cap)
+        sign = np.zeros(cap, dtype=np.int32)
+        xi = np.zeros((cap, self.L, self.q - 1), dtype=np.float64)
+        info = HopfieldInfo()
+        check(self._l.dca_mf_hopfield_fit(self._h, float(pseudocount), C.byref(args), _ptr(lam), _ptr(gain), _ptr(sign), _ptr(xi),
+                                          _ptr(res), C.byref(info)))
+        p = info.num_attractive + info.num_repulsive
+        return {"eigenvalues": lam[:p], "gains": gain[:p], "signs": sign[:p], "patterns": xi[:p], "residuals": res[:p],
+                "num_attractive": int(info.num_attractive), "num_repulsive": int(info.num_repulsive),
+                "iterations": (int(info.iterations[0]), int(info.iterations[1])),
+                "converged": (bool(info.converged[0]), bool(info.converged[1]))}
+
+    def mf_model_kind(self):
+        kind = C.c_int(0)
+        check(self._l.dca_mf_model_kind(self._h, C.byref(kind)))
+        return kind.value
+
+    def mf_hopfield_couplings(self):
+        n = self.L * (self.q - 1)
+        out = np.zeros((n, n), dtype=np.float64)
+        check(self._l.dca_mf_hopfield_couplings(self._h, _ptr(out)))
+        return out
+
+    def hopfield_project(self, patterns, Q=None):
+        """dca_hopfield_project: patterns float64[p, L, q - 1]; Q uint8[n, L] or None (the alignment) -> float64[n, p]"""
+        xi = np.ascontiguousarray(patterns, dtype=np.float64)
+        per = self.L * (self.q - 1)
+        if xi.size == 0 or xi.size % per:
+            raise ValueError("patterns must hold p x L x (q - 1) = p x %d x %d values, not %d" % (self.L, self.q - 1, xi.size))
+        p = xi.size // per
+        q_ = None if Q is None else np.ascontiguousarray(Q, dtype=np.uint8).reshape(-1, self.L)
+        n = self.N if q_ is None else int(q_.shape[0])
+        out = np.zeros((n, p), dtype=np.float64)
+        check(self._l.dca_hopfield_project(self._h, None if q_ is None else _ptr(q_), 0 if q_ is None else n, p, _ptr(xi),
+                                           _ptr(out) if n else None))
+        return out
+
+    def dense_apply(self, A, V, n=None):
+        """dca_dense_apply: A float64[n, ld] (ld >= n), V float64[n, b] -> A[:, :n] V through the operator kernel of the fit"""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        n = A.shape[0] if n is None else int(n)
+        out = np.zeros((n, V.shape[1]), dtype=np.float64)
+        check(self._l.dca_dense_apply(self._h, _ptr(A), n, A.shape[1], _ptr(V), V.shape[1], _ptr(out)))
         return out
 
     def spd_inverse(self, A):

@@ -1096,6 +1096,62 @@ int dca_mf_run(dca_ctx* ctx, double pseudocount, int apc, double* scores_out, do
     return dca_mf_engine_scores(ctx->mf, apc, scores_out);
 }
 
+// ------------------------------------------------------------------ Hopfield-Potts
+int dca_mf_hopfield_fit(dca_ctx* ctx, double pseudocount, const dca_hopfield_args* args, double* eigenvalues_out, double* gains_out,
+                        int32_t* signs_out, double* patterns_out, double* residuals_out, dca_hopfield_info* info_out)
+{
+    static const char* who = "dca_mf_hopfield_fit";
+    CHECK_CTX(ctx);
+    if (!args || !eigenvalues_out || !gains_out || !signs_out || !patterns_out || !residuals_out || !info_out) { dca_set_error("%s: args or an output is NULL", who); return DCA_ERR_ARG; }
+    if (args->selection != DCA_HOPFIELD_EXPLICIT && args->selection != DCA_HOPFIELD_LIKELIHOOD) { dca_set_error("%s: selection %d is neither explicit nor likelihood", who, args->selection); return DCA_ERR_ARG; }
+    if (args->selection == DCA_HOPFIELD_EXPLICIT &&
+        (args->num_attractive < 0 || args->num_attractive > 64 || args->num_repulsive < 0 || args->num_repulsive > 64)) {
+        dca_set_error("%s: num_attractive %d or num_repulsive %d is outside 0 .. 64", who, args->num_attractive, args->num_repulsive);
+        return DCA_ERR_ARG;
+    }
+    if (args->selection == DCA_HOPFIELD_LIKELIHOOD && (args->num_patterns < 1 || args->num_patterns > 128)) { dca_set_error("%s: num_patterns %d is outside 1 .. 128", who, args->num_patterns); return DCA_ERR_ARG; }
+    if (!(args->tol > 0.0)) { dca_set_error("%s: tol %g must be > 0", who, args->tol); return DCA_ERR_ARG; }
+    if (args->max_iterations < 1) { dca_set_error("%s: max_iterations %d < 1", who, args->max_iterations); return DCA_ERR_ARG; }
+    if (!(pseudocount >= 0.0 && pseudocount < 1.0)) { dca_set_error("%s: pseudocount %g is outside [0, 1)", who, pseudocount); return DCA_ERR_ARG; }
+    DCA_TRY(need_mf(ctx));
+    return dca_mf_engine_hopfield_fit(ctx->mf, pseudocount, args, eigenvalues_out, gains_out, signs_out, patterns_out, residuals_out, info_out);
+}
+int dca_mf_model_kind(dca_ctx* ctx, int* kind_out)
+{
+    CHECK_CTX(ctx);
+    if (!kind_out) return DCA_ERR_ARG;
+    *kind_out = ctx->mf ? dca_mf_engine_model_kind(ctx->mf) : DCA_MF_MODEL_NONE;
+    return DCA_OK;
+}
+int dca_mf_hopfield_couplings(dca_ctx* ctx, double* out)
+{
+    CHECK_CTX(ctx);
+    if (!out) return DCA_ERR_ARG;
+    DCA_TRY(need_mf(ctx));
+    return dca_mf_engine_hopfield_couplings(ctx->mf, out);
+}
+int dca_hopfield_project(dca_ctx* ctx, const uint8_t* Q, int nq, int p, const double* patterns, double* out)
+{
+    CHECK_CTX(ctx);
+    if (!patterns || !out) { dca_set_error("dca_hopfield_project: patterns or out is NULL"); return DCA_ERR_ARG; }
+    if (p < 1) { dca_set_error("dca_hopfield_project: p %d < 1", p); return DCA_ERR_ARG; }
+    if (Q && nq < 1) { dca_set_error("dca_hopfield_project: nq %d < 1", nq); return DCA_ERR_ARG; }
+    if (!ctx->dX) { dca_set_error("dca_hopfield_project: dca_set_msa first"); return DCA_ERR_STATE; }
+    // the patterns on all q states, a zero row for the gap, and no offsets: the projection kernel of the principal components
+    const int L = ctx->L, q = ctx->q, qm = q - 1;
+    std::vector<double> full((size_t)p * L * q, 0.0), zero(p, 0.0);
+    for (int m = 0; m < p; ++m)
+        for (int i = 0; i < L; ++i)
+            memcpy(full.data() + ((size_t)m * L + i) * q, patterns + ((size_t)m * L + i) * qm, (size_t)qm * sizeof(double));
+    return dca_pca_project_impl(ctx, Q, nq, p, full.data(), zero.data(), out);
+}
+int dca_dense_apply(dca_ctx* ctx, const double* A, int n, int ld, const double* V, int b, double* Y)
+{
+    CHECK_CTX(ctx);
+    if (!A || !V || !Y || n < 1 || ld < n || b < 1 || b > 72) { dca_set_error("dca_dense_apply: a NULL array, n %d < 1, ld %d < n or b %d outside 1 .. 72", n, ld, b); return DCA_ERR_ARG; }
+    return dca_dense_apply_impl(ctx, A, n, ld, V, b, Y);
+}
+
 int dca_spd_inverse(dca_ctx* ctx, const double* A, int n, double* Ainv_out)
 {
     CHECK_CTX(ctx);

@@ -382,6 +382,25 @@ int dca_pca_fit_impl(dca_ctx* ctx, int k, double tol, int max_iterations, uint64
 int dca_pca_project_impl(dca_ctx* ctx, const uint8_t* Q, int nq, int k, const double* components, const double* offsets,
                          double* proj_out);
 
+// the small block algebra of the fit for hopfield.hip: pca.hip's init, Gram + sum and rotate kernels as the fit launches them
+// (blocks are rows x b row-major; dGpart holds dca_pca_small_chunks(rows) * ba * bb doubles)
+int dca_pca_small_chunks(int rows);
+int dca_pca_small_init(dca_ctx* ctx, const char* who, double* dV, int rows, int b, uint64_t seed);
+int dca_pca_small_gram(dca_ctx* ctx, const char* who, const double* dA, int ba, const double* dB, int bb, int rows, bool diag,
+                       double* dGpart, double* dOut);
+int dca_pca_small_rotate(dca_ctx* ctx, const char* who, const double* dA, const double* dT1, const double* dB, const double* dT2, int rows,
+                         int b, double* dOut);
+
+// ---- hopfield.hip : the kernels of the Hopfield-Potts fit (dca_mf_engine_hopfield_fit drives them)
+int dca_hp_factor(dca_ctx* ctx, const double* dC, int L, int qm, int ld, double* dRinv);       // L * qm * qm doubles
+int dca_hp_whiten(dca_ctx* ctx, double* dC, int L, int qm, int ld, const double* dRinv);                   // in place
+int dca_hp_apply(dca_ctx* ctx, const double* dA, int n, int ld, const double* dV, int b, double* dY, double* dPart);
+int dca_hp_eigs(dca_ctx* ctx, const double* dA, int n, int ld, int k, double tol, int max_iterations, uint64_t seed, double* theta_out,
+                double* res_out, DevBuf<double>* dV, int* iterations_out, int* converged_out);
+int dca_hp_residuals(dca_ctx* ctx, const double* dA, int n, int ld, const double* dV, int b, const double* lambda, double* res_out);
+int dca_hp_assemble(dca_ctx* ctx, const double* xi, const int32_t* sign, int p, int n, double* dJ, int ld);
+int dca_dense_apply_impl(dca_ctx* ctx, const double* A, int n, int ld, const double* V, int b, double* Y);
+
 int dca_di_from_arrays_impl(dca_ctx* ctx, const double* couplings, int layout, const double* reg_fi, int L, int q,
                             double* fields_out, double* di_out, const double* fields_in = nullptr);
 
@@ -416,6 +435,11 @@ int dca_mf_engine_potts_source(MfEngine*, PottsSource* out, DevBuf<double>* dH_o
 // data statistics of a Boltzmann-learning run from this engine's weighted counts (dca_plm_bm_begin): device outputs
 // fi (L*q) = (1 - lambda) * f_i + lambda / q and fij (pairs*q*q, pair order, gap included) = (1 - lambda) * f_ij + lambda / q^2
 int dca_mf_engine_bm_freqs(MfEngine*, double lambda, double* dFi, double* dFij);
+// the Hopfield-Potts fit (dca_mf_hopfield_fit; arguments checked in capi.cpp): afterwards the engine's J is the Hopfield-Potts one
+int dca_mf_engine_hopfield_fit(MfEngine*, double theta, const dca_hopfield_args* args, double* eigenvalues_out, double* gains_out,
+                               int32_t* signs_out, double* patterns_out, double* residuals_out, dca_hopfield_info* info_out);
+int dca_mf_engine_model_kind(const MfEngine*);
+int dca_mf_engine_hopfield_couplings(MfEngine*, double* out);
 
 // ---- cholinv.hip : scale * inverse of an SPD matrix on the device (f64 MFMA)
 // dA: n x n row-major (ld = n), n multiple of 64; destroyed (holds the triangular factor's inverse afterwards).

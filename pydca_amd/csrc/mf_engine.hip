@@ -11,6 +11,11 @@
 // Craw comes out exactly symmetric because both (i,a,j,b) and (j,b,i,a) add the same
 // weights in the same order.
 #include "dca_internal.h"
+#include "hopfield_plan.h"
+#include "pca_host.h"
+
+#include <algorithm>
+#include <cmath>
 
 namespace {
 
@@ -328,6 +333,7 @@ struct MfEngine {
     DevBuf<double> dCnt1, dCraw, dFi, dC, dWork;
     double* dJ = nullptr;           // inside dWork
     bool have_counts = false, have_corr = false, have_J = false;
+    bool hopfield = false;          // the J held is the Hopfield-Potts one of dca_mf_engine_hopfield_fit, not -inv(C)
     bool corr_on_device = false;    // dC holds the correlation matrix (the factorisation of dca_mf_engine_couplings destroys it)
     double theta = 0.0;
     DevBuf<double> dRegFi;
@@ -476,6 +482,7 @@ int dca_mf_engine_corr(MfEngine* m, double theta, double* corr_out)
     DCA_TRY(mf_build_corr(m, theta));
     m->have_corr = true;
     m->have_J = false;
+    m->hopfield = false;
     m->theta = theta;
     if (corr_out) return copy_out_square(m, m->dC, corr_out);
     return DCA_OK;
@@ -493,6 +500,7 @@ int dca_mf_engine_couplings(MfEngine* m, double* out)
     int info = 0;
     m->corr_on_device = false;
     m->have_J = false;
+    m->hopfield = false;
     DCA_TRY(dca_spd_inverse_device(ctx, m->dC, m->np, m->dWork, &info, -1.0, &m->dJ));
     if (info != 0) {
         dca_set_error("Singular matrix: the correlation matrix is not positive definite (pivot %d)", info);
@@ -616,9 +624,124 @@ int dca_mf_engine_pair_couplings(MfEngine* m, const int* pairs, int npairs, int 
     return dca_pair_blocks(m->ctx, m->dJ, 1, DCA_F64, m->L, m->q, m->np, pairs, npairs, shift, out);
 }
 
+// The Hopfield-Potts fit (hopfield.hip): counts -> C -> per-site factors -> Gamma (in dC, a copy in the
+// fit's own dGamma) -> Gamma^-1 (dca_spd_inverse_device destroys dC, as for the mean-field couplings) -> the largest eigenpairs of Gamma and
+// of Gamma^-1 -> selection -> J into the engine's coupling buffer, where Gamma^-1 was.
+int dca_mf_engine_hopfield_fit(MfEngine* m, double theta, const dca_hopfield_args* args, double* eigenvalues_out, double* gains_out,
+                               int32_t* signs_out, double* patterns_out, double* residuals_out, dca_hopfield_info* info_out)
+{
+    static const char* who = "dca_mf_hopfield_fit";
+    dca_ctx* ctx = m->ctx;
+    if (m->winCount >= 0 || m->hook || m->native_reduce) {
+        dca_set_error("%s: a row window, a reduce hook or a native communicator is set: the fit runs on one GPU", who);
+        return DCA_ERR_STATE;
+    }
+    const int n = m->n, np = m->np, qm = m->q - 1, L = m->L;
+    const bool likelihood = args->selection == DCA_HOPFIELD_LIKELIHOOD;
+    const int p = likelihood ? args->num_patterns : args->num_attractive + args->num_repulsive;
+    if (p < 1 || p > n) { dca_set_error("%s: %d patterns asked for, outside 1 .. n = %d", who, p, n); return DCA_ERR_ARG; }
+    // a likelihood selection needs the gains of up to p patterns of either end before it knows the split
+    const int ka = likelihood ? std::min(p, kHpMaxPerEnd) : args->num_attractive;
+    const int kr = likelihood ? std::min(p, kHpMaxPerEnd) : args->num_repulsive;
+
+    DCA_TRY(mf_counts(m));
+    DCA_TRY(mf_build_corr(m, theta));
+    m->have_corr = true;
+    m->have_J = false;
+    m->hopfield = false;
+    m->theta = theta;
+    const size_t nn = (size_t)np * np;
+    DevBuf<double> dRinv, dGamma;              // dGamma: the whitened matrix (np x np), released when the fit returns
+    HIP_TRY_AS_NOMEM(dRinv.alloc((size_t)L * qm * qm, false), who);
+    DCA_TRY(dca_hp_factor(ctx, m->dC, L, qm, np, dRinv));
+    m->corr_on_device = false;                                     // dC holds Gamma from here on, then the inverse's leftovers
+    DCA_TRY(dca_hp_whiten(ctx, m->dC, L, qm, np, dRinv));          // rows and columns >= n stay the identity block
+    HIP_TRY_AS_NOMEM(dGamma.alloc(nn, false), who);
+    HIP_TRY_AS(hipMemcpyAsync(dGamma, m->dC, nn * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream), who);
+    double* dInv = nullptr;
+    if (kr > 0) {
+        if (!m->dWork) HIP_TRY_AS_NOMEM(m->dWork.alloc(2 * nn, false), who);
+        int info = 0;
+        DCA_TRY(dca_spd_inverse_device(ctx, m->dC, np, m->dWork, &info, 1.0, &dInv));
+        if (info != 0) { dca_set_error("%s: the whitened correlation matrix is not positive definite (pivot %d)", who, info); return DCA_ERR_NOT_SPD; }
+    } else {
+        if (!m->dWork) HIP_TRY_AS_NOMEM(m->dWork.alloc(2 * nn, false), who);
+        dInv = m->dWork.get() + nn;                                 // no inverse: the place of J all the same
+    }
+
+    // the two ends: Ritz values, residuals and Ritz vectors (n x block, in columns)
+    const int ba = hp_block(n, ka), br = hp_block(n, kr);
+    std::vector<double> thA(std::max(ba, 1)), resA(std::max(ba, 1)), thR(std::max(br, 1)), resR(std::max(br, 1)), lamR(std::max(br, 1));
+    std::vector<double> VA, VR;
+    int itA = 0, itR = 0, convA = 1, convR = 1;
+    if (ka > 0) {
+        DevBuf<double> dV;
+        DCA_TRY(dca_hp_eigs(ctx, dGamma, n, np, ka, args->tol, args->max_iterations, args->seed, thA.data(), resA.data(), &dV, &itA, &convA));
+        VA.resize((size_t)n * ba);
+        HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
+        HIP_TRY_AS(hipMemcpy(VA.data(), dV, VA.size() * sizeof(double), hipMemcpyDeviceToHost), who);
+    }
+    if (kr > 0) {
+        DevBuf<double> dV;
+        DCA_TRY(dca_hp_eigs(ctx, dInv, n, np, kr, args->tol, args->max_iterations, args->seed, thR.data(), resR.data(), &dV, &itR, &convR));
+        for (int j = 0; j < br; ++j) lamR[j] = 1.0 / thR[j];
+        DCA_TRY(dca_hp_residuals(ctx, dGamma, n, np, dV, br, lamR.data(), resR.data()));       // on Gamma itself
+        VR.resize((size_t)n * br);
+        HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
+        HIP_TRY_AS(hipMemcpy(VR.data(), dV, VR.size() * sizeof(double), hipMemcpyDeviceToHost), who);
+    }
+
+    int pa = ka, pr = kr;
+    if (likelihood && hp_select_likelihood(thA.data(), ka, lamR.data(), kr, p, &pa, &pr) != 0) {
+        dca_set_error("%s: the %d patterns of largest gain include more than %d of one end", who, p, kHpMaxPerEnd);
+        return DCA_ERR_ARG;
+    }
+
+    // u = R^-T v per site, the sign rule, xi = |1 - 1 / lambda|^1/2 u
+    std::vector<double> Rinv((size_t)L * qm * qm);
+    HIP_TRY_AS(hipStreamSynchronize(ctx->stream), who);
+    HIP_TRY_AS(hipMemcpy(Rinv.data(), dRinv, Rinv.size() * sizeof(double), hipMemcpyDeviceToHost), who);
+    for (int mu = 0; mu < pa + pr; ++mu) {
+        const bool att = mu < pa;
+        const int col = att ? mu : mu - pa, b = att ? ba : br;
+        const double lambda = att ? thA[col] : lamR[col];
+        const std::vector<double>& V = att ? VA : VR;
+        double* u = patterns_out + (size_t)mu * n;
+        for (int i = 0; i < L; ++i)
+            for (int a = 0; a < qm; ++a) {
+                double s = 0.0;
+                for (int c = a; c < qm; ++c) s += Rinv[((size_t)i * qm + c) * qm + a] * V[((size_t)i * qm + c) * b + col];
+                u[(size_t)i * qm + a] = s;
+            }
+        pca_fix_sign((size_t)n, u);
+        const double coef = 1.0 - 1.0 / lambda, scale = std::sqrt(std::fabs(coef));
+        for (int r = 0; r < n; ++r) u[r] *= scale;
+        eigenvalues_out[mu] = lambda;
+        gains_out[mu] = hp_gain(lambda);
+        signs_out[mu] = coef < 0.0 ? -1 : 1;
+        residuals_out[mu] = att ? resA[col] : resR[col];
+    }
+    m->dJ = dInv;
+    DCA_TRY(dca_hp_assemble(ctx, patterns_out, signs_out, pa + pr, n, m->dJ, np));
+    m->have_J = true;
+    m->hopfield = true;
+    info_out->num_attractive = pa; info_out->num_repulsive = pr;
+    info_out->iterations[0] = itA; info_out->iterations[1] = itR;
+    info_out->converged[0] = convA; info_out->converged[1] = convR;
+    return DCA_OK;
+}
+
+int dca_mf_engine_model_kind(const MfEngine* m) { return !m->have_J ? DCA_MF_MODEL_NONE : m->hopfield ? DCA_MF_MODEL_HOPFIELD : DCA_MF_MODEL_MEAN_FIELD; }
+
+int dca_mf_engine_hopfield_couplings(MfEngine* m, double* out)
+{
+    if (!m->have_J || !m->hopfield) { dca_set_error("dca_mf_hopfield_couplings: dca_mf_hopfield_fit first"); return DCA_ERR_STATE; }
+    return copy_out_square(m, m->dJ, out);
+}
+
 // Counts, frequencies, correlation matrix and couplings cached so far were summed under the previous exchange scheme (or the
 // previous weights): they are recomputed by the next query instead of answering for a single shard.
-void dca_mf_engine_invalidate(MfEngine* m) { m->have_counts = m->have_corr = m->have_J = m->corr_on_device = false; m->counts_global = false; }
+void dca_mf_engine_invalidate(MfEngine* m) { m->have_counts = m->have_corr = m->have_J = m->corr_on_device = false; m->counts_global = false; m->hopfield = false; }
 int dca_mf_engine_set_row_window(MfEngine* m, int first, int count)
 {
     if (count < 0) { first = 0; count = -1; }

@@ -265,25 +265,14 @@ struct PcaFit {
         HIP_TRY_AS(hipGetLastError(), who);
         return DCA_OK;
     }
-    // dOut (ba x bb, or ba with diag) = A^T B on the device
+    // dOut (ba x bb, or ba with diag) = A^T B on the device; the launches are dca_pca_small_gram / _rotate below
     int gram(const double* dA, int ba, const double* dB, int bb, bool diag, double* dOut)
     {
-        const int pairs = diag ? ba : ba * bb;
-        ScopedKernelClock kc(ctx, "pca_small");
-        hipLaunchKernelGGL(pca_gram_kernel, dim3(chunks, ceil_div(pairs, kThreads)), dim3(kThreads), 0, ctx->stream, dA, ba, dB, bb, rows,
-                           diag ? 1 : 0, dGpart.get());
-        hipLaunchKernelGGL(pca_sum_kernel, dim3(ceil_div(pairs, kThreads)), dim3(kThreads), 0, ctx->stream, dGpart.get(), chunks, pairs,
-                           dOut);
-        HIP_TRY_AS(hipGetLastError(), who);
-        return DCA_OK;
+        return dca_pca_small_gram(ctx, who, dA, ba, dB, bb, rows, diag, dGpart.get(), dOut);
     }
     int rotate(const double* dA, const double* dTa, const double* dB, const double* dTb, double* dOut)
     {
-        ScopedKernelClock kc(ctx, "pca_small");
-        hipLaunchKernelGGL(pca_rotate_kernel, dim3((unsigned)(((size_t)rows * b + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                           ctx->stream, dA, dTa, dB, dTb, rows, b, dOut);
-        HIP_TRY_AS(hipGetLastError(), who);
-        return DCA_OK;
+        return dca_pca_small_rotate(ctx, who, dA, dTa, dB, dTb, rows, b, dOut);
     }
     // dV <- orthonormalised dV, through the Gram matrix, twice; dR is the scratch block
     int orthonormalise(std::vector<double>& G, std::vector<double>& T)
@@ -301,6 +290,37 @@ struct PcaFit {
 };
 
 }  // namespace
+
+// The small block algebra, for the fit above (PcaFit::gram, ::rotate and the start block) and for hopfield.hip
+int dca_pca_small_chunks(int rows) { return ceil_div(rows, kGramRows); }
+int dca_pca_small_init(dca_ctx* ctx, const char* who, double* dV, int rows, int b, uint64_t seed)
+{
+    hipLaunchKernelGGL(pca_init_kernel, dim3((unsigned)(((size_t)rows * b + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, dV,
+                       rows, b, seed);
+    HIP_TRY_AS(hipGetLastError(), who);
+    return DCA_OK;
+}
+int dca_pca_small_gram(dca_ctx* ctx, const char* who, const double* dA, int ba, const double* dB, int bb, int rows, bool diag,
+                       double* dGpart, double* dOut)
+{
+    const int pairs = diag ? ba : ba * bb, chunks = ceil_div(rows, kGramRows);
+    ScopedKernelClock kc(ctx, "pca_small");
+    hipLaunchKernelGGL(pca_gram_kernel, dim3(chunks, ceil_div(pairs, kThreads)), dim3(kThreads), 0, ctx->stream, dA, ba, dB, bb, rows,
+                       diag ? 1 : 0, dGpart);
+    hipLaunchKernelGGL(pca_sum_kernel, dim3(ceil_div(pairs, kThreads)), dim3(kThreads), 0, ctx->stream, (const double*)dGpart, chunks, pairs,
+                       dOut);
+    HIP_TRY_AS(hipGetLastError(), who);
+    return DCA_OK;
+}
+int dca_pca_small_rotate(dca_ctx* ctx, const char* who, const double* dA, const double* dT1, const double* dB, const double* dT2, int rows,
+                         int b, double* dOut)
+{
+    ScopedKernelClock kc(ctx, "pca_small");
+    hipLaunchKernelGGL(pca_rotate_kernel, dim3((unsigned)(((size_t)rows * b + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream, dA,
+                       dT1, dB, dT2, rows, b, dOut);
+    HIP_TRY_AS(hipGetLastError(), who);
+    return DCA_OK;
+}
 
 int dca_pca_fit_impl(dca_ctx* ctx, int k, double tol, int max_iterations, uint64_t seed, double* eigenvalues_out,
                      double* components_out, double* offsets_out, double* residuals_out, double* total_variance_out,
@@ -363,9 +383,7 @@ int dca_pca_fit_impl(dca_ctx* ctx, int k, double tol, int max_iterations, uint64
         converged = 1;
         HIP_TRY_AS(hipMemsetAsync(S.dV, 0, (size_t)rows * b * sizeof(double), ctx->stream), who);
     } else {
-        hipLaunchKernelGGL(pca_init_kernel, dim3((unsigned)(((size_t)rows * b + kThreads - 1) / kThreads)), dim3(kThreads), 0, ctx->stream,
-                           S.dV.get(), rows, b, seed);
-        HIP_TRY_AS(hipGetLastError(), who);
+        DCA_TRY(dca_pca_small_init(ctx, who, S.dV.get(), rows, b, seed));
         DCA_TRY(S.orthonormalise(H, T));
     }
     while (!zero) {
