@@ -3,7 +3,7 @@
 // min_gain.  The model arrives as a PottsSource and is read in place through the free functions of potts_source.h.
 //
 // Two kernels:
-//   ascent_table_kernel   once per call and block of chains, lane = chain (cond_fields_kernel's style): the local-field table
+//   ascent_table_kernel   once per call and block of chains, lane = chain (cond_fields_kernel's style; the chunk staging is potts_rows.h's): the local-field table
 //                         U_i(a) = h_i(a) + sum over j != i, ascending, of J_ij(a, s_j), a sequential double sum (h first, then j
 //                         ascending: site_conditionals.h's order), for every free site i = f_kappa and state a, written as
 //                         tab[(c * F + kappa) * q + a].  The blocks of row i stream through LDS in double-buffered chunks.
@@ -27,36 +27,6 @@
 #include <vector>
 
 namespace {
-
-// registers <- the blocks of row i at the sites j0 .. j0 + CJ - 1 (site i itself is left out): element e of the chunk is value
-// e % q^2 of the stored block of site j0 + e / q^2, and goes to dst = kk * blk + b * QM + a for the term J_ij(a, b)
-template <typename S, int QM, int R>
-__device__ __forceinline__ void asc_chunk_load(const S* __restrict__ src, int kind, int L, int q, int ld, int i, int j0, int chunkVals,
-                                               uint32_t mqq, uint32_t mq, S (&val)[R], int (&dst)[R])
-{
-    const int qq = q * q, blk = q * QM;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = threadIdx.x + r * kAscInitChains;
-        dst[r] = -1;
-        if (e >= chunkVals) continue;
-        const int kk = fast_div(e, mqq), el = e - kk * qq;
-        const int j = j0 + kk;
-        if (j >= L || j == i) continue;
-        const int hi = fast_div(el, mq), lo = el - hi * q;
-        const int a = j > i ? hi : lo, b = j > i ? lo : hi;          // source order: (a, b) rows for j > i, (b, a) for j < i
-        val[r] = (S)(j > i ? potts_coupling(src, kind, L, q, ld, i, j, a, b) : potts_coupling(src, kind, L, q, ld, j, i, b, a));
-        dst[r] = kk * blk + b * QM + a;
-    }
-}
-
-template <typename S, int R>
-__device__ __forceinline__ void asc_chunk_store(S* __restrict__ buf, const S (&val)[R], const int (&dst)[R])
-{
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-        if (dst[r] >= 0) buf[dst[r]] = val[r];
-}
 
 // The table pass.  grid (F, ceil(nb / 256)); thread = chain c of the block.  LDS: two chunk buffers (CJ blocks of q x QM values
 // of S each).  state: site-major codes st[j * nS + c].  R: chunk elements per thread.
@@ -87,13 +57,13 @@ void ascent_table_kernel(const S* __restrict__ src, int kind, const double* __re
     S val[R];
     int dst[R];
     __syncthreads();
-    asc_chunk_load<S, QM, R>(src, kind, L, q, ld, i, 0, chunkVals, mqq, mq, val, dst);
-    asc_chunk_store<S, R>(buf0, val, dst);
+    row_chunk_load<S, QM, R, kAscInitChains>(src, kind, L, q, ld, AllSites(nullptr, L), i, i, 0, chunkVals, mqq, mq, val, dst);
+    row_chunk_store<S, R>(buf0, val, dst);
     __syncthreads();
 
     for (int t = 0; t < steps; ++t) {
         const int j0 = t * CJ;
-        if (t + 1 < steps) asc_chunk_load<S, QM, R>(src, kind, L, q, ld, i, j0 + CJ, chunkVals, mqq, mq, val, dst);
+        if (t + 1 < steps) row_chunk_load<S, QM, R, kAscInitChains>(src, kind, L, q, ld, AllSites(nullptr, L), i, i, j0 + CJ, chunkVals, mqq, mq, val, dst);
         const S* cur = buf0 + (t & 1) * bufVals;
         if (live) {
 #pragma unroll 1
@@ -102,6 +72,7 @@ void ascent_table_kernel(const S* __restrict__ src, int kind, const double* __re
                 if (j >= L) break;
                 if (j == i) continue;
                 const S* row = cur + jj * blk + (int)state[(size_t)j * nS + c] * QM;
+                // add_row's text, inline: through the helper this kernel alone compiled to other instructions
                 if constexpr (sizeof(S) == 4) {
 #pragma unroll
                     for (int a = 0; a < QM; a += 4) {
@@ -117,7 +88,7 @@ void ascent_table_kernel(const S* __restrict__ src, int kind, const double* __re
                 }
             }
         }
-        if (t + 1 < steps) asc_chunk_store<S, R>(buf0 + ((t + 1) & 1) * bufVals, val, dst);
+        if (t + 1 < steps) row_chunk_store<S, R>(buf0 + ((t + 1) & 1) * bufVals, val, dst);
         __syncthreads();
     }
     if (live) {
@@ -278,16 +249,7 @@ int dca_potts_ascend(dca_ctx* ctx, const PottsSource& ps, const uint8_t* X, int 
                       path_gain_out ? "given" : "NULL");
         return DCA_ERR_ARG;
     }
-    if (F < 0 || F > L || (F > 0 && !free_sites)) {
-        dca_set_error("%s: num_free %d outside [0, %d], or free_sites NULL", who, F, L);
-        return DCA_ERR_ARG;
-    }
-    for (int k = 0; k < F; ++k) {
-        if (free_sites[k] < 0 || free_sites[k] >= L || (k > 0 && free_sites[k] <= free_sites[k - 1])) {
-            dca_set_error("%s: free_sites[%d] = %d is outside [0, %d) or not above its predecessor", who, k, (int)free_sites[k], L);
-            return DCA_ERR_ARG;
-        }
-    }
+    DCA_TRY(dca_check_free_sites(free_sites, F, L, who));
     if (n == 0) return DCA_OK;
     DCA_TRY(dca_check_codes(X, (size_t)n * L, q, "ascend: X "));
 

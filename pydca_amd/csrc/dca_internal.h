@@ -263,6 +263,9 @@ int dca_potts_sample_conditional(dca_ctx* ctx, const PottsSource& ps, int n, int
                                  uint64_t first_sweep, double beta, const int32_t* free_sites, int num_free,
                                  const uint8_t* initial /* host n*L */, int random_start, uint8_t* out /* host n*L */);
 
+// DCA_ERR_ARG unless free_sites holds F indices of [0, L), strictly ascending (F in [0, L]); `who` opens the message
+int dca_check_free_sites(const int32_t* free_sites, int F, int L, const char* who);
+
 // ---- interaction.hip : inter-protein energies of host rows XA (nA x split) and XB (nB x (L - split)) in G groups
 // (dca_plm_interaction_energies semantics; all arguments checked here).  out: host.
 int dca_potts_interaction_energies(dca_ctx* ctx, const PottsSource& ps, int split, const uint8_t* XA, int nA, const uint8_t* XB, int nB,

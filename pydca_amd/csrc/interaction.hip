@@ -8,12 +8,13 @@
 // with Jt the stored block (gauge 0) or its zero-sum form over all q states, kept in double (gauge 1).
 //
 // Two kernels (geometry: interaction_plan.h):
-//   cross_fields_kernel   the geometry of cond_fields_kernel (sample_conditional.hip): grid (blocks of 256 A-sequences,
+//   cross_fields_kernel   the geometry of cond_fields_kernel (sample_conditional.hip; its staging, potts_rows.h, is not shared:
+//                         see below): grid (blocks of 256 A-sequences,
 //                         B-site j), thread = A-sequence with QM double accumulators, the blocks (i, LA + j) of CJ A-sites
 //                         staged through LDS in double-buffered chunks (the next chunk's loads are in flight in registers while
 //                         the current one is summed).  The blocks are staged as doubles, row a holding Jt(a, .) padded to QM
 //                         values; with gauge 1 the shift is applied in place while the block sits in LDS.  Output
-//                         phi[(m * LB + j) * q + b].
+//                         phi[(m * LB + j) * q + b].  Doubles staged untransposed and a gauge shift in LDS: a body of its own.
 //   cross_energy_kernel   one workgroup per item (a run of A-rows and a window over each row's B-partners); the rows' phi
 //                         sits in LDS a chunk of sites at a time, the B-codes are read site-major as in energy.hip, pair
 //                         p of the item is summed by thread p % 256 in slot p / 256; the running sums stay in registers across

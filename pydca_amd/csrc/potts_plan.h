@@ -84,7 +84,7 @@ SitePlan site_plan_t(int q)
 
 inline SitePlan site_plan(int q, size_t elem) { return elem == 4 ? site_plan_t<float>(q) : site_plan_t<double>(q); }
 
-// ---- sample.hip: gibbs_sweep_kernel<S, QM, RES, R, INTERP>
+// ---- sample.hip: gibbs_sweep_kernel<S, QM, RES, R, MODE>
 constexpr int kSThreads = 256;                    // 4 waves, 64 chains
 constexpr int kSChains = 64;
 constexpr int kSResidentL = 512;                  // chain codes in LDS up to 32 KiB
@@ -115,9 +115,9 @@ constexpr size_t kCFieldBudget = (size_t)1 << 30; // the field buffer of one blo
 // chunk elements per thread of the field pass: half the sweep's, every lane holds all QM accumulators there
 constexpr int cond_field_regs(size_t elem) { return sample_regs(elem) / 2; }
 
-// The sweep is the plain sweep's at F sites (the chunks run over the free positions, the free sites' codes sit in LDS up to
-// kSResidentL of them, and then the site list follows them there: F ints); the field pass stages chunks of CJF = CJ / 2 blocks
-// through two buffers and keeps nothing else in LDS.
+// The sweep's geometry is the plain sweep's at F sites (the chunks run over the free positions, the free sites' codes sit in LDS up
+// to kSResidentL of them, and then the site list follows them there: F ints); the field pass
+// stages chunks of CJF = CJ / 2 blocks through two buffers and keeps nothing else in LDS.
 struct CondSampleGeom { int QM, CJ, CJF; bool res; size_t lds, ldsFields; };
 
 inline CondSampleGeom cond_sample_geometry(int F, int q, size_t elem)

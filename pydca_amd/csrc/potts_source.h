@@ -25,8 +25,9 @@ __host__ __device__ __forceinline__ size_t pair_index(int L, int i, int j)
 // floor(e / d) for e * d < 2^32: m = floor(2^32 / d) + 1
 __device__ __forceinline__ int fast_div(int e, uint32_t m) { return (int)__umulhi((uint32_t)e, m); }
 
-// The two layouts.  Free functions for the two kernels that keep the view's members as __restrict__ scalar parameters
-// (energy_pairs_kernel, gibbs_sweep_kernel: at their register limit the allocator's result moved when they read a struct).
+// The two layouts.  Free functions for the kernels that keep the view's members as __restrict__ scalar parameters
+// (energy_pairs_kernel, gibbs_sweep_kernel: at their register limit the allocator's result moved when they read a struct)
+// and for the row staging of the other lane = chain kernels (potts_rows.h).
 template <typename S>
 __device__ __forceinline__ double potts_field(const S* src, const double* mfh, int kind, int q, int i, int a)
 {

@@ -8,7 +8,7 @@
 //                        J_ij(a, s_j), a sequential double sum (site_conditionals.h's order: h first, then j ascending), for
 //                        every free site i = f_kappa and state a, written as fld[(kappa * q + a) * nS + c].  With no clamped
 //                        site it is the widened h.
-//   cond_sweep_kernel    one launch per sweep: gibbs_sweep_kernel's geometry (64 chains per workgroup, 4 waves, wave w sums
+//   cond_sweep_kernel    one launch per sweep (the staging and the row add: potts_rows.h): gibbs_sweep_kernel's geometry (64 chains per workgroup, 4 waves, wave w sums
 //                        the positions k = w (mod 4), double-buffered chunks of CJ transposed blocks through LDS, the partials
 //                        meet in LDS in ascending w, wave 0 draws) with the chunk loop over the free POSITIONS k: the block
 //                        read is the one of the site j = f_k, in place, and wave 0 starts from fld instead of the field.  So
@@ -27,60 +27,6 @@
 #include <vector>
 
 namespace {
-
-static_assert(kCFieldChains == kSThreads, "both kernels stage a chunk with 256 threads");
-
-// registers <- the blocks of row i at the positions k0 .. k0 + CJ - 1 of `list` (count sites, ascending; the position `self`
-// is left out): element e of the chunk is value e % q^2 of the stored block of position k0 + e / q^2, and goes to
-// dst = kk * blk + b * QM + a for the term J_ij(a, b), so that a lane reads J(., s_j) as QM contiguous values
-template <typename S, int QM, int R>
-__device__ __forceinline__ void chunk_load(const S* __restrict__ src, int kind, int L, int q, int ld, const int* __restrict__ list,
-                                           int count, int self, int i, int k0, int chunkVals, uint32_t mqq, uint32_t mq,
-                                           S (&val)[R], int (&dst)[R])
-{
-    const int qq = q * q, blk = q * QM;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int e = threadIdx.x + r * kSThreads;
-        dst[r] = -1;
-        if (e >= chunkVals) continue;
-        const int kk = fast_div(e, mqq), el = e - kk * qq;
-        const int k = k0 + kk;
-        if (k >= count || k == self) continue;
-        const int j = list[k];
-        const int hi = fast_div(el, mq), lo = el - hi * q;
-        const int a = j > i ? hi : lo, b = j > i ? lo : hi;          // source order: (a, b) rows for j > i, (b, a) for j < i
-        val[r] = (S)(j > i ? potts_coupling(src, kind, L, q, ld, i, j, a, b) : potts_coupling(src, kind, L, q, ld, j, i, b, a));
-        dst[r] = kk * blk + b * QM + a;
-    }
-}
-
-template <typename S, int R>
-__device__ __forceinline__ void chunk_store(S* __restrict__ buf, const S (&val)[R], const int (&dst)[R])
-{
-#pragma unroll
-    for (int r = 0; r < R; ++r)
-        if (dst[r] >= 0) buf[dst[r]] = val[r];
-}
-
-// u[a] += row[a], a < QM, every term widened to double
-template <typename S, int QM>
-__device__ __forceinline__ void add_row(double (&u)[QM], const S* __restrict__ row)
-{
-    if constexpr (sizeof(S) == 4) {
-#pragma unroll
-        for (int a = 0; a < QM; a += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(row + a);
-            u[a] += (double)v.x; u[a + 1] += (double)v.y; u[a + 2] += (double)v.z; u[a + 3] += (double)v.w;
-        }
-    } else {
-#pragma unroll
-        for (int a = 0; a < QM; a += 2) {
-            const double2 v = *reinterpret_cast<const double2*>(row + a);
-            u[a] += v.x; u[a + 1] += v.y;
-        }
-    }
-}
 
 // tag-1 start of the free sites: s_i = floor(U * q), counter (chain, 0, i, 1) with the site index i; chains past n keep code 0
 __global__ void cond_random_start_kernel(int n, int q, int nS, const int* __restrict__ freeS, int F, uint64_t seed, uint64_t first_chain,
@@ -125,14 +71,14 @@ void cond_fields_kernel(const S* __restrict__ src, int kind, const double* __res
     int dst[R];
     __syncthreads();
     if (steps > 0) {
-        chunk_load<S, QM, R>(src, kind, L, q, ld, clamped, nC, -1, i, 0, chunkVals, mqq, mq, val, dst);
-        chunk_store<S, R>(buf0, val, dst);
+        row_chunk_load<S, QM, R, kCFieldChains>(src, kind, L, q, ld, ListedSites(clamped, nC), -1, i, 0, chunkVals, mqq, mq, val, dst);
+        row_chunk_store<S, R>(buf0, val, dst);
     }
     __syncthreads();
 
     for (int t = 0; t < steps; ++t) {
         const int k0 = t * CJ;
-        if (t + 1 < steps) chunk_load<S, QM, R>(src, kind, L, q, ld, clamped, nC, -1, i, k0 + CJ, chunkVals, mqq, mq, val, dst);
+        if (t + 1 < steps) row_chunk_load<S, QM, R, kCFieldChains>(src, kind, L, q, ld, ListedSites(clamped, nC), -1, i, k0 + CJ, chunkVals, mqq, mq, val, dst);
         const S* cur = buf0 + (t & 1) * bufVals;
         if (live) {
 #pragma unroll 1
@@ -142,7 +88,7 @@ void cond_fields_kernel(const S* __restrict__ src, int kind, const double* __res
                 add_row<S, QM>(u, cur + jj * blk + (int)state[(size_t)j * nS + c] * QM);
             }
         }
-        if (t + 1 < steps) chunk_store<S, R>(buf0 + ((t + 1) & 1) * bufVals, val, dst);
+        if (t + 1 < steps) row_chunk_store<S, R>(buf0 + ((t + 1) & 1) * bufVals, val, dst);
         __syncthreads();
     }
     if (live) {
@@ -189,13 +135,13 @@ void cond_sweep_kernel(const S* __restrict__ src, int kind, int L, int q, int ld
     // registers <- the chunk of step t (position t / nch, blocks of the positions k0 .. k0 + CJ - 1)
     auto load = [&](int t) {
         const int kappa = t / nch, k0 = (t - kappa * nch) * CJ;
-        chunk_load<S, QM, R>(src, kind, L, q, ld, sites, F, kappa, sites[kappa], k0, chunkVals, mqq, mq, val, dst);
+        row_chunk_load<S, QM, R, kSThreads>(src, kind, L, q, ld, ListedSites(sites, F), kappa, sites[kappa], k0, chunkVals, mqq, mq, val, dst);
     };
     auto code = [&](int k) -> int { return RES ? stL[k * kSChains + lane] : state[(size_t)sites[k] * nS + c0 + lane]; };
 
     __syncthreads();
     load(0);
-    chunk_store<S, R>(buf0, val, dst);
+    row_chunk_store<S, R>(buf0, val, dst);
     __syncthreads();
 
     double u[QM];
@@ -213,7 +159,7 @@ void cond_sweep_kernel(const S* __restrict__ src, int kind, int L, int q, int ld
             if (k == kappa) continue;
             add_row<S, QM>(u, cur + jj * blk + code(k) * QM);
         }
-        if (t + 1 < steps) chunk_store<S, R>(buf0 + ((t + 1) & 1) * bufVals, val, dst);
+        if (t + 1 < steps) row_chunk_store<S, R>(buf0 + ((t + 1) & 1) * bufVals, val, dst);
         if (ch == nch - 1) {                                  // position kappa complete: S_1, S_2, S_3 join wave 0's c + S_0 in order
             for (int w = 1; w < 4; ++w) {
                 if (wave == w)
@@ -307,6 +253,21 @@ hipError_t run_block(dca_ctx* ctx, const CondSampleGeom& g, const PottsView<S>& 
 
 }  // namespace
 
+int dca_check_free_sites(const int32_t* free_sites, int F, int L, const char* who)
+{
+    if (F < 0 || F > L || (F > 0 && !free_sites)) {
+        dca_set_error("%s: num_free %d outside [0, %d], or free_sites NULL", who, F, L);
+        return DCA_ERR_ARG;
+    }
+    for (int k = 0; k < F; ++k) {
+        if (free_sites[k] < 0 || free_sites[k] >= L || (k > 0 && free_sites[k] <= free_sites[k - 1])) {
+            dca_set_error("%s: free_sites[%d] = %d is outside [0, %d) or not above its predecessor", who, k, (int)free_sites[k], L);
+            return DCA_ERR_ARG;
+        }
+    }
+    return DCA_OK;
+}
+
 int dca_potts_sample_conditional(dca_ctx* ctx, const PottsSource& ps, int n, int sweeps, uint64_t seed, uint64_t first_chain,
                                  uint64_t first_sweep, double beta, const int32_t* free_sites, int num_free, const uint8_t* initial,
                                  int random_start, uint8_t* out)
@@ -318,16 +279,7 @@ int dca_potts_sample_conditional(dca_ctx* ctx, const PottsSource& ps, int n, int
                       out ? "given" : "NULL");
         return DCA_ERR_ARG;
     }
-    if (F < 0 || F > L || (F > 0 && !free_sites)) {
-        dca_set_error("%s: num_free %d outside [0, %d], or free_sites NULL", who, F, L);
-        return DCA_ERR_ARG;
-    }
-    for (int k = 0; k < F; ++k) {
-        if (free_sites[k] < 0 || free_sites[k] >= L || (k > 0 && free_sites[k] <= free_sites[k - 1])) {
-            dca_set_error("%s: free_sites[%d] = %d is outside [0, %d) or not above its predecessor", who, k, (int)free_sites[k], L);
-            return DCA_ERR_ARG;
-        }
-    }
+    DCA_TRY(dca_check_free_sites(free_sites, F, L, who));
     if (n == 0) return DCA_OK;
     DCA_TRY(dca_check_codes(initial, (size_t)n * L, q, "sample_conditional: initial "));
 

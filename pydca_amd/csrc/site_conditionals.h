@@ -13,7 +13,7 @@
 // to QM values: a lane reads it as QM contiguous values (ds_read_b128).  The chunk's query codes (CJ x 512 bytes of the
 // site-major copy) travel with it.  The next chunk's loads are in flight in registers while the current one is summed.
 #pragma once
-#include "dca_internal.h"
+#include "potts_rows.h"      // add_row (and dca_internal.h)
 
 #include <functional>
 #include <type_traits>
@@ -135,22 +135,8 @@ __device__ __forceinline__ void site_conditional_body(const Policy& P, int i, in
             if (j >= nb) break;
             if (P.skip(j)) continue;
 #pragma unroll
-            for (int p = 0; p < kSitePerLane; ++p) {
-                const S* row = cur + jj * blk + (int)cc[jj * kSiteSeqBlock + p * kSiteThreads + tid] * QM;
-                if constexpr (sizeof(S) == 4) {
-#pragma unroll
-                    for (int a = 0; a < QM; a += 4) {
-                        const float4 v = *reinterpret_cast<const float4*>(row + a);
-                        u[p][a] += (double)v.x; u[p][a + 1] += (double)v.y; u[p][a + 2] += (double)v.z; u[p][a + 3] += (double)v.w;
-                    }
-                } else {
-#pragma unroll
-                    for (int a = 0; a < QM; a += 2) {
-                        const double2 v = *reinterpret_cast<const double2*>(row + a);
-                        u[p][a] += v.x; u[p][a + 1] += v.y;
-                    }
-                }
-            }
+            for (int p = 0; p < kSitePerLane; ++p)
+                add_row<S, QM>(u[p], cur + jj * blk + (int)cc[jj * kSiteSeqBlock + p * kSiteThreads + tid] * QM);
         }
         if (t + 1 < steps) store(t + 1);
         __syncthreads();

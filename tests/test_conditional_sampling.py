@@ -22,7 +22,7 @@ from pydca_amd.meanfield_dca.meanfield_dca import MeanFieldDCA, MeanFieldDCAExce
 from pydca_amd.plmdca.plmdca import PlmDCA, PlmDCAException
 from potts_audit_reference import MARGIN_FACTOR, eps_draw, model_sabs
 from test_conditional_sampling_host import cond_gibbs_ref
-from test_potts_sampling import _g_test, mf_context, mf_model, plm_context
+from test_potts_sampling import _g_test, mf_context, mf_model, mf_random_context, plm_context
 
 pytestmark = pytest.mark.gpu
 
@@ -30,18 +30,6 @@ pytestmark = pytest.mark.gpu
 def backgrounds(n, L, q, seed):
     """a different background per chain"""
     return np.random.default_rng([seed, n, L, q]).integers(0, q, size=(n, L), dtype=np.uint8)
-
-
-def mf_random_context(L, q, seed, N=200):
-    """an mf model of any alphabet: random columns, each with its own state frequencies"""
-    rng = np.random.default_rng([seed, L, q])
-    X = np.stack([rng.choice(q, size=N, p=rng.dirichlet(np.ones(q))).astype(np.uint8) for _ in range(L)], axis=1)
-    ctx = _lib.Context(0, _lib.DCA_F64)
-    ctx.set_msa(X, q)
-    ctx.compute_weights(0.8, _lib.DCA_F64)
-    ctx.mf_corr_mat(0.5, want=False)
-    h, Jp = mf_model(ctx.mf_couplings(), ctx.mf_fields(), L, q)
-    return ctx, h, Jp
 
 
 def check_against_restatement(call, h, Jp, X0, free, sweeps, seed, beta=1.0, randomize=True, first_chain=0, first_sweep=0):
@@ -134,6 +122,15 @@ def test_free_codes_beyond_lds():
     free = np.setdiff1d(np.arange(L), np.arange(3, 600, 7)[:80])
     assert free.size == 520 and free[0] == 0 and free[-1] == L - 1
     check_against_restatement(ctx.plm_sample_conditional, h, Jp, backgrounds(64, L, q, 0), free, 2, seed=3)
+    ctx.close()
+
+
+def test_free_codes_beyond_lds_float64():
+    """the same list over a float64 model: the sweep kernel's other element type with the codes and the list in global memory"""
+    L, q = 600, 5
+    ctx, h, Jp = plm_context(L, q, _lib.DCA_F64, 601, sigma=0.05, N=16)
+    free = np.setdiff1d(np.arange(L), np.arange(3, 600, 7)[:80])
+    check_against_restatement(ctx.plm_sample_conditional, h, Jp, backgrounds(64, L, q, 1), free, 2, seed=4)
     ctx.close()
 
 

@@ -102,6 +102,18 @@ def mf_context(tag="mf_toy_protein"):
     return ctx, h, Jp, X
 
 
+def mf_random_context(L, q, seed, N=200):
+    """an mf model of any alphabet: random columns, each with its own state frequencies"""
+    rng = np.random.default_rng([seed, L, q])
+    X = np.stack([rng.choice(q, size=N, p=rng.dirichlet(np.ones(q))).astype(np.uint8) for _ in range(L)], axis=1)
+    ctx = _lib.Context(0, _lib.DCA_F64)
+    ctx.set_msa(X, q)
+    ctx.compute_weights(0.8, _lib.DCA_F64)
+    ctx.mf_corr_mat(0.5, want=False)
+    h, Jp = mf_model(ctx.mf_couplings(), ctx.mf_fields(), L, q)
+    return ctx, h, Jp
+
+
 # ---------------------------------------------------------------- 1. exact trajectories
 @pytest.mark.parametrize("q,L", [(5, 23), (21, 37)])
 @pytest.mark.parametrize("prec", [_lib.DCA_F32, _lib.DCA_F64])

@@ -21,7 +21,7 @@ from pydca_amd.fasta_reader import fasta_reader
 from pydca_amd.meanfield_dca.meanfield_dca import MeanFieldDCA, MeanFieldDCAException
 from pydca_amd.plmdca.plmdca import PlmDCA, PlmDCAException
 from tempered_reference import exact_distribution, other_basin_share, tempered_ref, two_basin_model
-from test_potts_sampling import _g_test, mf_context, plm_context
+from test_potts_sampling import _g_test, mf_context, mf_random_context, plm_context
 
 pytestmark = pytest.mark.gpu
 
@@ -61,6 +61,13 @@ def test_plm_without_exchange_is_the_plain_sampler(q, L, prec):
 def test_mf_without_exchange_is_the_plain_sampler():
     ctx, _h, _Jp, X = mf_context("mf_toy_rna")
     check_no_exchange(ctx.mf_sample_tempered, ctx.mf_sample, X.shape[1])
+    ctx.close()
+
+
+def test_mf_largest_alphabet_without_exchange_is_the_plain_sampler():
+    """q = 32: the tempered sweep with 32 accumulators per lane, which no other case reaches"""
+    ctx, _h, _Jp = mf_random_context(10, 32, 5)
+    check_no_exchange(ctx.mf_sample_tempered, ctx.mf_sample, 10)
     ctx.close()
 
 
